@@ -8,7 +8,11 @@ N > 1 by ONE RCCL sum-reduce of the W*H*3 accumulator to rank 0.  Strong scaling
 work is fixed as N grows.  The scene is packed by the product's Node host
 (node/bin/pt-pack.js) before timing; scene upload is outside the timed region.
 
-Prints ONE JSON line on rank 0 (contract in the task statement), with `roofline` for the
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up,
+times the steps and prints the headline fields (metric, value, unit, ms_per_step, ...) and the
+configuration; --dump-outputs DIR also writes the last timed step's accumulator, as the host
+receives it, to DIR/accumulator.npy.  Everything else is behind --full: the GPU's clock and power
+state, the CPU baseline, and `roofline` for the
 dominant kernel (the one with the most HIP-event time in the timed region, recorded by the
 library around every launch on the render stream: pt_profile_enable/pt_profile_read).
 Its algorithmic bytes per launch follow SURVEY.md §8d from the GPU's own work counters:
@@ -18,7 +22,8 @@ carries 48*Q + 96*Q_ext (the path model without camera rays and accumulation) / 
 megakernel k_regen carries the whole path model B_alg = 48*Q + 96*Q_ext + 24 B per sample in
 one launch.  `pipeline` gives B_alg over the
 whole render.  `cpu_baseline` is the C oracle (oracle/pt_oracle.c) on the host cores, rank 0
-at N=1 only.
+at N=1 only.  --full adds a counted render before the warm-up, HIP events around every launch of
+the warm-up and around the dominant kernel's launches in the last timed step.
 """
 import argparse
 import json
@@ -347,6 +352,15 @@ def metric_name(scene: str, W: int, H: int, depth: int) -> str:
     return f"Msamples/s (paths/s) {scene} {W}x{H} depth {depth}"
 
 
+def dump_outputs(out_dir: str, acc) -> None:
+    """--dump-outputs: what the timed path hands its caller after the last timed step, the f32
+    accumulator [H, W, 3] on the host (12 MB at 1024^2), as out_dir/accumulator.npy.  The scene, the
+    camera and the RNG salts (t_k = k) are fixed by the arguments, so two builds run with the same
+    arguments can be compared value for value."""
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "accumulator.npy"), np.ascontiguousarray(acc, dtype=np.float32))
+
+
 def native_multi(args):
     """bench.py --native-multi --gpus N: ONE process renders the step over N devices with the C ABI's
     pt_render_multi (frames dealt round-robin, one host thread per device, one ncclReduce onto
@@ -389,6 +403,8 @@ def native_multi(args):
                       "mode": args.mode, "samples_per_step": total,
                       "reduce": (args.reduce or "rccl") if n > 1 else
                       ("rccl (one-rank communicator)" if args.reduce == "rccl" else "none")}}
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, acc)
     print(json.dumps(out), flush=True)
 
 
@@ -411,8 +427,13 @@ def main():
     ap.add_argument("--native-multi", action="store_true",
                     help="one process drives --gpus devices through pt_render_multi (RCCL reduce inside the library)")
     ap.add_argument("--reduce", choices=["rccl", "ordered"], help="--native-multi: pt_render_multi's reduction")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-timing", action="store_true", help="diagnostic: no per-launch HIP events")
+    ap.add_argument("--full", action="store_true",
+                    help="also report the roofline of the dominant kernel (a counted render, per-launch HIP events in "
+                         "the warm-up and in the last timed step), the GPU's clock and power state and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the last step's host accumulator to DIR/accumulator.npy (f32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave the CPU baseline out")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="--full diagnostic: no per-launch HIP events")
     ap.add_argument("--opt", action="append", default=[], metavar="NAME=VALUE",
                     help="library option (pt_set_option) for A/B and profiling runs; repeatable")
     ap.add_argument("--readback", choices=["pt", "torch"], default="pt",
@@ -480,7 +501,7 @@ def main():
         pci = f"{props.pci_domain_id:04x}:{props.pci_bus_id:02x}:{props.pci_device_id:02x}"
     except Exception:  # noqa: BLE001  (older torch: no PCI fields)
         pci = None
-    sysfs = gpu_sysfs_dir(pci)
+    sysfs = gpu_sysfs_dir(pci) if args.full else None  # no directory: nothing is read or sampled
     state_start = gpu_state(sysfs)
     stream = torch.cuda.Stream(device=dev)
     acc = torch.zeros((H, W, 3), dtype=torch.float32, device=dev)
@@ -529,38 +550,44 @@ def main():
         stream.synchronize()
         copy_stream.synchronize()
 
-    # work counters for the roofline's algorithmic bytes (separate pass, not timed)
-    cnt = torch.zeros(6, dtype=torch.int64, device=dev)
-    with torch.cuda.stream(stream):
-        tmp = torch.zeros_like(acc)
-        scene.render_async(meta, frame0, nframes, fstride, args.depth, mode, tmp.data_ptr(), stream.cuda_stream,
-                           d_counters_ptr=cnt.data_ptr())
-    stream.synchronize()
-    c = cnt.cpu().tolist()
-    samples_c, q_ext, q_sh = c[0], c[1], c[2]
-    del tmp
+    # --full: work counters for the roofline's algorithmic bytes (separate pass, not timed)
+    if args.full:
+        cnt = torch.zeros(6, dtype=torch.int64, device=dev)
+        with torch.cuda.stream(stream):
+            tmp = torch.zeros_like(acc)
+            scene.render_async(meta, frame0, nframes, fstride, args.depth, mode, tmp.data_ptr(), stream.cuda_stream,
+                               d_counters_ptr=cnt.data_ptr())
+        stream.synchronize()
+        c = cnt.cpu().tolist()
+        samples_c, q_ext, q_sh = c[0], c[1], c[2]
+        del tmp
 
-    # warm-up with every kernel timed: it names the dominant kernel, the only one whose launches
+    # --full: warm-up with every kernel timed: it names the dominant kernel, the only one whose launches
     # carry events in the timed region (events around every launch cost ~5 % of the step)
-    scene.profile_enable(True)
+    if args.full:
+        scene.profile_enable(True)
     for _ in range(args.warmup):
         step()
     drain()
-    prof_warm = scene.profile_read()
-    scene.profile_enable(False)
+    prof_warm = scene.profile_read() if args.full else {}
+    if args.full:
+        scene.profile_enable(False)
     dominant = max(prof_warm, key=lambda k: prof_warm[k]["total_ms"]) if prof_warm else None
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
     # one event pair per step, read after the loop: the host enqueues step k + 1 while the GPU still
     # runs step k (a synchronisation per step would leave the GPU idle while ~150 launches are issued)
-    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
+    # (--full: the events only feed the roofline's render times; a plain run records none)
+    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) if args.full else (None, None)
+           for _ in range(args.steps)]
     # the dominant kernel's launches carry HIP events in the LAST timed step only: an event pair per
     # launch costs the step ~1 % at configs[1] (144 launches in 95 ms) and ~5 % for one rank's
     # 1/8 share (36 launches in 13 ms; profiles/r05ae_share_events.jsonl), so the other steps run
     # uninstrumented and the kernel's average launch and busy time come from that one step
-    scene.profile_select(dominant)
-    timed = not args.no_kernel_timing and dominant is not None
+    if args.full:
+        scene.profile_select(dominant)
+    timed = args.full and not args.no_kernel_timing and dominant is not None
     with GpuStateSampler(sysfs) as sampler:
         t0 = time.perf_counter()
         for i, (ev0, ev1) in enumerate(evs):
@@ -568,14 +595,15 @@ def main():
                 scene.profile_enable(True)
             step(ev0, ev1)
         drain()
-        render_ms = [ev0.elapsed_time(ev1) for ev0, ev1 in evs]
+        render_ms = [ev0.elapsed_time(ev1) for ev0, ev1 in evs] if args.full else []
         if world > 1:
             dist.barrier()
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
     state_end = gpu_state(sysfs)
-    prof = scene.profile_read()
-    scene.profile_enable(False)
+    prof = scene.profile_read() if timed else {}
+    if timed:
+        scene.profile_enable(False)
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev if backend != "gloo" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -585,40 +613,41 @@ def main():
     total_samples = W * H * (nframes if args.share_of > 1 else args.spp)
     ms_per_step = elapsed / args.steps * 1e3
     value = total_samples / (elapsed / args.steps) / 1e6
-    r_ms = float(np.mean(render_ms))
-    b_alg = (48.0 * (q_ext + q_sh) + 96.0 * q_ext + 24.0 * samples_c)  # bytes per render
-    if prof:
-        kernel = max(prof, key=lambda k: prof[k]["total_ms"])
-        launches_per_render = prof[kernel]["launches"]  # of the last timed step
-        k_ms = prof[kernel]["avg_ms"]
-        busy_ms = prof[kernel]["busy_ms"]  # union of the launches' intervals in that step
-        if kernel in ("k_wf_trace", "k_wf_leafpass"):
-            # the traversal's model: a ray record read and a hit record written per query (the big-leaf
-            # pass reads the same records and writes a key per query that meets a big leaf's boxes)
-            bytes_per_launch = 48.0 * (q_ext + q_sh) / launches_per_render
-        elif kernel == "k_wf_step":  # fused trace + shade: the path model minus camera rays and accumulation
-            bytes_per_launch = (48.0 * (q_ext + q_sh) + 96.0 * q_ext) / launches_per_render
-        else:  # the megakernel: the whole path model in one launch
-            bytes_per_launch = b_alg / launches_per_render
-        # achieved = the algorithmic bytes of all of a step's launches over the time the kernel
-        # is busy in that step (launches of the batch's parts overlap on their streams, so the
-        # per-launch event time over-counts: it is reported, not used)
-        achieved = bytes_per_launch * launches_per_render / (busy_ms * 1e-3) / 1e9
-    else:  # --no-kernel-timing (diagnostic)
-        kernel, launches_per_render, k_ms, busy_ms, bytes_per_launch, achieved = "n/a", 0, 0.0, 0.0, 0.0, 0.0
-    pipeline = b_alg / (r_ms * 1e-3) / 1e9
-    # SURVEY.md §8d's secondary figure, the algorithmic VALU work, from the same counters (the
-    # reference's own units: every triangle test and node step its traversal makes, and the path
-    # logic per bounce): 40 flop per triangle test + 2 x 24 per node step + 150 per extension query
-    flop_per_render = 40.0 * c[4] + 48.0 * c[3] + 150.0 * q_ext
-    valu_tflops = flop_per_render / max(samples_c, 1) * value * 1e6 / 1e12  # at the step's samples/s
-    # and the scene bytes the reference's traversal reads (SURVEY.md §8d secondary: 56 B per node
-    # step, 52 B per triangle test, 60 B per material fetch — one per extension query), the figure
-    # that bounds the traversal scenes from L2 rather than HBM
-    scene_per_render = 56.0 * c[3] + 52.0 * c[4] + 60.0 * q_ext
-    scene_gbs = scene_per_render / max(samples_c, 1) * value * 1e6 / 1e9
+    if args.full:  # the roofline's figures, from the counted render and the last step's events
+        r_ms = float(np.mean(render_ms))
+        b_alg = (48.0 * (q_ext + q_sh) + 96.0 * q_ext + 24.0 * samples_c)  # bytes per render
+        if prof:
+            kernel = max(prof, key=lambda k: prof[k]["total_ms"])
+            launches_per_render = prof[kernel]["launches"]  # of the last timed step
+            k_ms = prof[kernel]["avg_ms"]
+            busy_ms = prof[kernel]["busy_ms"]  # union of the launches' intervals in that step
+            if kernel in ("k_wf_trace", "k_wf_leafpass"):
+                # the traversal's model: a ray record read and a hit record written per query (the big-leaf
+                # pass reads the same records and writes a key per query that meets a big leaf's boxes)
+                bytes_per_launch = 48.0 * (q_ext + q_sh) / launches_per_render
+            elif kernel == "k_wf_step":  # fused trace + shade: the path model minus camera rays and accumulation
+                bytes_per_launch = (48.0 * (q_ext + q_sh) + 96.0 * q_ext) / launches_per_render
+            else:  # the megakernel: the whole path model in one launch
+                bytes_per_launch = b_alg / launches_per_render
+            # achieved = the algorithmic bytes of all of a step's launches over the time the kernel
+            # is busy in that step (launches of the batch's parts overlap on their streams, so the
+            # per-launch event time over-counts: it is reported, not used)
+            achieved = bytes_per_launch * launches_per_render / (busy_ms * 1e-3) / 1e9
+        else:  # --no-kernel-timing (diagnostic)
+            kernel, launches_per_render, k_ms, busy_ms, bytes_per_launch, achieved = "n/a", 0, 0.0, 0.0, 0.0, 0.0
+        pipeline = b_alg / (r_ms * 1e-3) / 1e9
+        # SURVEY.md §8d's secondary figure, the algorithmic VALU work, from the same counters (the
+        # reference's own units: every triangle test and node step its traversal makes, and the path
+        # logic per bounce): 40 flop per triangle test + 2 x 24 per node step + 150 per extension query
+        flop_per_render = 40.0 * c[4] + 48.0 * c[3] + 150.0 * q_ext
+        valu_tflops = flop_per_render / max(samples_c, 1) * value * 1e6 / 1e12  # at the step's samples/s
+        # and the scene bytes the reference's traversal reads (SURVEY.md §8d secondary: 56 B per node
+        # step, 52 B per triangle test, 60 B per material fetch — one per extension query), the figure
+        # that bounds the traversal scenes from L2 rather than HBM
+        scene_per_render = 56.0 * c[3] + 52.0 * c[4] + 60.0 * q_ext
+        scene_gbs = scene_per_render / max(samples_c, 1) * value * 1e6 / 1e9
 
-    if rank == 0:
+    if rank == 0 and args.full:
         prefixes = {"k_wf_trace": ("k_wf_trace<", "k_wf_trace_bf<"), "k_wf_step": ("k_wf_step_bf<",),
                     "k_wf_leafpass": ("k_wf_leafpass<",)}
         pre = prefixes.get(kernel, (kernel + "<",))
@@ -631,6 +660,7 @@ def main():
         tu = load_trace_union(W, H, args.spp, args.depth, world) if full else None
         if tu and tu.get("kernel") != kernel:
             tu = None
+    if rank == 0:
         out = {
             "metric": metric_name(args.scene, W, H, args.depth),
             "value": round(value, 3),
@@ -663,6 +693,9 @@ def main():
                        "share": ({"of": args.share_of, "rank": args.share_rank, "frames": nframes, "stride": fstride,
                                   "implied_aggregate_before_reduce": round(value * args.share_of, 3)}
                                  if args.share_of > 1 else None)},
+        }
+    if rank == 0 and args.full:
+        out.update({
             # the GPU's clocks, power and temperatures (sysfs, read-only) before the warm-up, sampled
             # every 50 ms through the timed region (min / median / max), and after it
             "gpu_state": {"pci": pci, "sysfs": sysfs, "start": state_start, "timed": sampler.summary(),
@@ -721,9 +754,12 @@ def main():
                                                       {k: v["total_ms"] / max(args.warmup, 1) for k, v in prof_warm.items()})
                                        if full else None),
                          "render_ms_steps": [round(x, 2) for x in render_ms]},
-        }
+        })
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(tri, bvh, meta, args.depth)
+    if rank == 0:
+        if args.dump_outputs:  # the last timed step's accumulator as the host received it
+            dump_outputs(args.dump_outputs, hosts[(nstep[0] - 1) % 2].numpy())
         print(json.dumps(out), flush=True)
     scene.close()
     if world > 1:
@@ -751,6 +787,8 @@ def dry_run(args, rank, world, ranks_seen, backend, dist, frames_for_rank, reduc
         elapsed = float(t.item())
     if rank == 0:
         frames_total = float(acc[0, 0, 0])  # the reduce summed every rank's frame count
+        if args.dump_outputs:  # the rehearsal's accumulator: every value is the frame count
+            dump_outputs(args.dump_outputs, acc.numpy())
         print(json.dumps({"metric": metric_name(args.scene, W, H, args.depth), "value": None, "unit": "Msamples/s",
                           "n_gpus": ranks_seen, "steps": args.steps, "warmup": args.warmup,
                           "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True,

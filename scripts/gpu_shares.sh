@@ -6,7 +6,7 @@ set -o pipefail
 OUT=${OUT:-gpurun_out/shares.jsonl}
 mkdir -p "$(dirname "$OUT")"
 : > "$OUT"
-run() { timeout -k 10 300 python -u bench.py --no-cpu-baseline "$@" | tee -a "$OUT"; }
+run() { timeout -k 10 300 python -u bench.py --full --no-cpu-baseline "$@" | tee -a "$OUT"; }
 run --steps 5 --warmup 1 &&
 for n in 2 4 8; do run --steps 5 --warmup 1 --share-of $n || exit 1; done &&
 run --steps 3 --warmup 1 --width 4096 --height 4096 --spp 4096 --share-of 8 &&

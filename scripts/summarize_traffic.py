@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Summarize the rocprofv3 PMC passes of scripts/collect_traffic.sh (gpurun_out/traffic/{fetch,
-write,valu}) into traffic.json: per kernel instance and launch, HBM bytes (FETCH_SIZE x 2 for
+"""Summarize the rocprofv3 PMC passes of scripts/collect_traffic.sh ($PT_OUT/traffic/{fetch,
+write,valu}, PT_OUT as that script exports it) into traffic.json: per kernel instance and launch, HBM bytes (FETCH_SIZE x 2 for
 gfx950 + WRITE_SIZE, KB -> bytes) and the VALU issue fraction
     valu_issue = k * SQ_ACTIVE_INST_VALU / (128 * GRBM_GUI_ACTIVE)
 (GRBM_GUI_ACTIVE summed over the 8 XCDs, each of 32 CUs x 4 SIMDs: SIMD-cycles = GRBM / 8 x 1024),
@@ -17,7 +17,7 @@ import os
 import re
 import sys
 
-SRC = "gpurun_out/traffic"
+SRC = os.path.join(os.environ.get("PT_OUT", "out"), "traffic")
 
 
 def load(tag, counters):

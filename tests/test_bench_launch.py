@@ -34,6 +34,20 @@ def test_gpus_n_spawns_n_ranks(n):
     assert out["config"]["frames_reduced"] == 16.0  # every rank's frame share went through the reduce
 
 
+def test_dump_outputs_writes_the_accumulator(tmp_path):
+    """--dump-outputs DIR: rank 0 writes the step's accumulator as DIR/accumulator.npy, f32 [H, W, 3]
+    (the rehearsal's accumulator holds the reduced frame count in every value)."""
+    import numpy as np
+    d = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-run", "--steps", "2",
+                        "--spp", "5", "--width", "8", "--height", "4", "--dump-outputs", str(d)], env=_env(),
+                       capture_output=True, text=True, timeout=240, cwd="/tmp")
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert os.listdir(d) == ["accumulator.npy"]
+    a = np.load(d / "accumulator.npy")
+    assert a.dtype == np.float32 and a.shape == (4, 8, 3) and (a == 5.0).all()
+
+
 def test_gpus_must_match_launcher_world_size():
     env = _env()
     env.update(WORLD_SIZE="1", RANK="0", LOCAL_RANK="0")
