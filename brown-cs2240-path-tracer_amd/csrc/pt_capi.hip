@@ -457,8 +457,7 @@ int build_layout(const float* tri, size_t tri_len, const float* bvh, size_t bvh_
     // Leaf remainders (pt_leafskip.cpp; option leaf_skip, read here and per render, default on):
     // scenes without mailbox (their kernels test every distinct entry once per ray anyway)
     if (!L.mailbox && opts_snapshot().flag("leaf_skip", 1) != 0)
-        build_leaf_skips(L.nodes, L.tris, L.tnorm, L.lights, kLeafSkipMaxLeaf, kLeafAlt, kLeafSkipProbeTests, L.nalt,
-                         &L.skip);
+        build_leaf_skips(L.nodes, L.tris, L.tnorm, L.lights, kLeafSkipMaxLeaf, kLeafSkipProbeTests, L.nalt, &L.skip);
     // |det| = |e1 . (d x e2)| <= |e1| |e2| |d| with |d| = 1 (every ray direction is normalised or
     // a reflection/refraction of unit vectors; non-finite ones give no hit on either path)
     double emax = 0.0;
@@ -574,7 +573,7 @@ struct pt_scene {
     // big leaves resolved before the traversal (k_wf_leafpass): the table (device copy in d_mem at
     // d_pre), every leaf's size (largest first), and the result keys (ensure_pres)
     std::vector<PreLeaf> pre;
-    // render_impl's choice of the leaf pass: per leaf of pre, probe queries passing its box filter and
+    // shape_view's choice of the leaf pass: per leaf of pre, probe queries passing its box filter and
     // visiting it (probe_pre_leaves, once, with the camera of the scene's first render that could
     // use the pass), from host copies of the tree, records and lights kept for it
     std::vector<std::array<uint32_t, 2>> pre_probe;
@@ -889,49 +888,42 @@ int make_params(const float* meta, int max_depth, FrameParams& fp) {
 // leaves (MedievalBoat 256^2 x 1: 62 / 35); other scenes from about 2^19 paths (Glossy 512^2 x 1:
 // 7.1 / 9.1, 512^2 x 2: 13.1 / 9.6).
 constexpr uint64_t kWfAutoMinPaths = 1ull << 19;
-// k_wf_trace narrows its windows when 32-entry ones would keep < 1/4 of the waves busy (option
-// trace_sparse=n; in-process A/B: MedievalBoat +16 %, Glossy and the synthetic scenes +-0.5 %)
-constexpr int kTraceSparseDefault = 4;
-// camera batches dealt to the fused kernel's regions by a permutation (option region_perm): a
-// block's 8 waves serve 8 neighbouring regions, which in row order hold neighbouring batches — at
-// 4096^2, 512 neighbouring pixels of one row (an eighth of it) on one CU; permuted, batches far
-// apart: 4096^2 2475 -> 2679 Msamples/s, 1024^2 and Mirror unchanged (profiles/r03h_ab_region_perm.txt)
-constexpr int kRegionPermDefault = 1;
+// The call's pipeline: option kernel, else the mode, AUTO by the call's paths and the scene (view's
+// mailbox and big_leaf > 0)
+bool wants_wavefront(const Opts& o, int mode, uint64_t paths, const SceneView& view) {
+    if (o.is("kernel", "wavefront")) return true;
+    if (o.is("kernel", "mega") || o.is("kernel", "literal")) return false;
+    const uint64_t auto_min = (view.mailbox || view.big_leaf > 0) ? 1 : kWfAutoMinPaths;
+    return mode == PT_MODE_WAVEFRONT || (mode == PT_MODE_AUTO && paths >= auto_min);
+}
 
+// The call's LaunchOpts: pt_flavour.h's defaults, the pipeline, and whatever pt_set_option overrides
 LaunchOpts launch_opts(const Opts& o, int mode, uint64_t paths, const SceneView& view) {
     LaunchOpts lo;
-    const uint64_t auto_min = (view.mailbox || view.big_leaf > 0) ? 1 : kWfAutoMinPaths;
-    lo.wavefront = mode == PT_MODE_WAVEFRONT || (mode == PT_MODE_AUTO && paths >= auto_min);
-    if (o.has("kernel")) {
-        lo.literal = o.is("kernel", "literal");
-        if (o.is("kernel", "wavefront")) lo.wavefront = true;
-        if (o.is("kernel", "mega") || lo.literal) lo.wavefront = false;
-    }
-    lo.lds = o.flag("lds", 1) != 0;
-    lo.fast_rcp = o.flag("fastrcp", lo.fast_rcp);
-    lo.parts = (int)o.num("parts", lo.parts);
-    lo.fuse_gen = o.flag("fuse_gen", lo.fuse_gen);
-    lo.dual = o.flag("dual", lo.dual);
-    lo.fuse = o.flag("fuse", lo.fuse);
-    lo.bf = o.flag("bf", lo.bf);
-    lo.mailbox = o.flag("mailbox", lo.mailbox);
+    lo.wavefront = wants_wavefront(o, mode, paths, view);
+    lo.literal = o.is("kernel", "literal");
+    auto flag = [&](const char* name, bool def) { return o.flag(name, def ? 1 : 0) != 0; };
+    lo.lds = flag("lds", lo.lds);
+    lo.fuse_gen = flag("fuse_gen", lo.fuse_gen);
+    lo.dual = flag("dual", lo.dual);
+    lo.region_perm = flag("region_perm", lo.region_perm);
+    if (const long p = o.num("parts", 0); p > 0) lo.parts = (int)p;  // 0: the default
     lo.sort = (int)o.num("sort", lo.sort);  // 1 / 8: direction octant; 64: + origin octant; 512: + 4^3 origin cells
-    lo.trace_sparse = (int)o.num("trace_sparse", kTraceSparseDefault);
-    lo.region_perm = o.flag("region_perm", kRegionPermDefault);
-    lo.regen = (int)std::max(0L, std::min(1L << 20, o.num("regen", 0)));
-    lo.trace_ring = (int)o.num("trace_ring", 0);
-    lo.trace_blocks = (int)o.num("wf_trace_blocks", 0);
-    lo.watchdog = (uint32_t)o.num("trace_watchdog", 0);
-    lo.bf_slots = (int)o.num("bf_slots", -1);
-    lo.leaf_blocks = (int)o.num("leaf_blocks", 0);
+    lo.trace_sparse = (int)o.num("trace_sparse", lo.trace_sparse);
+    lo.regen = (int)std::max(0L, std::min(1L << 20, o.num("regen", lo.regen)));
+    lo.trace_ring = (int)o.num("trace_ring", lo.trace_ring);
+    lo.trace_blocks = (int)o.num("wf_trace_blocks", lo.trace_blocks);
+    lo.watchdog = (uint32_t)o.num("trace_watchdog", lo.watchdog);
+    lo.bf_slots = (int)o.num("bf_slots", lo.bf_slots);
+    lo.leaf_blocks = (int)o.num("leaf_blocks", lo.leaf_blocks);
     // | 4: the pair walk's second check of the open chunks with the entries' own normals (option
     // leaf_refine, default on; pt_leafpass.hip)
-    lo.leaf_pairs = (int)std::max(0L, std::min(2L, o.num("leaf_pairs", 1))) | (o.flag("leaf_refine", 1) != 0 ? 4 : 0);
-    if (o.has("trav")) {
-        static const char* const names[] = {"nested", "flat1", "pred", "lean", "lean2", "lean4", "lean8", "lean16", "lean32"};
-        for (int k = 0; k < 9; ++k)
-            if (o.is("trav", names[k])) lo.trav = k;
-    }
+    lo.leaf_pairs = (int)std::max(0L, std::min(2L, o.num("leaf_pairs", 1))) | (flag("leaf_refine", true) ? 4 : 0);
+    int trav = -1;
+    static const char* const names[TRAV_BASE_COUNT] = {"nested", "flat1", "pred", "lean", "lean2", "lean4", "lean8", "lean16", "lean32"};
+    for (int k = 0; k < TRAV_BASE_COUNT; ++k)
+        if (o.is("trav", names[k])) trav = k;
+    lo.set_flavour_opts(trav, o.flag("fastrcp", -1), o.flag("mailbox", -1), o.flag("bf", -1), o.flag("fuse", -1));
     return lo;
 }
 
@@ -942,7 +934,7 @@ LaunchOpts launch_opts(const Opts& o, int mode, uint64_t paths, const SceneView&
 // (probe of option wf_paths)
 constexpr uint64_t kWfTargetPaths = 64ull << 20;
 constexpr int kBigLeafDefault = 128;
-constexpr long kPreRatioDefault = 50;  // render_impl: the leaf pass when >= 50 % of its work is visited
+constexpr long kPreRatioDefault = 50;  // shape_view: the leaf pass when >= 50 % of its work is visited
 
 int ensure_rad(pt_scene* s, uint64_t paths) {
     if (s->d_rad && s->rad_cap >= paths) { s->wf.rad = s->d_rad; s->wf.rad_cap = s->rad_cap; return PT_OK; }
@@ -1058,24 +1050,12 @@ int take_watchdog(pt_scene* s) {
     return fail(PT_ERR_HIP, msg);
 }
 
-int render_impl(pt_scene* s, const float* meta, uint32_t frame0, uint32_t nframes, uint32_t stride, int max_depth,
-                int mode, bool accum, float* d_out, Counters* d_cnt, hipStream_t stream) {
-    FrameParams fp{};
-    int rc = make_params(meta, max_depth, fp);
-    if (rc != PT_OK) return rc;
-    if (mode != PT_MODE_AUTO && mode != PT_MODE_MEGAKERNEL && mode != PT_MODE_WAVEFRONT)
-        return fail(PT_ERR_INVALID, "unknown mode");
-    if (accum && (uint64_t)frame0 + (uint64_t)(nframes ? nframes - 1 : 0) * stride >= (1ull << 24))
-        return fail(PT_ERR_INVALID, "frame index >= 2^24 (t_k = u32(f32(k)) would round)");
-    HIP_TRY(hipSetDevice(s->device));
-    if (nframes == 0) return PT_OK;
-    const uint64_t npix = (uint64_t)fp.width * fp.height;
-    struct ProfScope {  // attach the scene's profiler to this thread for the launches below
-        explicit ProfScope(KernelProfiler* p) { t_prof = p; }
-        ~ProfScope() { t_prof = nullptr; }
-    } prof_scope(s->prof_on ? &s->prof : nullptr);
-    SceneView view = s->view;
-    const Opts o = opts_snapshot();
+// The scene as this call's kernels see it: the scene's view with the per-call choices applied — the
+// big-leaf threshold, leaf chunks, the pooled runs' length, leaf remainders, and whether the big
+// leaves are resolved before the traversal (for the camera of fp).  paths: the call's, for AUTO's
+// choice of pipeline.
+int shape_view(pt_scene* s, const Opts& o, const FrameParams& fp, int mode, uint64_t paths, SceneView& view) {
+    view = s->view;
     if (o.has("node_bias")) view.node_bias = std::max(1L, o.num("node_bias", 1));  // A/B runs
     if (o.has("node_steps")) view.node_steps = (int32_t)std::max(1L, std::min(8L, o.num("node_steps", 1)));
     // big leaves (lean traversal): a ray reaching a leaf of >= big_leaf entries has it tested by the
@@ -1115,7 +1095,6 @@ int render_impl(pt_scene* s, const float* meta, uint32_t frame0, uint32_t nframe
     if (o.flag("leaf_skip", 1) == 0 || (view.big_leaf > 0 && view.big_leaf < kLeafSkipMaxLeaf)) view.nalt = nullptr;
     // the brute-force replay walks the BfNode tree without a stack (bf_stackless=0: the stack walk; A/B)
     if (o.flag("bf_stackless", 1) == 0) view.bfnode = nullptr;
-    const LaunchOpts lo = launch_opts(o, mode, npix * (accum ? nframes : 1), view);
     // big leaves resolved before the traversal (k_wf_leafpass, pt_leafpass.hip; option leaf_pre=0:
     // the cooperative turns and chunk walks inside k_wf_trace): the leaves of >= big_leaf entries, at
     // most kMaxPre of them — with more, the threshold rises above the (kMaxPre + 1)-th largest and
@@ -1133,7 +1112,7 @@ int render_impl(pt_scene* s, const float* meta, uint32_t frame0, uint32_t nframe
     view.npre = 0;
     view.pre = nullptr;
     const long pre_opt = o.num("leaf_pre", 2);
-    if (lo.wavefront && view.big_leaf > 0 && pre_opt != 0 && !s->pre.empty()) {
+    if (wants_wavefront(o, mode, paths, view) && view.big_leaf > 0 && pre_opt != 0 && !s->pre.empty()) {
         int32_t T = view.big_leaf;
         if (s->leaf_sizes.size() > (size_t)kMaxPre && s->leaf_sizes[kMaxPre] >= T) T = s->leaf_sizes[kMaxPre] + 1;
         int np = 0;
@@ -1144,7 +1123,7 @@ int render_impl(pt_scene* s, const float* meta, uint32_t frame0, uint32_t nframe
         // (advisor r05; leaf_pre=1 still forces the pass)
         if (pre_opt != 1 && T > view.big_leaf) np = 0;
         if (np > 0 && pre_opt != 1) {
-            std::lock_guard<std::mutex> lk(s->pre_mu);
+            std::lock_guard<std::mutex> lk(s->pre_mu);  // held for the probe and for the reading of its result
             ProbeCamera pc{};
             for (int c = 0; c < 3; ++c) pc.cam[c] = fp.cam[c];
             for (int c = 0; c < 16; ++c) pc.M[c] = fp.M[c];
@@ -1159,14 +1138,14 @@ int render_impl(pt_scene* s, const float* meta, uint32_t frame0, uint32_t nframe
                 s->pre_cam = pc;
                 s->pre_probed = true;
             }
-        }
-        if (np > 0 && pre_opt != 1 && s->pre_probe.size() >= (size_t)np) {
-            double filt = 0.0, vis = 0.0;
-            for (int b = 0; b < np; ++b) {
-                filt += (double)s->pre_probe[(size_t)b][0] * s->pre[(size_t)b].n;
-                vis += (double)s->pre_probe[(size_t)b][1] * s->pre[(size_t)b].n;
+            if (s->pre_probe.size() >= (size_t)np) {
+                double filt = 0.0, vis = 0.0;
+                for (int b = 0; b < np; ++b) {
+                    filt += (double)s->pre_probe[(size_t)b][0] * s->pre[(size_t)b].n;
+                    vis += (double)s->pre_probe[(size_t)b][1] * s->pre[(size_t)b].n;
+                }
+                if (filt > 0.0 && vis * 100.0 < filt * (double)o.num("pre_ratio", kPreRatioDefault)) np = 0;
             }
-            if (filt > 0.0 && vis * 100.0 < filt * (double)o.num("pre_ratio", kPreRatioDefault)) np = 0;
         }
         if (np > 0) {
             // pt_device.h pre_slot finds a leaf's key slot by its first record among the first np table
@@ -1182,6 +1161,35 @@ int render_impl(pt_scene* s, const float* meta, uint32_t frame0, uint32_t nframe
             for (int b = 0; b < kMaxPre; ++b) view.pre_rec0[b] = b < np ? s->pre[(size_t)b].rec0 : -1;
         }
     }
+    // a remainder stands for its leaf by another first record and count: the leaves the cooperative
+    // turns or the leaf pass take (>= big_leaf entries) must have none (every remainder's leaf has
+    // fewer than kLeafSkipMaxLeaf entries)
+    if (view.nalt != nullptr && view.big_leaf > 0 && view.big_leaf < kLeafSkipMaxLeaf)
+        return fail(PT_ERR_SCENE, "internal: leaf remainders with a big-leaf threshold below their largest leaf");
+    return PT_OK;
+}
+
+int render_impl(pt_scene* s, const float* meta, uint32_t frame0, uint32_t nframes, uint32_t stride, int max_depth,
+                int mode, bool accum, float* d_out, Counters* d_cnt, hipStream_t stream) {
+    FrameParams fp{};
+    int rc = make_params(meta, max_depth, fp);
+    if (rc != PT_OK) return rc;
+    if (mode != PT_MODE_AUTO && mode != PT_MODE_MEGAKERNEL && mode != PT_MODE_WAVEFRONT)
+        return fail(PT_ERR_INVALID, "unknown mode");
+    if (accum && (uint64_t)frame0 + (uint64_t)(nframes ? nframes - 1 : 0) * stride >= (1ull << 24))
+        return fail(PT_ERR_INVALID, "frame index >= 2^24 (t_k = u32(f32(k)) would round)");
+    HIP_TRY(hipSetDevice(s->device));
+    if (nframes == 0) return PT_OK;
+    const uint64_t npix = (uint64_t)fp.width * fp.height;
+    struct ProfScope {  // attach the scene's profiler to this thread for the launches below
+        explicit ProfScope(KernelProfiler* p) { t_prof = p; }
+        ~ProfScope() { t_prof = nullptr; }
+    } prof_scope(s->prof_on ? &s->prof : nullptr);
+    const Opts o = opts_snapshot();
+    const uint64_t paths = npix * (accum ? nframes : 1);
+    SceneView view;
+    if ((rc = shape_view(s, o, fp, mode, paths, view)) != PT_OK) return rc;
+    const LaunchOpts lo = launch_opts(o, mode, paths, view);
     if ((rc = take_watchdog(s)) != PT_OK) return rc;  // an earlier asynchronous render failed
     if (lo.wavefront) {
         // the target in whole pairs of frames (a batch's two parts take whole frames each): 4096^2

@@ -3,6 +3,7 @@
 // per-lane LDS stack, light sampling, hemisphere sampling, camera rays.
 // Every function cites the WGSL it restates; numerics follow pt_math.h.
 #pragma once
+#include "pt_flavour.h"
 #include "pt_layout.h"
 #include "pt_math.h"
 
@@ -344,16 +345,6 @@ __device__ __forceinline__ int pre_slot(const SceneView& sc, int rec0) {
 // PRE: a node step whose hit leaf children include a pre-resolved big leaf loads that leaf's key
 // now (the first such leaf of the pair), so it arrives behind the next steps' own loads instead of
 // stalling the wave in its leaf turn (pre_apply)
-// Leaf remainders (SceneView::nalt, pt_leafskip.cpp): the descriptor of the remainder of a leaf
-// whose ray tested leaf `prev` last (first record << 7 | count), -1 when the leaf has none for it
-__device__ __forceinline__ int alt_pick(const int4 p, const int4 q, int prev) {
-    int v = -1;
-    v = prev == p.x ? p.y : v;
-    v = prev == p.z ? p.w : v;
-    v = prev == q.x ? q.y : v;
-    v = prev == q.z ? q.w : v;
-    return v;
-}
 
 template <bool COUNT, bool PRE = false>
 __device__ __forceinline__ bool lean_node_unit(const SceneView& sc, const Ray& r, TravLean& s, Counters& cnt) {
@@ -362,15 +353,8 @@ __device__ __forceinline__ bool lean_node_unit(const SceneView& sc, const Ray& r
     int4 d = reinterpret_cast<const int4*>(np)[3];
     // leaf remainders: loaded beside the node (the counting build walks the reference's leaves)
     const bool alt = !COUNT && sc.nalt != nullptr;
-    int4 al0{}, al1{}, ar0{}, ar1{};  // kLeafAlt 1: al0 = (prevL, remL, prevR, remR); 4: two int4 per side
-    if (alt) {
-        if constexpr (kLeafAlt == 1) {
-            al0 = sc.nalt[s.node];
-        } else {
-            const int4* ap = sc.nalt + 4 * s.node;
-            al0 = ap[0]; al1 = ap[1]; ar0 = ap[2]; ar1 = ap[3];
-        }
-    }
+    int4 al{};  // (prevL, remL, prevR, remR); a remainder is first record << 7 | count
+    if (alt) al = sc.nalt[s.node];
     if (COUNT) { cnt.nodes++; cnt.box_tests += 2; }
     s.ld = ray_box(r, a.x, a.y, a.z, a.w, b.x, b.y);
     s.rd = ray_box(r, b.z, b.w, c.x, c.y, c.z, c.w);
@@ -383,14 +367,8 @@ __device__ __forceinline__ bool lean_node_unit(const SceneView& sc, const Ray& r
         // left one is tested too.  The leaves keep their identity (first records) for `last`.
         const bool lt = li & lleaf & (d.z > 0), rt = ri & rleaf & (d.w > 0);
         const int pr = lt ? d.x : s.last;
-        int dl, dr;
-        if constexpr (kLeafAlt == 1) {
-            dl = s.last == al0.x ? al0.y : -1;
-            dr = pr == al0.z ? al0.w : -1;
-        } else {
-            dl = alt_pick(al0, al1, s.last);
-            dr = alt_pick(ar0, ar1, pr);
-        }
+        const int dl = s.last == al.x ? al.y : -1;
+        const int dr = pr == al.z ? al.w : -1;
         if (lt & (dl >= 0)) { lrec = dl >> 7; ln = dl & 127; }
         if (rt & (dr >= 0)) { rrec = dr >> 7; rn = dr & 127; }
         s.last = rt ? d.y : pr;
@@ -1002,7 +980,7 @@ __device__ __forceinline__ bool lean_leaf_pool(const SceneView& sc, const Ray& r
 // Each iteration runs ONE unit type for the whole wave — a leaf turn (up to K triangle tests)
 // when leaf lanes >= node_bias * node lanes, else a node turn — keeping each lane's unit order.
 // PRUN: the pooled leaf turns' run length (lean_leaf_pool)
-// PRE: the big leaves were resolved before the traversal (pre_apply; TRAV 26x / 27x)
+// PRE: the big leaves were resolved before the traversal (pre_apply; the FLV_PRE flavours)
 template <int K, bool COUNT, bool FAST_RCP, bool BIG = false, bool CHUNKS = false, int PRUN = 4, bool PRE = false,
           class ST>
 __device__ __forceinline__ bool trav_step_lean(const SceneView& sc, const Ray& r, TravLean& s, const ST& stack,
@@ -1139,12 +1117,8 @@ __device__ __forceinline__ bool trav_step_mb(const SceneView& sc, const Ray& r, 
     return true;
 }
 
-// Traversal flavours (LaunchOpts.trav): 0 nested loops (trace), 1 flattened with per-lane
-// branches (trav_step), 2 flattened and predicated (trav_step_pred), 3 lean (trav_step_lean),
-// 4 lean with two triangle tests per leaf turn, 5 with four, 6 with eight, 7 with sixteen; +10: the lean
-// flavours with 1/det from rcp_rn (scenes with SceneView::fast_rcp); +100: mailboxed lean flavours;
-// +160: big leaves (cooperative turns / chunk walks); +260: big leaves resolved before the traversal.
-template <int TRAV, bool LEAN = (TRAV >= 3)>
+// Traversal flavours (TRAV: pt_flavour.h)
+template <int TRAV, bool LEAN = flv_lean_state(TRAV)>
 struct TravSel { using type = TravState; };
 template <int TRAV>
 struct TravSel<TRAV, true> { using type = TravLean; };
@@ -1154,24 +1128,19 @@ struct TravSel<TRAV, true> { using type = TravLean; };
 template <int TRAV, bool COUNT, bool CHUNKS = false, int PRUN = 4, class ST>
 __device__ __forceinline__ bool trav_advance(const SceneView& sc, const Ray& r, typename TravSel<TRAV>::type& s,
                                              const ST& stack, Counters& cnt) {
-    if constexpr (TRAV >= 100 && TRAV < 160) {  // mailboxed lean<K> (SceneView::mailbox scenes); + 10: fast reciprocal
-        constexpr int K = 1 << (TRAV % 10 - 3);
-        return trav_step_mb<K, COUNT, ((TRAV / 10) & 1) != 0>(sc, r, s, stack, cnt);
-    }
-    else if constexpr (TRAV >= 3) {  // TRAV + 10: fast reciprocal; + 160: big-leaf cooperation; + 260: pre-resolved
-        constexpr int B = TRAV % 10;
-        constexpr int K = 1 << (B - 3);  // lean, lean2, lean4, lean8, lean16, lean32
-        return trav_step_lean<K, COUNT, ((TRAV / 10) & 1) != 0, TRAV >= 160, CHUNKS, PRUN, (TRAV >= 260)>(sc, r, s, stack,
-                                                                                                           cnt);
-    }
-    else if constexpr (TRAV == 1) return trav_step<COUNT>(sc, r, s, stack, cnt);
+    if constexpr (flv_mailbox(TRAV))  // mailboxed lean<K> (SceneView::mailbox scenes)
+        return trav_step_mb<flv_lean_k(TRAV), COUNT, flv_fast(TRAV)>(sc, r, s, stack, cnt);
+    else if constexpr (flv_lean(TRAV))  // lean, lean2, lean4, lean8, lean16, lean32
+        return trav_step_lean<flv_lean_k(TRAV), COUNT, flv_fast(TRAV), flv_big(TRAV), CHUNKS, PRUN, flv_pre(TRAV)>(sc, r, s, stack,
+                                                                                                                  cnt);
+    else if constexpr (flv_base(TRAV) == TRAV_FLAT) return trav_step<COUNT>(sc, r, s, stack, cnt);
     else return trav_step_pred<COUNT>(sc, r, s, stack, cnt);
 }
 
 template <int TRAV, bool COUNT, class ST>
 __device__ __forceinline__ int trace_any(const SceneView& sc, const Ray& r, float& t_out, const ST& stack,
                                          Counters& cnt) {
-    if (TRAV == 0) return trace<COUNT>(sc, r, t_out, stack, cnt);
+    if (flv_base(TRAV) == TRAV_NESTED) return trace<COUNT>(sc, r, t_out, stack, cnt);
     typename TravSel<TRAV>::type s;
     trav_init(s, true);
     while (trav_advance<TRAV, COUNT>(sc, r, s, stack, cnt)) {

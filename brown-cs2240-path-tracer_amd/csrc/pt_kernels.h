@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "pt_device.h"
+#include "pt_flavour.h"
 
 // ids for k_selftest_math (also used by pt_selftest_math in the C-ABI)
 enum {
@@ -52,31 +53,7 @@ constexpr int kMegaBlock = 256;
 // dynamic LDS a workgroup may use for traversal stacks + a staged scene copy
 constexpr size_t kLdsSceneBudget = 64 * 1024;
 
-// Kernel selection (pt_set_option overrides for tests and A/B runs; pt_capi.hip launch_opts).
-struct LaunchOpts {
-    bool wavefront = false;  // wavefront pipeline (pt_wavefront.hip)
-    bool literal = false;  // k_mega: the reference's control flow
-    bool lds = true;       // stage the scene in LDS when it fits
-    int fast_rcp = -1;     // rcp_rn for 1/det where SceneView::fast_rcp says it is exact: -1 per-pipeline default
-    int dual = -1;         // wavefront batch split in parts on their own streams: -1 default (on)
-    int fuse_gen = 1;      // fused kernel: the first launch makes the camera paths (0: k_wf_generate)
-    int parts = -1;        // parts of a wavefront batch on their own streams (1..kMaxParts): -1 default (2)
-    int mailbox = -1;      // mailboxed lean traversal where SceneView::mailbox allows it: -1 default (on)
-    int bf = -1;           // wavefront, mailbox scenes: brute-force + replay trace kernel: -1 default (on)
-    int fuse = -1;         // bf trace fused with the shading (k_wf_step_bf): -1 default (on)
-    int trav = -1;         // traversal: -1 per-pipeline default, 0 nested, 1 flat, 2 predicated, 3 lean, 4..8 lean2..lean32
-    int sort = -1;         // traversal pipeline: survivors grouped per shade block by 8 / 64 / 512 coherence keys (0 off): -1 default (512)
-    int bf_slots = -1;     // brute-force kernels: hit slots per lane (< kBfSlots: tests of the recompute path): -1 default
-    int trace_blocks = 0;  // traversal / step kernels: cap on the grid (tests): 0 = occupancy-derived
-    int trace_sparse = -1; // k_wf_trace: narrower windows when 32-entry ones keep < 1/n of the waves busy (n; 0 off): -1 default
-    int region_perm = -1;  // k_wf_step_bf: camera batches dealt to regions by a permutation (WfBuffers::rq); -1 default
-    int trace_ring = 0;    // k_wf_trace's hit ring: 0 auto, 128 or 256
-    uint32_t watchdog = 0; // k_wf_trace iterations before a wave gives up (tests of the failure report): 0 default
-    int leaf_blocks = 0;   // k_wf_leafpass grid (A/B): 0 = occupancy-derived
-    int leaf_pairs = 5;    // k_wf_leafpass walks chunked leaves by (ray, chunk) pairs (option leaf_pairs; | 4: leaf_refine)
-    int regen = 0;         // fused kernel: camera batches per region admitted by every extension launch (0: all at once)
-};
-
+// LaunchOpts (the per-call options, with their defaults): pt_flavour.h
 bool scene_fits_lds(const SceneView& sc);
 
 // Wavefront path state (HBM), `capacity` entries per queue; see pt_wavefront.hip.  Every
@@ -131,26 +108,13 @@ constexpr uint32_t kRegions = 512;
 constexpr uint32_t kQueueSlackRegions = 4096;
 constexpr size_t kWfBytesPerPath = 64 + 64 + 40 + 8 + 12;
 
-// Dual-stream wavefront: two streams owned by the scene, created back to back so that HIP's
+// The wavefront's parts: streams owned by the scene, created back to back so that HIP's
 // round-robin stream -> hardware-queue mapping puts them on different queues (a shared queue
-// serialises the halves), plus fork/join events with the caller's stream.  Null = one stream.
+// serialises the parts), plus fork/join events with the caller's stream.  Null = one stream.
 constexpr int kMaxParts = 4;  // parts of a wavefront batch on their own streams (LaunchOpts::parts)
 struct WfStreams {
     hipStream_t aux[kMaxParts] = {};
     hipEvent_t fork = nullptr, join[kMaxParts] = {};
-    bool fuse_gen = true;  // LaunchOpts::fuse_gen
-    int nparts = 2;
-    int sort_bins = 0;     // LaunchOpts::sort: k_wf_shade groups a block's survivors by a coherence key of 8 / 64 / 512 values (0: off)
-    // per-call launch shape (LaunchOpts, filled by launch_wavefront)
-    int trace_blocks = 0;  // cap on the trace / step grid (0: occupancy-derived)
-    int trace_sparse = 0;  // k_wf_trace windows below 32 entries for short queues (LaunchOpts::trace_sparse)
-    int region_perm = 0;   // LaunchOpts::region_perm
-    int trace_ring = 0;    // LaunchOpts::trace_ring
-    int bf_slots = -1;     // hit slots per lane of the brute-force kernels (-1: kBfSlots)
-    uint32_t watchdog = 0; // k_wf_trace iteration limit (0: kTraceWatchdog)
-    int leaf_blocks = 0;   // LaunchOpts::leaf_blocks
-    int leaf_pairs = 5;    // LaunchOpts::leaf_pairs
-    int regen = 0;         // LaunchOpts::regen
 };
 hipError_t launch_wavefront(const LaunchOpts& lo, const SceneView& sc, const FrameParams& fp, const WfBuffers& wb,
                             uint32_t frame0, uint32_t nframes, uint32_t stride, bool accum, bool count, float* out,

@@ -108,14 +108,10 @@ struct alignas(16) PreLeaf {
 };
 static_assert(offsetof(PreLeaf, c0) == 16 && offsetof(PreLeaf, path) == 32, "k_wf_leafpass reads PreLeaf as ints 4, 5, 8..");
 
-// leaf remainders (pt_leafskip.cpp, SceneView::nalt): per leaf child, kLeafAlt earlier leaves whose
-// entries its remainders leave out; leaves of fewer than kLeafSkipMaxLeaf entries have them (the
-// count is 7 bits of the descriptor; big-leaf thresholds below it turn the skip off, pt_capi.hip)
-#ifndef PT_LEAF_ALT
-#define PT_LEAF_ALT 1
-#endif
-constexpr int kLeafAlt = PT_LEAF_ALT;
-static_assert(kLeafAlt == 1 || kLeafAlt == 4, "one or four (prev, remainder) pairs per side");
+// leaf remainders (pt_leafskip.cpp, SceneView::nalt): per leaf child, one earlier leaf whose entries
+// its remainder leaves out (four per side measured 10-12 % slower); leaves of fewer
+// than kLeafSkipMaxLeaf entries have them (the count is 7 bits of the descriptor; big-leaf thresholds
+// below it turn the skip off, pt_capi.hip)
 constexpr int kLeafSkipMaxLeaf = 64;
 
 struct alignas(16) Material {
@@ -177,7 +173,7 @@ struct SceneView {
     // i2 < vn_range (the branch applies); global memory, read for the winning record only
     const float4* tnorm;
     int32_t vnormals;
-    // big leaves in step (lean traversal, TRAV + 160): the lanes of a wave walk a leaf of at least
+    // big leaves in step (lean traversal, FLV_BIG): the lanes of a wave walk a leaf of at least
     // big_leaf entries in one shared rotated order (lean_leaf_loop; 0 = off)
     int32_t big_leaf;
     // leaf chunks (pt_leafbvh.cpp; nullptr when the scene has none or option leaf_walk=0): chunks,
@@ -198,7 +194,7 @@ struct SceneView {
     // the traversal kernel's per-wave LDS keys (64: lean_leaf_pool's per-lane bests, the first
     // kMultiRays of them chunk_turn_multi's; set by k_wf_trace, nullptr in the other kernels)
     uint64_t* lkeys;
-    // big leaves resolved before the traversal (k_wf_leafpass; the wavefront's TRAV 26x/27x
+    // big leaves resolved before the traversal (k_wf_leafpass; the wavefront's FLV_PRE
     // instances): the npre leaves of pre (device table, the largest first) are exactly the leaves of
     // at least big_leaf entries; pres[b * pres_stride + i] is queue entry i's (t, position) key for
     // leaf b (set by k_wf_trace from its part's WfBuffers; nullptr elsewhere)
@@ -208,11 +204,12 @@ struct SceneView {
     const uint64_t* pres;
     int32_t pre_rec0[kMaxPre];  // pre[b].rec0 by value (kernel arguments: the traversal's slot lookup in SGPRs)
     // leaf remainders (pt_leafskip.cpp; nullptr: none or option leaf_skip=0): per node, per side,
-    // kLeafAlt pairs (first record of the leaf M the ray tested last, the remainder "this leaf minus
+    // one pair (first record of the leaf M the ray tested last, the remainder "this leaf minus
     // M" as first record << 7 | count); the lean node step takes the remainder whose M matches
     // TravLean::last (pt_device.h lean_node_unit).  Global memory, never staged into LDS
     const int4* nalt;
 };
+static_assert(sizeof(int4) == 2 * sizeof(int2), "a node's two (prev, remainder) int2 pairs (pt_leafskip.cpp) are exactly one int4");
 
 // Per-call camera/settings block derived from the reference's 48-float meta
 // (program-raymarch.wgsl:11-22, program-raymarch.ts:79-92).

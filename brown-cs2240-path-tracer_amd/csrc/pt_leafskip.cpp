@@ -13,10 +13,10 @@
 // wins, so ties resolve as before.
 //
 // The per-ray state is one int: the first record of the last non-empty leaf the ray tested
-// (TravLean::last).  For a leaf L, `alts` earlier leaves M are chosen, and for each the remainder
+// (TravLean::last).  For a leaf L, one earlier leaf M is chosen, and the remainder
 // "L minus M" — L's records whose uid M holds removed, order kept — is appended to the records.
-// A node step that enters a leaf child L whose ray came from one of its M tests that remainder
-// instead (nalt: per node and side, `alts` pairs (M's first record, remainder first record << 7 |
+// A node step that enters a leaf child L whose ray came from its M tests that remainder
+// instead (nalt: per node and side, one pair (M's first record, remainder first record << 7 |
 // count)).  scripts/leaf_repeats_ring.py measured the catch on host models of the reference
 // traversal: of Glossy's 18.5 repeated tests per ray (52.5 tests), the last leaf holds 15.1; four
 // probe-chosen leaves per L catch 14.1, the nearest earlier leaves alone 11.1.
@@ -69,11 +69,11 @@ bool skip_tri(const Tri& tr, const SkipRay& r, float& t) {
 }  // namespace
 
 void build_leaf_skips(const std::vector<Node>& nodes, std::vector<Tri>& tris, std::vector<float4>& tnorm,
-                      const std::vector<Light>& lights, int max_leaf, int alts, uint64_t max_tests,
+                      const std::vector<Light>& lights, int max_leaf, uint64_t max_tests,
                       std::vector<int2>& nalt, LeafSkipStats* stats) {
     nalt.clear();
     if (stats) *stats = LeafSkipStats{};
-    if (alts <= 0 || nodes.empty() || tris.empty()) return;
+    if (nodes.empty() || tris.empty()) return;
     max_leaf = std::min(max_leaf, kLeafSkipMaxLeaf);
     // the leaves (non-empty leaf children), by first record; their uid sets, sorted
     std::unordered_map<int32_t, int32_t> leaf_of;  // first record -> leaf index
@@ -210,16 +210,15 @@ void build_leaf_skips(const std::vector<Node>& nodes, std::vector<Tri>& tris, st
         }
         if (stats) stats->probe_tests = tests;
     }
-    // per leaf L: up to `alts` earlier leaves M sharing entries with it — the probe's most frequent
-    // last leaves before L weighted by what they share, then the nearest sharing predecessors in
-    // the visit order
+    // per leaf L: one earlier leaf M sharing entries with it — the probe's most frequent last leaf
+    // before L weighted by what they share, else the nearest sharing predecessor in the visit order
     std::vector<std::vector<std::pair<double, int32_t>>> cand(nl);
     for (const auto& kv : seen_pair) {
         const size_t l = (size_t)(kv.first >> 32), m = (size_t)(uint32_t)kv.first;
         const size_t sh = shared(l, m);
         if (sh) cand[l].emplace_back((double)kv.second * (double)sh, (int32_t)m);
     }
-    nalt.assign(nodes.size() * 2 * (size_t)alts, make_int2(INT32_MIN, 0));
+    nalt.assign(nodes.size() * 2, make_int2(INT32_MIN, 0));
     std::vector<std::vector<int2>> chosen(nl);  // (M's first record, desc) per leaf
     const size_t cap = tris.size();  // the remainders' records at most double the scene's
     size_t added = 0;
@@ -229,24 +228,17 @@ void build_leaf_skips(const std::vector<Node>& nodes, std::vector<Tri>& tris, st
         std::sort(c.begin(), c.end(), [](const std::pair<double, int32_t>& x, const std::pair<double, int32_t>& y) {
             return x.first > y.first || (x.first == y.first && x.second < y.second);
         });
-        std::vector<int32_t> ms;
-        for (const auto& x : c) {
-            if ((int)ms.size() >= alts) break;
-            ms.push_back(x.second);
-        }
-        for (int32_t k = opos[l] - 1, look = 0; k >= 0 && (int)ms.size() < alts && look < 64; --k, ++look) {
-            const int32_t m = order[(size_t)k];
-            if (std::find(ms.begin(), ms.end(), m) == ms.end() && shared(l, (size_t)m)) ms.push_back(m);
-        }
-        for (int32_t m : ms) {
+        int32_t m = c.empty() ? -1 : c.front().second;
+        for (int32_t k = opos[l] - 1, look = 0; k >= 0 && m < 0 && look < 64; --k, ++look)
+            if (shared(l, (size_t)order[(size_t)k])) m = order[(size_t)k];
+        if (m >= 0) {
             std::vector<int32_t> keep;
             for (int32_t k = 0; k < cnt[l]; ++k) {
                 const int32_t u = tris[(size_t)(rec0[l] + k)].uid;
                 if (!std::binary_search(uids[(size_t)m].begin(), uids[(size_t)m].end(), u)) keep.push_back(k);
             }
-            if ((int32_t)keep.size() == cnt[l]) continue;
             const size_t start = tris.size();
-            if (added + keep.size() > cap || start + keep.size() >= ((size_t)1 << 24)) break;
+            if ((int32_t)keep.size() == cnt[l] || added + keep.size() > cap || start + keep.size() >= ((size_t)1 << 24)) continue;
             for (int32_t k : keep) {
                 Tri t = tris[(size_t)(rec0[l] + k)];
                 t.lbvh = 0;
@@ -266,7 +258,7 @@ void build_leaf_skips(const std::vector<Node>& nodes, std::vector<Tri>& tris, st
             const int32_t c = side ? nodes[n].rcnt : nodes[n].lcnt, ref = side ? nodes[n].rref : nodes[n].lref;
             if (c <= 0) continue;
             const auto& ch = chosen[(size_t)leaf_of[ref]];
-            for (size_t a = 0; a < ch.size(); ++a) nalt[(n * 2 + (size_t)side) * (size_t)alts + a] = ch[a];
+            if (!ch.empty()) nalt[n * 2 + (size_t)side] = ch[0];
         }
     }
     if (stats) stats->records = added;

@@ -213,17 +213,12 @@ __host__ __device__ constexpr uint32_t stage_bytes(uint32_t ring) { return kWinR
 // after the waves' stages, when the scene needs them (pooled leaf turns or leaf chunks: keys_on),
 // 64 keys per wave — one per lane for lean_leaf_pool, the first kMultiRays for chunk_turn_multi
 constexpr uint32_t kKeyBytes = 64 * 8;
-// Only the lean flavours pool leaf turns or walk chunks (trav_step_lean; not the mailboxed 1xx nor
-// the flattened 1 / 2), so only their instances reserve the keys (advisor r04: every instance did)
-template <int TRAV>
-__host__ __device__ constexpr bool lean_flavour() { return TRAV >= 3 && !(TRAV >= 100 && TRAV < 160) && TRAV < 300; }
+// Only the lean flavours pool leaf turns or walk chunks (trav_step_lean; not the mailboxed nor the
+// flattened ones), so only their instances reserve the keys (advisor r04: every instance did)
 template <int TRAV>
 __host__ __device__ inline bool keys_on(const SceneView& sc) {
-    return lean_flavour<TRAV>() && (sc.leaf_pool != 0 || sc.lnodes != nullptr);
+    return flv_lean(TRAV) && (sc.leaf_pool != 0 || sc.lnodes != nullptr);
 }
-// the traversal flavours that have a 256-entry-ring instance (the defaults: lean16 + fast rcp, with
-// and without big-leaf turns); the others always use 128
-constexpr bool has_big_ring(int trav) { return trav == 17 || trav == 177 || trav == 277; }
 constexpr uint32_t kTraceBlock = 512;  // 8 waves share one LDS copy of the scene
 // LDS of k_wf_trace per block: the lanes' traversal stacks (max_stack entries of 4 B) and per wave
 // stage_bytes(ring)
@@ -255,7 +250,7 @@ __device__ __forceinline__ void wf_trace_body(SceneView sc, WfBuffers wb, int in
     char* key_base = stage_base + (blockDim.x / 64u) * stage_bytes(nring);
     const uint32_t key_bytes = keys_on<TRAV>(sc) ? (blockDim.x / 64u) * kKeyBytes : 0u;
     sc.lkeys = key_bytes ? reinterpret_cast<uint64_t*>(key_base + (threadIdx.x / 64u) * kKeyBytes) : nullptr;
-    sc.pres = wb.pres;  // this part's pre-resolved big leaves (TRAV 26x / 27x; k_wf_leafpass)
+    sc.pres = wb.pres;  // this part's pre-resolved big leaves (FLV_PRE; k_wf_leafpass)
     sc.pres_stride = wb.pres_stride;
     if (blockIdx.x == 0 && threadIdx.x == 0) wb.ctl[in_q ? WF_COUNT0 : WF_COUNT1] = 0;  // shade's output count
     const uint32_t count = wb.ctl[WF_WATCHDOG] ? 0u : wb.ctl[in_q ? WF_COUNT1 : WF_COUNT0];  // gave up: skip
@@ -375,7 +370,7 @@ __device__ __forceinline__ void wf_trace_body(SceneView sc, WfBuffers wb, int in
                     r = unpack_ray(wray[2 * o], wray[2 * o + 1], p);
                     sq = k;
                     trav_init(s, true);
-                    if constexpr (TRAV >= 260 && TRAV < 300) s.qi = wcur * wr + o;  // its queue entry
+                    if constexpr (flv_pre(TRAV)) s.qi = wcur * wr + o;  // its queue entry
                     has = true;
                 }
                 cur = min(cur + (uint32_t)__popcll(need), wend);
@@ -407,7 +402,7 @@ __global__ __launch_bounds__(kTraceBlock) void k_wf_trace(SceneView sc, WfBuffer
                                                           uint32_t watchdog, int sparse) {
     wf_trace_body<LDS, TRAV, COUNT, RING, PRUN>(sc, wb, in_q, cnt_out, watchdog, sparse);
 }
-// The instances with pre-resolved big leaves (TRAV 26x / 27x): held to 80 VGPRs, 6 waves per SIMD
+// The instances with pre-resolved big leaves (FLV_PRE): held to 80 VGPRs, 6 waves per SIMD
 // (83 unconstrained: 5 waves)
 #ifndef PT_TRACE_PRE_WAVES
 #define PT_TRACE_PRE_WAVES 6
@@ -433,8 +428,7 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(PT_
 // Exact: a triangle test is a pure function of (ray, record), so phase 1 computes the same t
 // (and hit predicate) the traversal would, and phase 2 applies them in the mailboxed order
 // with the same strict-< update, tie-break and pruning; tests of entries the traversal never
-// reaches have no effect.  A ray with more than `nslots` (<= kBfSlots) hits recomputes the rest on demand.
-constexpr int kBfSlots = 8;
+// reaches have no effect.  A ray with more than `nslots` (<= kBfSlots, pt_flavour.h) hits recomputes the rest on demand.
 __device__ __forceinline__ TriRec load_tri_scalar(const Tri* tris, int i) {
     // uniform index: constant address space, so the record comes through s_load (no VGPRs)
     const __attribute__((address_space(4))) float* f = (const __attribute__((address_space(4))) float*)(tris + i);
@@ -1029,19 +1023,18 @@ __global__ __launch_bounds__(256) void k_wf_accum(const float* __restrict__ rad,
         const hipError_t e_ = (expr);            \
         if (e_ != hipSuccess) return e_;         \
     } while (0)
-// TRAV >= 300: the brute-force + replay kernel (k_wf_trace_bf; + 10: fast reciprocal); >= 400: fused
-// with the shading (k_wf_step_bf)
+// the kernel of a flavour (pt_flavour.h)
 template <bool LDS, int TRAV, bool COUNT, uint32_t RING = kHitRing, int PRUN = 4>
 constexpr const void* trace_kernel() {
-    if constexpr (TRAV >= 400) return (const void*)k_wf_step_bf<false, LDS, ((TRAV / 10) & 1) != 0, COUNT>;
-    else if constexpr (TRAV >= 300) return (const void*)k_wf_trace_bf<LDS, ((TRAV / 10) & 1) != 0, COUNT>;
-    else if constexpr (TRAV >= 260) return (const void*)k_wf_trace_pre<LDS, TRAV, COUNT, RING, PRUN>;
+    if constexpr (flv_fused(TRAV)) return (const void*)k_wf_step_bf<false, LDS, flv_fast(TRAV), COUNT>;
+    else if constexpr (flv_brute_force(TRAV)) return (const void*)k_wf_trace_bf<LDS, flv_fast(TRAV), COUNT>;
+    else if constexpr (flv_pre(TRAV)) return (const void*)k_wf_trace_pre<LDS, TRAV, COUNT, RING, PRUN>;
     else return (const void*)k_wf_trace<LDS, TRAV, COUNT, RING, PRUN>;
 }
 // the k_wf_trace instances with a 256-entry ring and with pooled runs of 2 (SceneView::leaf_pool
-// == 2): the default flavours, uncounted (the others pool runs of 4: the same bits and counts)
+// == 2): the default flavours (flv_big_ring), uncounted (the others pool runs of 4: the same bits and counts)
 template <int TRAV, bool COUNT>
-constexpr bool has_variants() { return TRAV < 300 && has_big_ring(TRAV) && !COUNT; }
+constexpr bool has_variants() { return flv_big_ring(TRAV) && !COUNT; }
 template <bool LDS, int TRAV, bool COUNT>
 static const void* trace_instance(uint32_t ring, bool run2) {
     if constexpr (has_variants<TRAV, COUNT>()) {
@@ -1056,7 +1049,7 @@ static const void* trace_instance(uint32_t ring, bool run2) {
 template <bool LDS, int TRAV, bool COUNT>
 static size_t trace_lds(const SceneView& sc, uint32_t ring = kHitRing) {
     const size_t span = LDS ? sc.span_bytes : 0;
-    if (TRAV >= 300) return (size_t)sc.max_stack * kTraceBlock * 4 + (kTraceBlock / 64) * ((size_t)kBfSlots * 64 * 4) + span;
+    if (flv_brute_force(TRAV)) return (size_t)sc.max_stack * kTraceBlock * 4 + (kTraceBlock / 64) * ((size_t)kBfSlots * 64 * 4) + span;
     return (size_t)sc.max_stack * 4 * kTraceBlock + (kTraceBlock / 64) * (stage_bytes(ring) + (keys_on<TRAV>(sc) ? kKeyBytes : 0)) + span;
 }
 // resident blocks of `kernel` per CU at `lds` bytes of dynamic LDS, times the CUs: the persistent
@@ -1109,20 +1102,20 @@ static WfBuffers wb_part(const WfBuffers& wb, int h, int nparts, size_t rad_off)
 template <int TRAV, bool COUNT>
 static SceneView bf_view(const SceneView& sc) {
     SceneView v = sc;
-    if (TRAV >= 300 && !COUNT && sc.bfnode) v.max_stack = 0;
+    if (flv_brute_force(TRAV) && !COUNT && sc.bfnode) v.max_stack = 0;
     return v;
 }
 
 template <bool LDS, int TRAV, bool COUNT>
 static hipError_t wf_render_t(const SceneView& sc_in, const FrameParams& fp, const WfBuffers& wb, uint32_t frame0,
                               uint32_t nframes, uint32_t stride, bool accum, float* out, Counters* cnt,
-                              hipStream_t stream, const WfStreams& ws) {
+                              hipStream_t stream, const WfStreams& ws, const LaunchOpts& lo) {
     SceneView sc = bf_view<TRAV, COUNT>(sc_in);
     const uint32_t npix = fp.width * fp.height;
-    // the batch in ws.nparts parts on as many streams when a part holds at least a frame: one
+    // the batch in lo.parts parts on as many streams when a part holds at least a frame: one
     // part's kernel fills the others' launch tails and boundaries (and, with separate trace and
     // shade kernels, a VALU-bound trace runs beside an HBM-bound shade)
-    int np = ws.aux[0] != nullptr ? ws.nparts : 1;
+    int np = lo.dual && ws.aux[0] != nullptr ? std::max(1, std::min(kMaxParts, lo.parts)) : 1;
     while (np > 1 && (nframes < (uint32_t)np || wb.capacity / np < npix)) np /= 2;
     const uint32_t F = np * std::max<uint32_t>(1, std::min<uint32_t>((nframes + np - 1) / np, (uint32_t)(wb.capacity / np / npix)));
     // k_wf_trace's instance: the 256-entry hit ring when its extra 8 KB per block cost no block per
@@ -1142,22 +1135,23 @@ static hipError_t wf_render_t(const SceneView& sc_in, const FrameParams& fp, con
     if constexpr (has_variants<TRAV, COUNT>()) {
         const size_t l1 = trace_lds<LDS, TRAV, COUNT>(sc, kHitRing), l2 = trace_lds<LDS, TRAV, COUNT>(sc, kHitRingMax);
         const bool fits = l2 <= max_block_lds() &&
-                          (ws.trace_ring == (int)kHitRingMax ||
-                           (ws.trace_ring <= 0 && occupancy_blocks(trace_instance<LDS, TRAV, COUNT>(kHitRingMax, run2), l2) >=
+                          (lo.trace_ring == (int)kHitRingMax ||
+                           (lo.trace_ring <= 0 && occupancy_blocks(trace_instance<LDS, TRAV, COUNT>(kHitRingMax, run2), l2) >=
                                                       occupancy_blocks(trace_instance<LDS, TRAV, COUNT>(kHitRing, run2), l1)));
         if (fits) nring = kHitRingMax;
     }
     const size_t lds = trace_lds<LDS, TRAV, COUNT>(sc, nring);
     int tblocks = occupancy_blocks(trace_instance<LDS, TRAV, COUNT>(nring, run2), lds);
-    if (ws.trace_blocks > 0) tblocks = std::min(tblocks, ws.trace_blocks);  // option wf_trace_blocks (tests)
+    if (lo.trace_blocks > 0) tblocks = std::min(tblocks, lo.trace_blocks);  // option wf_trace_blocks (tests)
     const int iters = 2 * (fp.max_depth + 1);
     // option trace_watchdog: tests of the failure report
-    const uint32_t watchdog = ws.watchdog > 0 ? ws.watchdog : kTraceWatchdog;
-    const int sparse = std::max(0, std::min(ws.trace_sparse, 1 << 20));
+    const uint32_t watchdog = lo.watchdog > 0 ? lo.watchdog : kTraceWatchdog;
+    const int sparse = std::max(0, std::min(lo.trace_sparse, 1 << 20));
     // option bf_slots < kBfSlots: tests of the recompute path
-    const int bf_slots = ws.bf_slots >= 0 ? std::min(kBfSlots, ws.bf_slots) : kBfSlots;
-    if constexpr (TRAV >= 400) {  // the camera batches' table (k_wf_camtab), before every part's GEN launch
-        if (ws.fuse_gen) {
+    const int bf_slots = std::min(kBfSlots, lo.bf_slots);
+    const int sort_bins = lo.sort > 0 ? (lo.sort >= 512 ? 512 : lo.sort >= 64 ? 64 : 8) : 0;
+    if constexpr (flv_fused(TRAV)) {  // the camera batches' table (k_wf_camtab), before every part's GEN launch
+        if (lo.fuse_gen) {
             if (sc.n_tris - sc.mb_base > 64) return hipErrorInvalidValue;  // mailbox scenes: <= 64 entries
             hipLaunchKernelGGL(k_wf_camtab, dim3(1), dim3(64), 0, stream, sc, fp, wb.camtab);
         }
@@ -1178,12 +1172,12 @@ static hipError_t wf_render_t(const SceneView& sc_in, const FrameParams& fp, con
             f0 += fh;
             ++nh;
         }
-        if constexpr (TRAV >= 400) {  // region-partitioned queues (k_wf_step_bf)
+        if constexpr (flv_fused(TRAV)) {  // region-partitioned queues (k_wf_step_bf)
             const uint32_t R = std::min<uint32_t>(kRegions, (uint32_t)tblocks * (kTraceBlock / 64));
             // region_perm: region r takes camera batches r q mod R (q ~ 0.618 R, coprime with R), so
             // the 8 waves of a block (8 neighbouring regions) work on batches far apart in the image
             uint32_t q = 1, qi = 1;
-            if (ws.region_perm && R > 2) {
+            if (lo.region_perm && R > 2) {
                 auto gcd = [](uint32_t a, uint32_t b) { while (b) { const uint32_t t = a % b; a = b; b = t; } return a; };
                 q = std::max<uint32_t>(1, (uint32_t)(R * 0.6180339887498949));
                 while (gcd(q, R) != 1) ++q;
@@ -1202,7 +1196,7 @@ static hipError_t wf_render_t(const SceneView& sc_in, const FrameParams& fp, con
         // before the fork: on a part's stream the second part's memset waited ~0.5 ms for a CU slot
         // behind the first part's first launch, and the parts ran that far apart (a kernel trace of
         // the bench, r06m)
-        const bool fgen = TRAV >= 400 && ws.fuse_gen;
+        const bool fgen = flv_fused(TRAV) && lo.fuse_gen;
         if (fgen)
             for (int h = 0; h < nh; ++h)
                 HIP_RETURN_IF(hipMemsetAsync(pv[h].w.rcnt + kRegions, 0, kRegions * sizeof(uint32_t), stream));
@@ -1214,12 +1208,12 @@ static hipError_t wf_render_t(const SceneView& sc_in, const FrameParams& fp, con
         // admitted by each extension launch; regen_cam = the most camera batches of any region
         uint32_t regen_q = 0, regen_cam = 0;
         int iters_b = iters;
-        if (TRAV >= 400 && fgen && ws.regen > 0) {
+        if (fgen && lo.regen > 0) {
             for (int h = 0; h < nh; ++h) {
                 const uint32_t nbat = (pv[h].P + 63) / 64;
                 regen_cam = std::max(regen_cam, (nbat + pv[h].w.nreg - 1) / pv[h].w.nreg);
             }
-            regen_q = (uint32_t)ws.regen;
+            regen_q = (uint32_t)lo.regen;
             if (regen_q < regen_cam)  // J admitting launches, the last admission's paths need max_depth + 1 more
                 iters_b = 2 * ((int)((regen_cam + regen_q - 1) / regen_q) + fp.max_depth);
             else
@@ -1235,9 +1229,8 @@ static hipError_t wf_render_t(const SceneView& sc_in, const FrameParams& fp, con
             const hipStream_t st = pv[h].st;
             const WfBuffers& w = pv[h].w;
             const int sblocks = (int)((pv[h].P + kShadeBlock - 1) / kShadeBlock);
-            if constexpr (TRAV >= 400) {  // trace + shade in one launch
-                constexpr bool rcp = ((TRAV / 10) & 1) != 0;
-#define PT_STEP(E, G) PT_LAUNCH(KID_WF_STEP, st, (k_wf_step_bf<E, LDS, rcp, COUNT, G>), dim3(tblocks), dim3(kTraceBlock), \
+            if constexpr (flv_fused(TRAV)) {  // trace + shade in one launch
+#define PT_STEP(E, G) PT_LAUNCH(KID_WF_STEP, st, (k_wf_step_bf<E, LDS, flv_fast(TRAV), COUNT, G>), dim3(tblocks), dim3(kTraceBlock), \
                                 lds, st, sc, fp, w, it, cnt, bf_slots, frame0, stride, pv[h].fbase, pv[h].P, !accum, regen_q)
                 if (regen_q > 0 && (it & 1) == 0 && (uint32_t)(it / 2) * regen_q < regen_cam) PT_STEP(true, 2);
                 else if (fgen && it == 0) PT_STEP(true, 1);
@@ -1245,15 +1238,15 @@ static hipError_t wf_render_t(const SceneView& sc_in, const FrameParams& fp, con
                 else PT_STEP(false, 0);
 #undef PT_STEP
                 return hipSuccess;
-            } else if constexpr (TRAV >= 300) {
-                PT_LAUNCH(KID_WF_TRACE, st, (k_wf_trace_bf<LDS, ((TRAV / 10) & 1) != 0, COUNT>), dim3(tblocks),
+            } else if constexpr (flv_brute_force(TRAV)) {
+                PT_LAUNCH(KID_WF_TRACE, st, (k_wf_trace_bf<LDS, flv_fast(TRAV), COUNT>), dim3(tblocks),
                           dim3(kTraceBlock), lds, st, sc, w, in_q, cnt, bf_slots);
             } else {
-                if constexpr (TRAV >= 260 && TRAV < 300)  // the big leaves first (k_wf_leafpass)
-                    HIP_RETURN_IF(launch_leafpass(sc, w, in_q, ((TRAV / 10) & 1) != 0, ws.leaf_blocks, ws.leaf_pairs, st));
+                if constexpr (flv_pre(TRAV))  // the big leaves first (k_wf_leafpass)
+                    HIP_RETURN_IF(launch_leafpass(sc, w, in_q, flv_fast(TRAV), lo.leaf_blocks, lo.leaf_pairs, st));
 #define PT_TRACE(RG, PR)                                                                                        \
     do {                                                                                                        \
-        if constexpr (TRAV >= 260)                                                                              \
+        if constexpr (flv_pre(TRAV))                                                                            \
             PT_LAUNCH(KID_WF_TRACE, st, (k_wf_trace_pre<LDS, TRAV, COUNT, RG, PR>), dim3(tblocks), dim3(kTraceBlock), \
                       lds, st, sc, w, in_q, cnt, watchdog, sparse);                                             \
         else                                                                                                    \
@@ -1272,10 +1265,10 @@ static hipError_t wf_render_t(const SceneView& sc_in, const FrameParams& fp, con
             }
             if ((it & 1) == 0)
                 PT_LAUNCH(KID_WF_SHADE_EXT, st, (k_wf_shade<true, COUNT>), dim3(sblocks), dim3(kShadeBlock), 0, st, sc, fp,
-                          w, cnt, ws.sort_bins);
+                          w, cnt, sort_bins);
             else
                 PT_LAUNCH(KID_WF_SHADE_SHADOW, st, (k_wf_shade<false, COUNT>), dim3(sblocks), dim3(kShadeBlock), 0, st, sc,
-                          fp, w, cnt, ws.sort_bins);
+                          fp, w, cnt, sort_bins);
             return hipSuccess;
         };
         for (int it = 0; it < iters_b; ++it) {
@@ -1296,67 +1289,22 @@ static hipError_t wf_render_t(const SceneView& sc_in, const FrameParams& fp, con
     return hipGetLastError();
 }
 
-hipError_t launch_wavefront(const LaunchOpts& lo, const SceneView& scene, const FrameParams& fp, const WfBuffers& wb,
+hipError_t launch_wavefront(const LaunchOpts& lo, const SceneView& sc, const FrameParams& fp, const WfBuffers& wb,
                             uint32_t frame0, uint32_t nframes, uint32_t stride, bool accum, bool count, float* out,
-                            Counters* cnt, hipStream_t stream, const WfStreams& ws_in) {
-    WfStreams ws = lo.dual != 0 ? ws_in : WfStreams{};  // parts on streams by default: +15 % measured (in-process A/B)
-    ws.nparts = std::max(1, std::min(kMaxParts, lo.parts > 0 ? lo.parts : 2));
-    ws.fuse_gen = lo.fuse_gen != 0;
-    // survivors grouped per shade block by direction octant and origin cell (PT_SORT; default 512
-    // keys = 8 octants x 4^3 cells: CornellBox-Glossy +4.7 % with 64 keys, +1.2 % more with 512,
-    // MedievalBoat unchanged, in-process A/B)
-    const int sort = lo.sort >= 0 ? lo.sort : 512;
-    ws.sort_bins = sort > 0 ? (sort >= 512 ? 512 : sort >= 64 ? 64 : 8) : 0;
-    ws.trace_blocks = lo.trace_blocks;
-    ws.trace_sparse = std::max(0, lo.trace_sparse);
-    ws.region_perm = lo.region_perm > 0 ? 1 : 0;
-    ws.regen = std::max(0, lo.regen);
-    ws.trace_ring = lo.trace_ring;
-    ws.bf_slots = lo.bf_slots;
-    ws.watchdog = lo.watchdog;
-    ws.leaf_blocks = lo.leaf_blocks;
-    ws.leaf_pairs = lo.leaf_pairs;
+                            Counters* cnt, hipStream_t stream, const WfStreams& ws) {
     if (!accum) { nframes = 1; stride = 1; }
-    SceneView sc = scene;  // node_bias <= 0: chosen per instance in wf_render_t
     const bool lds = lo.lds && scene_fits_lds(sc);
-    // lean16 with the fast reciprocal by default (measured best on gfx950, scripts/perf_variants.py);
-    // the wavefront always uses a flattened traversal; lean flavours take the fast reciprocal
-    // (+10) when it is exact for the scene
-    const int base = lo.trav < 0 ? 7 : (lo.trav == 0 ? 1 : lo.trav);
-    const bool fast = lo.fast_rcp != 0 && sc.fast_rcp;
-    // mailboxed lean<K> (+100) for scenes with <= 64 distinct leaf entries
-    const bool mb = lo.mailbox != 0 && sc.mailbox && base >= 5 && base <= 8;
-    // brute force + replay (k_wf_trace_bf) by default for mailbox scenes; an explicit trav option
-    // or bf=0 keeps the traversal kernels
-    const bool bf = lo.bf != 0 && lo.mailbox != 0 && sc.mailbox && lo.trav < 0;
-    // big-leaf cooperation (+160) for lean<4..16> on scenes with leaves of >= big_leaf entries; those
-    // leaves resolved before the traversal instead (+260, k_wf_leafpass) when the scene's table of
-    // pre-resolved leaves holds them (render_impl: option leaf_pre, default on) and the buffers exist
-    const bool big = !bf && !mb && sc.big_leaf > 0 && base >= 5 && base <= 7;
-    const bool pre = big && sc.npre > 0 && sc.pre && wb.pres;
-    const int trav = bf ? (lo.fuse == 0 ? 300 : 400) + (fast ? 10 : 0)
-                   : mb ? 100 + base + (fast ? 10 : 0)
-                        : base + ((base >= 3 && fast) ? 10 : 0) + (big ? (pre ? 260 : 160) : 0);
-#define WF(L, T)                                                                                               \
-    if (trav == T) {                                                                                           \
-        if (count) return wf_render_t<L, T, true>(sc, fp, wb, frame0, nframes, stride, accum, out, cnt, stream, ws); \
-        return wf_render_t<L, T, false>(sc, fp, wb, frame0, nframes, stride, accum, out, cnt, stream, ws);         \
-    }
-    if (lds) {
-        WF(true, 1) WF(true, 2) WF(true, 3) WF(true, 4) WF(true, 5) WF(true, 6) WF(true, 7) WF(true, 8)
-        WF(true, 13) WF(true, 14) WF(true, 15) WF(true, 16) WF(true, 17) WF(true, 18)
-        WF(true, 300) WF(true, 310) WF(true, 400) WF(true, 410)
-        WF(true, 105) WF(true, 106) WF(true, 107) WF(true, 115) WF(true, 116) WF(true, 117) WF(true, 118)
-        WF(true, 165) WF(true, 166) WF(true, 167) WF(true, 175) WF(true, 176) WF(true, 177)
-        WF(true, 265) WF(true, 266) WF(true, 267) WF(true, 275) WF(true, 276) WF(true, 277)
-    } else {
-        WF(false, 1) WF(false, 2) WF(false, 3) WF(false, 4) WF(false, 5) WF(false, 6) WF(false, 7) WF(false, 8)
-        WF(false, 13) WF(false, 14) WF(false, 15) WF(false, 16) WF(false, 17) WF(false, 18)
-        WF(false, 300) WF(false, 310) WF(false, 400) WF(false, 410)
-        WF(false, 105) WF(false, 106) WF(false, 107) WF(false, 115) WF(false, 116) WF(false, 117) WF(false, 118)
-        WF(false, 165) WF(false, 166) WF(false, 167) WF(false, 175) WF(false, 176) WF(false, 177)
-        WF(false, 265) WF(false, 266) WF(false, 267) WF(false, 275) WF(false, 276) WF(false, 277)
-    }
+    // the leaf pass (FLV_PRE) when the scene's table of pre-resolved leaves holds its big leaves
+    // (pt_capi.hip shape_view: option leaf_pre, default on) and the buffers exist
+    const int trav = select_wavefront(lo, sc.fast_rcp != 0, sc.mailbox != 0, sc.big_leaf > 0, sc.npre > 0 && sc.pre && wb.pres);
+    // sc.node_bias <= 0: chosen per instance in wf_render_t
+#define WF_ARGS sc, fp, wb, frame0, nframes, stride, accum, out, cnt, stream, ws, lo
+#define WF(T)                                                                                                        \
+    case T:                                                                                                          \
+        return lds ? (count ? wf_render_t<true, T, true>(WF_ARGS) : wf_render_t<true, T, false>(WF_ARGS))            \
+                   : (count ? wf_render_t<false, T, true>(WF_ARGS) : wf_render_t<false, T, false>(WF_ARGS));
+    switch (trav) { PT_WF_FLAVOURS(WF) }
+#undef WF_ARGS
 #undef WF
     return hipErrorInvalidValue;
 }

@@ -148,12 +148,17 @@ int pt_set_hw_queues(int n);
  *   "kernel"        auto | mega | wavefront | literal    pipeline (auto = PT_MODE_* and the scene)
  *   "trav"          nested|flat1|pred|lean|lean2|lean4|lean8|lean16|lean32   traversal flavour
  *   "lds" "fastrcp" "dual" "fuse" "fuse_gen" "bf" "mailbox" "bf_stackless" "region_perm"
- *   "leaf_walk" "leaf_pool" "leaf_skip"                                     0 | 1 switches
+ *   "leaf_walk" "leaf_pool" "leaf_skip"                                     0 | 1 switches (default 1)
  *   "parts" "sort" "node_bias" "big_leaf" "bf_slots" "wf_paths" "wf_trace_blocks" "trace_sparse"
  *   "trace_ring" "trace_watchdog" "node_steps" "regen"                      integers
- *                                       (node_steps 1..8: node steps per node turn of the lean
- *                                        traversal; regen: camera batches per region admitted by
- *                                        every extension launch of the fused kernel, 0 = off)
+ *                                       (defaults: parts 2, sort 512, node_bias 4 / 1 by kernel
+ *                                        instance (megakernel 8), big_leaf 128, bf_slots 8, wf_paths
+ *                                        64 Mi, wf_trace_blocks 0 = by occupancy, trace_sparse 4,
+ *                                        trace_ring 0 = by occupancy, trace_watchdog 2^24;
+ *                                        node_steps 1..8: node steps per node turn of the lean
+ *                                        traversal, default 4, megakernel 1; regen: camera batches
+ *                                        per region admitted by every extension launch of the
+ *                                        fused kernel, default 0 = off)
  *   "mb_uid_order"  forward | reverse   (read by pt_scene_create: uid numbering of mailbox scenes)
  *   "leaf_bvh"      integer             (read by pt_scene_create: leaves with a leaf BVH, >= this many entries)
  *   "pool_run"      2 | 4               (entries per run of the pooled leaf turns; default per scene)

@@ -2,7 +2,7 @@
 """A/B the render kernels (PT_KERNEL variants) on one workload, interleaved in one process.
 
 Usage: python scripts/perf_variants.py [--scene CornellBox] [--res 1024] [--spp 64] [--depth 8]
-       [--rounds 3] [--variants literal,regen,regen_lds]
+       [--rounds 3] [--variants literal,mega_lean_lds,auto]
 Prints one JSON line per variant: median/min kernel ms and Msamples/s.
 """
 import argparse
