@@ -73,6 +73,7 @@ constexpr OptSpec kOptSpecs[] = {
     {"lds", OPT_BOOL, nullptr},          {"fastrcp", OPT_BOOL, nullptr},     {"dual", OPT_BOOL, nullptr},
     {"fuse", OPT_BOOL, nullptr},         {"fuse_gen", OPT_BOOL, nullptr},    {"bf", OPT_BOOL, nullptr},
     {"mailbox", OPT_BOOL, nullptr},      {"bf_stackless", OPT_BOOL, nullptr}, {"trace_sparse", OPT_INT, nullptr},
+    {"bf_narrow", OPT_BOOL, nullptr},
     {"region_perm", OPT_BOOL, nullptr},  {"regen", OPT_INT, nullptr},  {"trace_ring", OPT_INT, nullptr},
     {"parts", OPT_INT, nullptr},         {"sort", OPT_INT, nullptr},
     {"node_bias", OPT_INT, nullptr},     {"node_steps", OPT_INT, nullptr},     {"big_leaf", OPT_INT, nullptr},     {"bf_slots", OPT_INT, nullptr},
@@ -162,6 +163,7 @@ struct HostLayout {
     std::vector<float4> tnorm;    // vertex-normal mode: 3 per record (SceneView::tnorm)
     std::vector<BfNode> bfnode;   // mailbox scenes with <= 64 internal nodes, <= 63 entries (SceneView::bfnode)
     std::vector<int32_t> bfmap;
+    std::vector<BfNode> bfnarrow; // ... of <= 32 internal nodes, <= 32 entries: the narrow payload (SceneView::bfnarrow)
     std::vector<LNode> lnodes;    // leaf BVHs (SceneView::lnodes), and per such leaf (first record, entries, nodes)
     std::vector<int32_t> lidx;
     std::vector<Tri> ltris;       // per chunk slot: its entry's record, lbvh = the entry's position in its leaf
@@ -354,6 +356,29 @@ int build_layout(const float* tri, size_t tri_len, const float* bvh, size_t bvh_
                     for (int c = 0; c < 3; ++c) { b.lmin[c] = nd.lmin[c]; b.lmax[c] = nd.lmax[c]; b.rmin[c] = nd.rmin[c]; b.rmax[c] = nd.rmax[c]; }
                     b.lm = nd.lcnt < 0 ? (1ull << 63) | (uint64_t)pre[(size_t)nd.lref] : (nd.lcnt > 0 ? L.lmask[(size_t)nd.lref] : 0ull);
                     b.rm = nd.rcnt < 0 ? (1ull << 63) | (uint64_t)pre[(size_t)nd.rref] : (nd.rcnt > 0 ? L.lmask[(size_t)nd.rref] : 0ull);
+                }
+                // the narrow payload (pt_layout.h): per child the uid set beneath it in the low word
+                // (children are numbered after their parents, so a backward sweep has every subtree's
+                // union ready), the inner flag and pre-order number in the high word
+                if (U <= kBfNarrowMax && L.nodes.size() <= (size_t)kBfNarrowMax) {
+                    std::vector<uint64_t> below(L.nodes.size(), 0);
+                    auto child_set = [&](int32_t ref, int32_t cnt) {
+                        return cnt < 0 ? below[(size_t)ref] : (cnt > 0 ? L.lmask[(size_t)ref] : 0ull);
+                    };
+                    for (size_t n = L.nodes.size(); n-- > 0;) {
+                        const Node& nd = L.nodes[n];
+                        below[n] = child_set(nd.lref, nd.lcnt) | child_set(nd.rref, nd.rcnt);
+                    }
+                    L.bfnarrow = L.bfnode;
+                    for (size_t i = 0; i < L.bfmap.size(); ++i) {
+                        const Node& nd = L.nodes[(size_t)L.bfmap[i]];
+                        auto word = [&](int32_t ref, int32_t cnt) {
+                            const uint64_t hi = cnt < 0 ? (uint64_t)(kBfNarrowInner | (uint32_t)pre[(size_t)ref]) : 0ull;
+                            return hi << 32 | (child_set(ref, cnt) & 0xffffffffull);
+                        };
+                        L.bfnarrow[i].lm = word(nd.lref, nd.lcnt);
+                        L.bfnarrow[i].rm = word(nd.rref, nd.rcnt);
+                    }
                 }
             }
         }
@@ -631,6 +656,8 @@ extern "C" {
 
 int pt_abi_version(void) { return PT_ABI_VERSION; }
 
+int pt_last_bf_width(void) { return pt::last_bf_width(); }
+
 int pt_profile_enable(pt_scene* s, int enable) {
     if (!s) return fail(PT_ERR_INVALID, "null scene");
     HIP_TRY(hipSetDevice(s->device));
@@ -735,7 +762,9 @@ int pt_scene_create(const float* triangle_data, size_t triangle_len, const float
     const size_t o_lmask = align_up(o_lights + L.lights.size() * sizeof(Light), 16);
     const size_t o_bfnode = align_up(o_lmask + L.lmask.size() * sizeof(uint64_t), 16);
     const size_t o_bfmap = align_up(o_bfnode + L.bfnode.size() * sizeof(BfNode), 16);
-    const size_t o_cnt = align_up(o_bfmap + L.bfmap.size() * sizeof(int32_t), 256);
+    const size_t o_bfnarrow = align_up(o_bfmap + L.bfmap.size() * sizeof(int32_t), 16);
+    const size_t span_end = o_bfnarrow + L.bfnarrow.size() * sizeof(BfNode);  // the LDS span ends here
+    const size_t o_cnt = align_up(span_end, 256);
     const size_t o_tn = align_up(o_cnt + sizeof(Counters), 256);
     const size_t o_lnode = align_up(o_tn + std::max<size_t>(1, L.tnorm.size()) * sizeof(float4), 256);
     const size_t o_lidx = align_up(o_lnode + L.lnodes.size() * sizeof(LNode), 256);
@@ -757,6 +786,7 @@ int pt_scene_create(const float* triangle_data, size_t triangle_len, const float
         up(o_lmask, L.lmask.data(), L.lmask.size() * sizeof(uint64_t)) != hipSuccess ||
         up(o_bfnode, L.bfnode.data(), L.bfnode.size() * sizeof(BfNode)) != hipSuccess ||
         up(o_bfmap, L.bfmap.data(), L.bfmap.size() * sizeof(int32_t)) != hipSuccess ||
+        up(o_bfnarrow, L.bfnarrow.data(), L.bfnarrow.size() * sizeof(BfNode)) != hipSuccess ||
         up(o_tn, L.tnorm.data(), L.tnorm.size() * sizeof(float4)) != hipSuccess ||
         up(o_lnode, L.lnodes.data(), L.lnodes.size() * sizeof(LNode)) != hipSuccess ||
         up(o_lidx, L.ltris.data(), L.ltris.size() * sizeof(Tri)) != hipSuccess ||
@@ -811,7 +841,9 @@ int pt_scene_create(const float* triangle_data, size_t triangle_len, const float
     s->view.bfmap = L.bfmap.empty() ? nullptr : reinterpret_cast<const int32_t*>(base + o_bfmap);
     s->view.off_bfnode = (uint32_t)(o_bfnode - o_nodes);
     s->view.off_bfmap = (uint32_t)(o_bfmap - o_nodes);
-    s->view.span_bytes = (uint32_t)align_up(o_bfmap + L.bfmap.size() * sizeof(int32_t) - o_nodes, 16);
+    s->view.bfnarrow = L.bfnarrow.empty() ? nullptr : reinterpret_cast<const BfNode*>(base + o_bfnarrow);
+    s->view.off_bfnarrow = (uint32_t)(o_bfnarrow - o_nodes);
+    s->view.span_bytes = (uint32_t)align_up(span_end - o_nodes, 16);
     s->d_counters = reinterpret_cast<Counters*>(base + o_cnt);
     s->info = L.info;
     s->info.device_bytes = total;
@@ -1095,6 +1127,8 @@ int shape_view(pt_scene* s, const Opts& o, const FrameParams& fp, int mode, uint
     if (o.flag("leaf_skip", 1) == 0 || (view.big_leaf > 0 && view.big_leaf < kLeafSkipMaxLeaf)) view.nalt = nullptr;
     // the brute-force replay walks the BfNode tree without a stack (bf_stackless=0: the stack walk; A/B)
     if (o.flag("bf_stackless", 1) == 0) view.bfnode = nullptr;
+    // ... and its 32-bit instance where the scene has the narrow payload (bf_narrow=0: the 64-bit one; tests)
+    if (o.flag("bf_narrow", 1) == 0 || !view.bfnode) view.bfnarrow = nullptr;
     // big leaves resolved before the traversal (k_wf_leafpass, pt_leafpass.hip; option leaf_pre=0:
     // the cooperative turns and chunk walks inside k_wf_trace): the leaves of >= big_leaf entries, at
     // most kMaxPre of them — with more, the threshold rises above the (kMaxPre + 1)-th largest and

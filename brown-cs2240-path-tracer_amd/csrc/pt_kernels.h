@@ -120,6 +120,10 @@ hipError_t launch_wavefront(const LaunchOpts& lo, const SceneView& sc, const Fra
                             uint32_t frame0, uint32_t nframes, uint32_t stride, bool accum, bool count, float* out,
                             Counters* cnt, hipStream_t stream, const WfStreams& ws);
 
+// set width (32 / 64 bits) of the stackless replay in the fused kernel launched last in this process
+// (0: none yet, or the stack walk) — pt_last_bf_width, for the tests of the narrow instance
+int last_bf_width();
+
 // Megakernel render (accum=true: frames frame0 + i*stride, i < nframes, added to out) or one
 // dispatch (accum=false: raw radiance of salt frame0 written to out).
 hipError_t launch_megakernel(const LaunchOpts& lo, const SceneView& sc, const FrameParams& fp, uint32_t frame0,

@@ -46,6 +46,14 @@ struct alignas(16) BfNode {
     uint64_t lm, rm;
 };
 static_assert(sizeof(BfNode) == 64, "bf node is 4 x 16 B");
+// Narrow payload (SceneView::bfnarrow: scenes of <= 32 distinct entries and <= 32 internal nodes):
+// the same nodes in the same order, each child's word split in two 32-bit halves —
+//   low   the set of uids beneath that child: a leaf's own set, an internal child's union over its
+//         whole subtree (what the replay's pruning asks: does this child hold a hit not yet resolved?)
+//   high  0x80000000 | pre-order number for an internal child, else 0
+// read by the 32-bit instance of the replay (pt_wavefront.hip bf_replay_stackless<.., true>).
+constexpr uint32_t kBfNarrowInner = 0x80000000u;
+constexpr int kBfNarrowMax = 32;  // entries, and internal nodes
 
 // The nine floats a triangle test reads fill the first 36 bytes so that a test loads them
 // with two ds_read_b128 + one ds_read_b32 (10 LDS cycles per wave); with v0/e1/e2 each in its
@@ -168,6 +176,10 @@ struct SceneView {
     const BfNode* bfnode;
     const int32_t* bfmap;
     uint32_t off_bfnode, off_bfmap;
+    // the BfNode tree again with the narrow payload (nullptr: the scene has more than kBfNarrowMax
+    // entries or nodes, or option bf_narrow=0), inside the LDS span at off_bfnarrow
+    const BfNode* bfnarrow;
+    uint32_t off_bfnarrow;
     // vertex-normal mode (pt_scene_set_vertex_normals; the reference's commented-out branch,
     // intersection-logic.wgsl:81-108): per record (v0n, v1n, v2n) as 3 float4, v0n.w = 1 where
     // i2 < vn_range (the branch applies); global memory, read for the winning record only

@@ -24,6 +24,7 @@
 #include "pt_path.h"
 
 #include <algorithm>
+#include <atomic>
 #include <cstdlib>
 #include <map>
 #include <mutex>
@@ -457,9 +458,76 @@ __device__ __forceinline__ bool mb_first_node(const SceneView& sc, int node, boo
     return false;
 }
 
-template <bool FAST_RCP>
-__device__ __forceinline__ int bf_replay_stackless(const SceneView& sc, const Ray& r, bool active, uint64_t hits,
+//
+// NARROW (scenes of <= 32 entries and <= 32 internal nodes: SceneView::bfnarrow, e.g. CornellBox): the
+// same walk with every set — hits, tested, pend, the leaf sets — in one 32-bit register instead of
+// a pair, and with a pruning the narrow payload allows: a child's low word is the set of entries
+// beneath it (pt_layout.h), and the walk takes a child only if that set still holds a hit of this
+// ray that no leaf has resolved yet, (low & hits & ~tested) != 0.  Exact: visiting a subtree without
+// such a hit only adds entries to `tested` that are no hits, or hits already in it, and the only
+// reader of `tested` is rh = m & ~tested & hits — so the visit changes neither best, best_t, bcur
+// nor any later rh; the nodes it would have queued lie inside that subtree, and the pending set
+// orders the others by their numbers whatever else it holds, so they are visited in the same order
+// with the same best_t at each decision.  A pruned leaf child holds neither entry of a tie the pair
+// resolves (both are unresolved hits), so mb_first_node scans to the same answer without it.  The
+// child's box test is issued only when some lane of the wave takes that child (wave vote).
+template <bool FAST_RCP, bool NARROW = false>
+__device__ __forceinline__ int bf_replay_stackless(const SceneView& sc, const Ray& r, bool active,
+                                                   std::conditional_t<NARROW, uint32_t, uint64_t> hits,
                                                    float tmin, const float* slot, int nslots, float& t_out PH_PARAM) {
+    if constexpr (NARROW) {
+        uint32_t pend = active ? 1u : 0u;  // pre-order node 0 = the root
+        uint32_t tested = 0;
+        int best = -1;
+        float best_t = -1.0f;
+        while (wave_any(pend != 0)) {
+            if (pend != 0) {
+                PH_ITER(PH_REPLAY);
+                const int n = (int)__builtin_ctz(pend);
+                pend &= pend - 1;
+                const BfNode& bn = sc.bfnarrow[n];
+                const uint32_t lset = (uint32_t)bn.lm, lhi = (uint32_t)(bn.lm >> 32);
+                const uint32_t rset = (uint32_t)bn.rm, rhi = (uint32_t)(bn.rm >> 32);
+                const uint32_t open = hits & ~tested;  // hits no leaf has resolved yet
+                const bool lneed = (lset & open) != 0, rneed = (rset & open) != 0;
+                float ld = 0.0f, rd = 0.0f;
+                if (__builtin_amdgcn_ballot_w64(lneed) != 0)  // wave-uniform
+                    ld = ray_box(r, bn.lmin[0], bn.lmin[1], bn.lmin[2], bn.lmax[0], bn.lmax[1], bn.lmax[2]);
+                if (__builtin_amdgcn_ballot_w64(rneed) != 0)
+                    rd = ray_box(r, bn.rmin[0], bn.rmin[1], bn.rmin[2], bn.rmax[0], bn.rmax[1], bn.rmax[2]);
+                const bool li = lneed & (0.0f < ld), ri = rneed & (0.0f < rd);
+                const bool lint = lhi != 0, rint = rhi != 0;
+                const uint32_t m = ((li & !lint) ? lset : 0u) | ((ri & !rint) ? rset : 0u);
+                uint32_t rh = m & open;
+                tested |= m;
+                bool bcur = false;  // the best came from this leaf pair
+                while (rh) {
+                    PH_ITER(PH_RLEAF);
+                    const int u = (int)__builtin_ctz(rh);
+                    rh &= rh - 1;
+                    const int k = __popc(hits & ((1u << u) - 1u));
+                    const int rec = sc.mb_base + u;
+                    float t;
+                    if (k < nslots) t = slot[64 * k];
+                    else tri_hit<FAST_RCP>(sc.tris, rec, r, t);  // a hit, so the same t as phase 1
+                    bool take = (best_t < 0.0f) | (t < best_t);
+                    if ((t == best_t) & bcur) take = mb_first_node(sc, sc.bfmap[n], li, ri, u, best - sc.mb_base);
+                    best_t = take ? t : best_t;
+                    best = take ? rec : best;
+                    bcur |= take;
+                }
+                if (best_t == tmin) {
+                    pend = 0;
+                } else {
+                    const bool tl = (li & lint) && !((best_t > 0.0f) & (ld > best_t));
+                    const bool tr = (ri & rint) && !((best_t > 0.0f) & (rd > best_t));
+                    pend |= (tl ? 1u << (lhi & 31u) : 0u) | (tr ? 1u << (rhi & 31u) : 0u);
+                }
+            }
+        }
+        t_out = best_t;
+        return best;
+    } else {
     constexpr uint64_t kInner = 1ull << 63;
     uint64_t pend = active ? 1ull : 0ull;  // pre-order node 0 = the root
     uint64_t tested = 0;
@@ -505,6 +573,7 @@ __device__ __forceinline__ int bf_replay_stackless(const SceneView& sc, const Ra
     }
     t_out = best_t;
     return best;
+    }  // !NARROW
 }
 
 // Camera batches (CAM: every ray of the batch starts at the camera, fp.cam — the fused kernel's GEN
@@ -526,7 +595,9 @@ __global__ void k_wf_camtab(SceneView sc, FrameParams fp, float4* camtab) {
 
 // Closest hit of the 64 rays of one batch (lane = ray; `valid` false lanes give no hit):
 // phase 1 + phase 2 above.  Returns the record (or -1) and its t in t_out.
-template <bool FAST_RCP, bool COUNT, bool CAM = false>
+// NARROW (never with COUNT; the caller's scene has SceneView::bfnarrow): the set of entries hit in 32
+// bits, and the 32-bit replay.
+template <bool FAST_RCP, bool COUNT, bool CAM = false, bool NARROW = false>
 __device__ __forceinline__ int bf_closest(const SceneView& sc, const Tri* gtris, const Ray& r, bool valid, float* slot,
                                           int nslots, const LStack32& stack, Counters& c, float& t_out,
                                           const float4* camtab PH_PARAM) {
@@ -534,7 +605,9 @@ __device__ __forceinline__ int bf_closest(const SceneView& sc, const Tri* gtris,
     // phase 1: every distinct entry against all 64 rays.  The test is tri_hit's arithmetic cut
     // after u: when no lane passes the det and u tests (the early-out chain of
     // ray-triangle-intersection.wgsl:15-24) the rest cannot make a hit and is skipped for the wave
-    uint64_t hits = 0;
+    static_assert(!(NARROW && COUNT), "the counting instances keep the 64-bit sets");
+    using Set = std::conditional_t<NARROW, uint32_t, uint64_t>;
+    Set hits = 0;
     int nh = 0;
     const uint64_t vmask = __builtin_amdgcn_ballot_w64(valid);  // loop-invariant part of phase 1's vote
     float tmin = 3.0e38f;  // smallest t of any entry this ray hits
@@ -576,7 +649,7 @@ __device__ __forceinline__ int bf_closest(const SceneView& sc, const Tri* gtris,
         if (h) {
             if (nh < nslots) slot[64 * nh] = t;
             ++nh;
-            hits |= 1ull << u;
+            hits |= (Set)1 << u;
             tmin = t < tmin ? t : tmin;  // = fminf here (t > 1e-8, never NaN) without its two canonicalising v_max
         }
     }
@@ -592,6 +665,8 @@ __device__ __forceinline__ int bf_closest(const SceneView& sc, const Tri* gtris,
         pa.v[PH_COUNT][0] = t1;
     }
 #endif
+    if constexpr (NARROW)
+        return bf_replay_stackless<FAST_RCP, true>(sc, r, valid && hits != 0, hits, tmin, slot, nslots, t_out PH_PASS);
     if constexpr (!COUNT) {
         if (sc.bfnode) {  // wave-uniform: the stackless walk (bf_replay_stackless)
             return bf_replay_stackless<FAST_RCP>(sc, r, valid && hits != 0, hits, tmin, slot, nslots, t_out PH_PASS);
@@ -689,7 +764,7 @@ struct GenArgs {
 // genk (GEN instances; wave-uniform): >= 0 makes this batch camera batch genk of the region
 // instead of queue batch b (the first launch); -1 reads the queue.
 // CAM: the batch's rays are camera rays (a fresh batch of the first launch: bf_closest's table)
-template <bool EXT, bool FAST_RCP, bool COUNT, bool GEN = false, bool CAM = GEN, class Append>
+template <bool EXT, bool FAST_RCP, bool COUNT, bool GEN = false, bool CAM = GEN, bool NARROW = false, class Append>
 __device__ __forceinline__ void bf_step_batch(const SceneView& sc, const Tri* gtris, const FrameParams& fp,
                                               const WfBuffers& wb, size_t rbase, uint32_t b, uint32_t count,
                                               const BfLds& l, int nslots, Counters& c, Append append,
@@ -748,7 +823,7 @@ __device__ __forceinline__ void bf_step_batch(const SceneView& sc, const Tri* gt
     }
 #endif
     // CAM: a camera batch (the first launch reads no queue: genk >= 0 throughout)
-    const int rec = bf_closest<FAST_RCP, COUNT, CAM>(sc, gtris, r, valid, l.slot, nslots, l.stack, c, t, wb.camtab PH_PASS);
+    const int rec = bf_closest<FAST_RCP, COUNT, CAM, NARROW>(sc, gtris, r, valid, l.slot, nslots, l.stack, c, t, wb.camtab PH_PASS);
 #if PT_PHASE_STATS
     uint64_t t3 = ph_now();
     pa.v[PH_REPLAY][0] += t3 - pa.v[PH_COUNT][0];
@@ -824,11 +899,18 @@ __device__ __forceinline__ void bf_step_batch(const SceneView& sc, const Tri* gt
 // the region's camera batches j q .. (j + 1) q - 1 behind its queued survivors, so the launches stay
 // full until the camera batches run out (the host launches 2 (ceil(max camera batches / q) +
 // max_depth) iterations).  Those launches mix queued and camera batches: no camera table.
-template <bool EXT, bool LDS, bool FAST_RCP, bool COUNT, int GEN = 0>
+// GEN | 4 (kStepNarrow): the narrow instance — 32-bit sets in phase 1 and the replay
+// (bf_replay_stackless NARROW), launched by the host for scenes with SceneView::bfnarrow.  The width
+// rides in GEN so that the kernel keeps its five template arguments (profile tools read them by
+// position).
+constexpr int kStepNarrow = 4;
+template <bool EXT, bool LDS, bool FAST_RCP, bool COUNT, int GENW = 0>
 __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_wf_step_bf(SceneView sc, FrameParams fp, WfBuffers wb, int it,
                                                            Counters* cnt_out, int nslots, uint32_t frame0,
                                                            uint32_t stride, uint32_t fbase, uint32_t P, bool raw_salt,
                                                            uint32_t q) {
+    constexpr int GEN = GENW & 3;
+    constexpr bool NARROW = (GENW & kStepNarrow) != 0;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const BfLds l = bf_lds(smem, sc);
     const uint32_t nwaves = gridDim.x * (blockDim.x / 64);
@@ -866,7 +948,7 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(8, 
     PhaseAcc pa{};
 #endif
     for (uint32_t b = g; b < nb; b += G)  // this region's batches, interleaved over its waves
-        bf_step_batch<EXT, FAST_RCP, COUNT, GEN != 0, GEN == 1>(sc, gtris, fp, wb, (size_t)rg * wb.rstride, b, count, l,
+        bf_step_batch<EXT, FAST_RCP, COUNT, GEN != 0, GEN == 1, NARROW>(sc, gtris, fp, wb, (size_t)rg * wb.rstride, b, count, l,
                                                                 nslots, c, [&](uint32_t n) { return atomicAdd(out_count, n); },
                                                                 ga, b < nqb ? (int64_t)-1 : (int64_t)(k0 + b - nqb) PH_PASS);
     if (COUNT) flush_counters(c, cnt_out);
@@ -1096,6 +1178,9 @@ static WfBuffers wb_part(const WfBuffers& wb, int h, int nparts, size_t rad_off)
     return v;
 }
 
+static std::atomic<int> g_bf_width{0};
+int last_bf_width() { return g_bf_width.load(); }
+
 // The brute-force kernels without counters replay without a stack when the scene has the BfNode
 // tree (bf_replay_stackless): no per-lane stack in their LDS (CornellBox: 14 KB of a 512-thread
 // block's 43 KB, so 4 blocks fit a CU's 160 KB instead of 3 — 8 waves per SIMD instead of 6).
@@ -1150,6 +1235,10 @@ static hipError_t wf_render_t(const SceneView& sc_in, const FrameParams& fp, con
     // option bf_slots < kBfSlots: tests of the recompute path
     const int bf_slots = std::min(kBfSlots, lo.bf_slots);
     const int sort_bins = lo.sort > 0 ? (lo.sort >= 512 ? 512 : lo.sort >= 64 ? 64 : 8) : 0;
+    // the fused kernel's narrow instance (kStepNarrow): uncounted, scene in LDS, and the scene has the
+    // narrow payload (pt_capi.hip: <= 32 entries and nodes, stackless replay and bf_narrow on)
+    constexpr bool kNarrowOk = flv_fused(TRAV) && LDS && !COUNT;
+    const bool narrow = kNarrowOk && sc.bfnode && sc.bfnarrow;
     if constexpr (flv_fused(TRAV)) {  // the camera batches' table (k_wf_camtab), before every part's GEN launch
         if (lo.fuse_gen) {
             if (sc.n_tris - sc.mb_base > 64) return hipErrorInvalidValue;  // mailbox scenes: <= 64 entries
@@ -1230,13 +1319,24 @@ static hipError_t wf_render_t(const SceneView& sc_in, const FrameParams& fp, con
             const WfBuffers& w = pv[h].w;
             const int sblocks = (int)((pv[h].P + kShadeBlock - 1) / kShadeBlock);
             if constexpr (flv_fused(TRAV)) {  // trace + shade in one launch
-#define PT_STEP(E, G) PT_LAUNCH(KID_WF_STEP, st, (k_wf_step_bf<E, LDS, flv_fast(TRAV), COUNT, G>), dim3(tblocks), dim3(kTraceBlock), \
-                                lds, st, sc, fp, w, it, cnt, bf_slots, frame0, stride, pv[h].fbase, pv[h].P, !accum, regen_q)
+#define PT_STEP_(E, G) PT_LAUNCH(KID_WF_STEP, st, (k_wf_step_bf<E, LDS, flv_fast(TRAV), COUNT, G>), dim3(tblocks), dim3(kTraceBlock), \
+                                 lds, st, sc, fp, w, it, cnt, bf_slots, frame0, stride, pv[h].fbase, pv[h].P, !accum, regen_q)
+#define PT_STEP(E, G)                                                    \
+    do {                                                                 \
+        bool narrow_ = false;                                            \
+        if constexpr (kNarrowOk && (G) != 2) narrow_ = narrow;           \
+        if constexpr (kNarrowOk && (G) != 2) {                           \
+            if (narrow_) PT_STEP_(E, (G) | kStepNarrow);                 \
+        }                                                                \
+        if (!narrow_) PT_STEP_(E, G);                                    \
+        g_bf_width = narrow_ ? 32 : (!COUNT && sc.bfnode) ? 64 : 0;      \
+    } while (0)
                 if (regen_q > 0 && (it & 1) == 0 && (uint32_t)(it / 2) * regen_q < regen_cam) PT_STEP(true, 2);
                 else if (fgen && it == 0) PT_STEP(true, 1);
                 else if ((it & 1) == 0) PT_STEP(true, 0);
                 else PT_STEP(false, 0);
 #undef PT_STEP
+#undef PT_STEP_
                 return hipSuccess;
             } else if constexpr (flv_brute_force(TRAV)) {
                 PT_LAUNCH(KID_WF_TRACE, st, (k_wf_trace_bf<LDS, flv_fast(TRAV), COUNT>), dim3(tblocks),

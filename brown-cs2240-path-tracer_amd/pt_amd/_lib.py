@@ -179,6 +179,15 @@ def reset_options() -> None:
     load_library().pt_reset_options()
 
 
+def last_bf_width() -> int:
+    """pt_last_bf_width: set width of the stackless replay in the fused step kernel launched last in
+    this process — 32 (the narrow instance: scenes of <= 32 entries and nodes, option bf_narrow), 64,
+    or 0 (none yet, the counting instances, the stack walk)."""
+    f = load_library().pt_last_bf_width
+    f.restype = ctypes.c_int
+    return int(f())
+
+
 class options:
     """Context manager: `with pt_amd.options(kernel="wavefront", trav="lean16"): ...` sets the
     options for the block and restores the previous values after it."""

@@ -159,6 +159,9 @@ int pt_set_hw_queues(int n);
  *                                        traversal, default 4, megakernel 1; regen: camera batches
  *                                        per region admitted by every extension launch of the
  *                                        fused kernel, default 0 = off)
+ *   "bf_narrow"     0 | 1               (default 1: scenes of <= 32 distinct entries and <= 32 internal
+ *                                        nodes run the fused kernel's 32-bit instance — narrow sets and
+ *                                        the replay's subtree pruning; 0 keeps the 64-bit one: tests)
  *   "mb_uid_order"  forward | reverse   (read by pt_scene_create: uid numbering of mailbox scenes)
  *   "leaf_bvh"      integer             (read by pt_scene_create: leaves with a leaf BVH, >= this many entries)
  *   "pool_run"      2 | 4               (entries per run of the pooled leaf turns; default per scene)
@@ -172,6 +175,10 @@ int pt_set_hw_queues(int n);
 int pt_set_option(const char* name, const char* value);
 int pt_get_option(const char* name, char* buf, size_t cap);
 void pt_reset_options(void);
+
+/* Which instance of the fused step kernel this process launched last: 32 (option bf_narrow), 64, or
+ * 0 (none yet, a counting instance, or the stack walk of bf_stackless=0).  For tests. */
+int pt_last_bf_width(void);
 
 /* Destroys the RCCL communicators pt_render_multi made (they are cached per device list; the
  * library also destroys them when the process exits).  Not concurrent with pt_render_multi. */
