@@ -890,7 +890,10 @@ namespace {
 
 // meta (program-raymarch.ts:79-92) -> FrameParams.  view_half_h uses the pinned tan
 // (program-raymarch.wgsl:62); it is uniform, so it is evaluated once here.
-int make_params(const float* meta, int max_depth, FrameParams& fp) {
+// win: the window of the image the call renders (NULL: the whole image); row_pitch: pixels between
+// rows of its destination (NULL: the window's width, a dense [h][w][3] buffer).
+int make_params(const float* meta, int max_depth, FrameParams& fp, const pt_window* win = nullptr,
+                const size_t* pitch = nullptr) {
     if (!meta) return fail(PT_ERR_INVALID, "meta is NULL");
     const float W = meta[0], H = meta[1];
     if (!(W >= 1.0f && H >= 1.0f && W <= 32768.0f && H <= 32768.0f) || W != std::floor(W) || H != std::floor(H))
@@ -908,6 +911,16 @@ int make_params(const float* meta, int max_depth, FrameParams& fp) {
     fp.width = (uint32_t)W; fp.height = (uint32_t)H;
     fp.direct_only = meta[46] > 0.0f ? 1 : 0;
     fp.max_depth = max_depth < 0 ? 16 : max_depth;
+    const pt_window whole = {0, 0, fp.width, fp.height};
+    const pt_window& w = win ? *win : whole;
+    if (w.w < 1 || w.h < 1) return fail(PT_ERR_INVALID, "window: w and h must be at least 1");
+    if ((uint64_t)w.x0 + w.w > fp.width || (uint64_t)w.y0 + w.h > fp.height)
+        return fail(PT_ERR_INVALID, "window: x0 + w and y0 + h must lie within the image (meta[0..1])");
+    const size_t row_pitch = pitch ? *pitch : w.w;
+    if (row_pitch < w.w) return fail(PT_ERR_INVALID, "row_pitch is smaller than the window's width");
+    if (row_pitch > 0xffffffffull) return fail(PT_ERR_INVALID, "row_pitch out of range");
+    fp.win_x0 = w.x0; fp.win_y0 = w.y0; fp.win_w = w.w; fp.win_h = w.h;
+    fp.row_pitch = (uint32_t)row_pitch;
     return PT_OK;
 }
 
@@ -1203,10 +1216,12 @@ int shape_view(pt_scene* s, const Opts& o, const FrameParams& fp, int mode, uint
     return PT_OK;
 }
 
+// d_out: the window's first pixel, rows row_pitch pixels apart (win NULL: the whole image)
 int render_impl(pt_scene* s, const float* meta, uint32_t frame0, uint32_t nframes, uint32_t stride, int max_depth,
-                int mode, bool accum, float* d_out, Counters* d_cnt, hipStream_t stream) {
+                int mode, bool accum, float* d_out, Counters* d_cnt, hipStream_t stream, const pt_window* win = nullptr,
+                const size_t* pitch = nullptr) {
     FrameParams fp{};
-    int rc = make_params(meta, max_depth, fp);
+    int rc = make_params(meta, max_depth, fp, win, pitch);
     if (rc != PT_OK) return rc;
     if (mode != PT_MODE_AUTO && mode != PT_MODE_MEGAKERNEL && mode != PT_MODE_WAVEFRONT)
         return fail(PT_ERR_INVALID, "unknown mode");
@@ -1214,7 +1229,7 @@ int render_impl(pt_scene* s, const float* meta, uint32_t frame0, uint32_t nframe
         return fail(PT_ERR_INVALID, "frame index >= 2^24 (t_k = u32(f32(k)) would round)");
     HIP_TRY(hipSetDevice(s->device));
     if (nframes == 0) return PT_OK;
-    const uint64_t npix = (uint64_t)fp.width * fp.height;
+    const uint64_t npix = (uint64_t)fp.win_w * fp.win_h;  // paths per frame: the window's
     struct ProfScope {  // attach the scene's profiler to this thread for the launches below
         explicit ProfScope(KernelProfiler* p) { t_prof = p; }
         ~ProfScope() { t_prof = nullptr; }
@@ -1276,6 +1291,14 @@ int ensure_accum(pt_scene* s, size_t n) {
 
 extern "C" {
 
+int pt_render_window_async(pt_scene* s, const float meta[48], const pt_window* win, uint32_t frame0, uint32_t nframes,
+                           uint32_t frame_stride, int max_depth, int mode, float* d_accum, size_t row_pitch,
+                           pt_counters* d_counters, void* stream) {
+    if (!s || !d_accum || !meta) return fail(PT_ERR_INVALID, "null argument");
+    return render_impl(s, meta, frame0, nframes, frame_stride, max_depth, mode, true, d_accum,
+                       reinterpret_cast<Counters*>(d_counters), static_cast<hipStream_t>(stream), win, &row_pitch);
+}
+
 int pt_render_async(pt_scene* s, const float meta[48], uint32_t frame0, uint32_t nframes, uint32_t frame_stride,
                     int max_depth, int mode, float* d_accum, pt_counters* d_counters, void* stream) {
     if (!s || !d_accum) return fail(PT_ERR_INVALID, "null argument");
@@ -1306,17 +1329,22 @@ static int blocking_stream(pt_scene* s) {
 
 int pt_render(pt_scene* s, const float meta[48], uint32_t frame0, uint32_t nframes, uint32_t frame_stride,
               int max_depth, int mode, float* accum, pt_counters* counters) {
+    return pt_render_window(s, meta, nullptr, frame0, nframes, frame_stride, max_depth, mode, accum, counters);
+}
+
+int pt_render_window(pt_scene* s, const float meta[48], const pt_window* win, uint32_t frame0, uint32_t nframes,
+                     uint32_t frame_stride, int max_depth, int mode, float* accum, pt_counters* counters) {
     if (!s || !accum || !meta) return fail(PT_ERR_INVALID, "null argument");
     FrameParams fp{};
-    int rc = make_params(meta, max_depth, fp);
+    int rc = make_params(meta, max_depth, fp, win);
     if (rc != PT_OK) return rc;
-    const size_t n = (size_t)fp.width * fp.height * 3;
+    const size_t n = (size_t)fp.win_w * fp.win_h * 3;
     HIP_TRY(hipSetDevice(s->device));
     if ((rc = ensure_accum(s, n)) != PT_OK || (rc = blocking_stream(s)) != PT_OK) return rc;
     HIP_TRY(hipMemcpyAsync(s->d_accum, accum, n * sizeof(float), hipMemcpyHostToDevice, s->stream));
     if (counters) HIP_TRY(hipMemsetAsync(s->d_counters, 0, sizeof(Counters), s->stream));
     rc = render_impl(s, meta, frame0, nframes, frame_stride, max_depth, mode, true, s->d_accum,
-                     counters ? s->d_counters : nullptr, s->stream);
+                     counters ? s->d_counters : nullptr, s->stream, win);
     if (rc != PT_OK) return rc;
     HIP_TRY(hipMemcpyAsync(accum, s->d_accum, n * sizeof(float), hipMemcpyDeviceToHost, s->stream));
     if (counters) HIP_TRY(hipMemcpyAsync(counters, s->d_counters, sizeof(Counters), hipMemcpyDeviceToHost, s->stream));
@@ -1331,14 +1359,18 @@ int pt_frame_async(pt_scene* s, const float meta[48], uint32_t t, int max_depth,
 }
 
 int pt_frame(pt_scene* s, const float meta[48], uint32_t t, int max_depth, float* radiance) {
+    return pt_frame_window(s, meta, nullptr, t, max_depth, radiance);
+}
+
+int pt_frame_window(pt_scene* s, const float meta[48], const pt_window* win, uint32_t t, int max_depth, float* radiance) {
     if (!s || !radiance || !meta) return fail(PT_ERR_INVALID, "null argument");
     FrameParams fp{};
-    int rc = make_params(meta, max_depth, fp);
+    int rc = make_params(meta, max_depth, fp, win);
     if (rc != PT_OK) return rc;
-    const size_t n = (size_t)fp.width * fp.height * 3;
+    const size_t n = (size_t)fp.win_w * fp.win_h * 3;
     HIP_TRY(hipSetDevice(s->device));
     if ((rc = ensure_accum(s, n)) != PT_OK || (rc = blocking_stream(s)) != PT_OK) return rc;
-    rc = render_impl(s, meta, t, 1, 1, max_depth, PT_MODE_AUTO, false, s->d_accum, nullptr, s->stream);
+    rc = render_impl(s, meta, t, 1, 1, max_depth, PT_MODE_AUTO, false, s->d_accum, nullptr, s->stream, win);
     if (rc != PT_OK) return rc;
     HIP_TRY(hipMemcpyAsync(radiance, s->d_accum, n * sizeof(float), hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));

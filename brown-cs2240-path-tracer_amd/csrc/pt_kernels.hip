@@ -59,10 +59,18 @@ __device__ f3 radiance(const SceneView& sc, const FrameParams& fp, Ray ray, uint
     return L;
 }
 
-__device__ __forceinline__ void pixel_of(uint32_t& x, uint32_t& y) {
+// The lane's pixel: the 16x16 grid covers the call's window, (x, y) are the pixel's coordinates in
+// the IMAGE (what camera_ray takes) and the result is its place in the destination (window-relative,
+// rows row_pitch pixels apart); false outside the window (x = y = 0 then, the result 0).
+__device__ __forceinline__ bool pixel_of(const FrameParams& fp, uint32_t& x, uint32_t& y, size_t& o) {
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    x = blockIdx.x * 16 + (w & 1) * 8 + (lane & 7);
-    y = blockIdx.y * 16 + (w >> 1) * 8 + (lane >> 3);
+    const uint32_t i = blockIdx.x * 16 + (w & 1) * 8 + (lane & 7);
+    const uint32_t j = blockIdx.y * 16 + (w >> 1) * 8 + (lane >> 3);
+    const bool valid = i < fp.win_w && j < fp.win_h;
+    x = valid ? fp.win_x0 + i : 0;
+    y = valid ? fp.win_y0 + j : 0;
+    o = valid ? 3 * ((size_t)j * fp.row_pitch + i) : 0;
+    return valid;
 }
 
 template <bool ACCUM, bool COUNT>
@@ -71,10 +79,11 @@ __global__ __launch_bounds__(kMegaBlock) void k_mega(SceneView sc, FrameParams f
     __shared__ int32_t s_stack[kStackMax * kMegaBlock];
     const LStack32 stack = LStack32::make(reinterpret_cast<char*>(s_stack), kMegaBlock);
     uint32_t x, y;
-    pixel_of(x, y);
+    size_t oi;
+    const bool valid = pixel_of(fp, x, y, oi);
     Counters c = {};
-    if (x < fp.width && y < fp.height) {
-        float* o = out + 3 * ((size_t)y * fp.width + x);
+    if (valid) {
+        float* o = out + oi;
         f3 acc = ACCUM ? mk(o[0], o[1], o[2]) : mk(0.0f, 0.0f, 0.0f);
         for (uint32_t i = 0; i < nframes; ++i) {
             uint32_t t = ACCUM ? (uint32_t)(float)(frame0 + i * stride) : frame0;
@@ -99,10 +108,10 @@ __global__ __launch_bounds__(kMegaBlock) void k_regen(SceneView sc, FrameParams 
     const LStack32 stack = LStack32::make(smem, kMegaBlock);  // [max_stack][256] int32, lane-minor
     if (LDS) stage_scene_lds(sc, smem + (uint32_t)sc.max_stack * kMegaBlock * 4u);
     uint32_t x, y;
-    pixel_of(x, y);
+    size_t oi;
+    const bool valid = pixel_of(fp, x, y, oi);
     Counters c = {};
-    const bool valid = x < fp.width && y < fp.height;
-    float* o = out + 3 * ((size_t)(valid ? y : 0) * fp.width + (valid ? x : 0));
+    float* o = out + oi;
     f3 acc = (ACCUM && valid) ? mk(o[0], o[1], o[2]) : mk(0.0f, 0.0f, 0.0f);
 
     enum { kIdle = 0, kExt = 1, kShadow = 2 };
@@ -379,7 +388,7 @@ bool scene_fits_lds(const SceneView& sc) {
 template <bool LDS, int TRAV, bool ACCUM, bool COUNT>
 static void launch_regen_t(const SceneView& sc, const FrameParams& fp, uint32_t frame0, uint32_t nframes, uint32_t stride,
                            float* out, Counters* cnt, hipStream_t stream) {
-    dim3 grid((fp.width + 15) / 16, (fp.height + 15) / 16), block(kMegaBlock);
+    dim3 grid((fp.win_w + 15) / 16, (fp.win_h + 15) / 16), block(kMegaBlock);
     size_t lds = (size_t)sc.max_stack * kMegaBlock * 4 + (LDS ? sc.span_bytes : 0);
     PT_LAUNCH(KID_REGEN, stream, (k_regen<LDS, TRAV, ACCUM, COUNT>), grid, block, lds, stream, sc, fp, frame0, nframes, stride, out,
                        cnt);
@@ -409,7 +418,7 @@ hipError_t launch_megakernel(const LaunchOpts& lo, const SceneView& scene, const
     if (sc.node_steps <= 0) sc.node_steps = 1;
     if (!accum) { nframes = 1; stride = 1; }
     if (lo.literal) {
-        dim3 grid((fp.width + 15) / 16, (fp.height + 15) / 16), block(kMegaBlock);
+        dim3 grid((fp.win_w + 15) / 16, (fp.win_h + 15) / 16), block(kMegaBlock);
 #define LIT(A, C) PT_LAUNCH(KID_MEGA, stream, (k_mega<A, C>), grid, block, 0, stream, sc, fp, frame0, nframes, stride, out, cnt)
         if (accum) { if (count) LIT(true, true); else LIT(true, false); }
         else { if (count) LIT(false, true); else LIT(false, false); }

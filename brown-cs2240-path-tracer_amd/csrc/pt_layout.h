@@ -237,6 +237,12 @@ struct FrameParams {
     uint32_t width, height;  // u32(meta[0]), u32(meta[1])
     int32_t direct_only;  // meta[46] > 0
     int32_t max_depth;    // literal 16 in `while(depth <= 16)`, program-raymarch.wgsl:118
+    // The window of the image a call renders (pt_render_window; the whole image: 0, 0, width,
+    // height).  Everything above stays the IMAGE's, so camera_ray gives a pixel the same ray, jitter
+    // and seed whatever window it is rendered in.  Window pixel (i, j) is image pixel
+    // (win_x0 + i, win_y0 + j) and is stored at out + 3 * (j * row_pitch + i)
+    uint32_t win_x0, win_y0, win_w, win_h;
+    uint32_t row_pitch;   // pixels between rows of the destination, >= win_w
 };
 
 }  // namespace pt

@@ -147,14 +147,17 @@ __device__ __forceinline__ Ray unpack_shadow_ray(float4 a, float4 h, float4 n, u
 }
 
 // The camera path made for queue slot s (the s-th path of a batch part in generation order): its
-// frame f, pixel (x, y) and path id p = f * npix + y * W + x — row-major within its frame, the
-// radiance index k_wf_accum reads; slot = path id.
+// frame f, pixel (x, y) of the IMAGE and path id p = f * npix + j * win_w + i over the call's window
+// (npix = win_w * win_h, (i, j) = (x - win_x0, y - win_y0)) — row-major within its frame's window,
+// the radiance index k_wf_accum reads; slot = path id.  This and pixel_of (pt_kernels.hip) are the
+// only places that tie a launch slot to a pixel.
 __device__ __forceinline__ uint32_t slot_path(uint32_t s, const FrameParams& fp, uint32_t& x, uint32_t& y, uint32_t& f) {
-    const uint32_t W = fp.width, npix = W * fp.height;
+    const uint32_t W = fp.win_w, npix = W * fp.win_h;
     f = s / npix;
     const uint32_t q = s - f * npix;
-    y = q / W;
-    x = q - y * W;
+    const uint32_t j = q / W;
+    y = j + fp.win_y0;
+    x = q - j * W + fp.win_x0;
     return s;
 }
 
@@ -1082,12 +1085,14 @@ __global__ __launch_bounds__(kShadeBlock) void k_wf_shade(SceneView sc, FramePar
     if (COUNT) flush_counters(c, cnt_out);
 }
 
-// acc += clamp(radiance) for the batch's frames in order (program-raymarch.ts:283-285)
+// acc += clamp(radiance) for the batch's frames in order (program-raymarch.ts:283-285); window
+// pixel pix = j * win_w + i lives at acc + 3 * (j * row_pitch + i)
 __global__ __launch_bounds__(256) void k_wf_accum(const float* __restrict__ rad, float* __restrict__ acc, uint32_t npix,
-                                                  uint32_t F, bool accumulate) {
+                                                  uint32_t win_w, uint32_t row_pitch, uint32_t F, bool accumulate) {
     const uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x;
     if (pix >= npix) return;
-    float* o = acc + 3 * (size_t)pix;
+    const uint32_t j = pix / win_w;
+    float* o = acc + 3 * ((size_t)j * row_pitch + (pix - j * win_w));
     f3 a = accumulate ? mk(o[0], o[1], o[2]) : mk(0.0f, 0.0f, 0.0f);
     for (uint32_t f = 0; f < F; ++f) {
         const float* r = rad + 3 * ((size_t)f * npix + pix);
@@ -1196,7 +1201,7 @@ static hipError_t wf_render_t(const SceneView& sc_in, const FrameParams& fp, con
                               uint32_t nframes, uint32_t stride, bool accum, float* out, Counters* cnt,
                               hipStream_t stream, const WfStreams& ws, const LaunchOpts& lo) {
     SceneView sc = bf_view<TRAV, COUNT>(sc_in);
-    const uint32_t npix = fp.width * fp.height;
+    const uint32_t npix = fp.win_w * fp.win_h;  // paths per frame: the window's
     // the batch in lo.parts parts on as many streams when a part holds at least a frame: one
     // part's kernel fills the others' launch tails and boundaries (and, with separate trace and
     // shade kernels, a VALU-bound trace runs beside an HBM-bound shade)
@@ -1383,8 +1388,8 @@ static hipError_t wf_render_t(const SceneView& sc_in, const FrameParams& fp, con
                 HIP_RETURN_IF(hipStreamWaitEvent(stream, ws.join[h], 0));
             }
         }
-        PT_LAUNCH(KID_WF_ACCUM, stream, k_wf_accum, dim3((npix + 255) / 256), dim3(256), 0, stream, wb.rad, out, npix, Fb,
-                  accum);
+        PT_LAUNCH(KID_WF_ACCUM, stream, k_wf_accum, dim3((npix + 255) / 256), dim3(256), 0, stream, wb.rad, out, npix, fp.win_w,
+                  fp.row_pitch, Fb, accum);
     }
     return hipGetLastError();
 }

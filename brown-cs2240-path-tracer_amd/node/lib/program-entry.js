@@ -29,13 +29,25 @@ function make_meta(screenDimension, camera_data, scene_description, time_elapsed
     ]);
 }
 
+/** [x0, y0, w, h] as four non-negative integers (w, h >= 1), else an Error; null/undefined: none */
+function check_window(window) {
+    if (window === undefined || window === null) return null;
+    if (!Array.isArray(window) || window.length !== 4 || !window.every((v) => Number.isInteger(v) && v >= 0 && v <= 0xffffffff) ||
+        window[2] < 1 || window[3] < 1)
+        throw Error(`window must be [x0, y0, w, h] (non-negative integers, w and h at least 1), not ${JSON.stringify(window)}`);
+    return window.slice();
+}
+
 /**
  * programEntry(screenDimension, primitive_data, camera_data, scene_description, options?)
  *   -> Promise<{accum: Float32Array(W*H*3), sample_runs, rgba: Uint8ClampedArray(W*H*4), counters, scene_info}>
  * options: {device=0, devices=[...] (several GPUs: pt_render_multi), maxDepth=16, mode='auto', frame0=0, chunk=spp,
  *           onFrames(done, total), imageOnly=false,
  *           vertexNormals=false (the reference's commented-out smooth-normal branch; changes results),
- *           counters=false (work counters: the kernels' counting builds, slower; counters is null without)}
+ *           counters=false (work counters: the kernels' counting builds, slower; counters is null without),
+ *           window=[x0, y0, w, h] (render that rectangle of the image only: accum is w*h*3 and rgba w*h*4, the
+ *           crop of the windowless result — every pixel's samples and its tone map are the full image's; not
+ *           with imageOnly or several devices)}
  * imageOnly: render and tone-map on the device in one call and return only {rgba, counters, ...}
  * (no accumulator crosses PCIe; pt_render_image).
  * As in the reference only primitive_data[0] is rendered (program-raymarch.wgsl:31,33).
@@ -47,6 +59,8 @@ async function programEntry(screenDimension, primitive_data, camera_data, scene_
     const meta = make_meta(screenDimension, camera_data, scene_description, 0);
     const mode = typeof o.mode === 'number' ? o.mode : MODE[o.mode];
     if (mode === undefined) throw Error(`unknown mode ${o.mode}`);
+    const win = check_window(o.window);
+    if (win && (o.imageOnly || (o.devices && o.devices.length > 1))) throw Error('window: not with imageOnly or several devices');
     if (o.devices && o.devices.length > 1) return programEntryMulti(pt, meta, W, H, primitive_data, scene_description, o, mode);
     const scene = pt.sceneCreate(primitive_data[0].triangle_data, primitive_data[0].bvh_data,
                                  o.devices && o.devices.length ? o.devices[0] : o.device);
@@ -63,17 +77,19 @@ async function programEntry(screenDimension, primitive_data, camera_data, scene_
                                            !!o.counters);
             return { accum: null, sample_runs: spp, rgba, counters: c, scene_info };
         }
-        const accum = new Float32Array(W * H * 3);
+        const npix = win ? win[2] * win[3] : W * H;
+        const accum = new Float32Array(npix * 3);
         const counters = { samples: 0, ext_queries: 0, shadow_queries: 0, nodes: 0, tri_tests: 0, box_tests: 0 };
         for (let done = 0; done < spp; done += chunk) {
             const n = Math.min(chunk, spp - done);
-            const c = await pt.render(scene, meta, o.frame0 + done, n, 1, o.maxDepth, mode, accum, !!o.counters);
+            const c = win ? await pt.renderWindow(scene, meta, win, o.frame0 + done, n, 1, o.maxDepth, mode, accum, !!o.counters)
+                          : await pt.render(scene, meta, o.frame0 + done, n, 1, o.maxDepth, mode, accum, !!o.counters);
             if (c) for (const k of Object.keys(counters)) counters[k] += c[k];
             if (o.onFrames) o.onFrames(done + n, spp);
         }
-        const rgba = new Uint8ClampedArray(W * H * 4);
+        const rgba = new Uint8ClampedArray(npix * 4);
         pt.tonemap(accum, spp, rgba);
-        return { accum, sample_runs: spp, rgba, counters: o.counters ? counters : null, scene_info };
+        return { accum, sample_runs: spp, rgba, counters: o.counters ? counters : null, scene_info, window: win };
     } finally {
         pt.sceneDestroy(scene);
     }
@@ -99,4 +115,4 @@ async function programEntryMulti(pt, meta, W, H, primitive_data, scene_descripti
     }
 }
 
-module.exports = { programEntry, make_meta, MODE };
+module.exports = { programEntry, make_meta, check_window, MODE };

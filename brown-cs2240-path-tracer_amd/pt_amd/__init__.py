@@ -19,6 +19,7 @@ from ._lib import (  # noqa: F401
     PtError,
     Scene,
     SceneInfo,
+    Window,
     abi_version,
     build_id,
     bvh_build,
@@ -29,6 +30,7 @@ from ._lib import (  # noqa: F401
     options,
     release_communicators,
     render_multi,
+    render_tiled,
     reset_options,
     selftest_math,
     selftest_rcp,

@@ -46,6 +46,39 @@ class SceneInfo(ctypes.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+class Window(ctypes.Structure):
+    """pt_window: pixels [x0, x0 + w) x [y0, y0 + h) of the image."""
+    _fields_ = [(n, ctypes.c_uint32) for n in ("x0", "y0", "w", "h")]
+
+
+def _uint(v, what: str, lo: int = 0) -> int:
+    """v as an integer in [lo, 2^32), else PtError(-1): the argument checks of the window calls."""
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+        raise PtError(-1, f"{what} must be an integer, not {v!r}")
+    if not lo <= int(v) <= 0xFFFFFFFF:
+        raise PtError(-1, f"{what} must lie in [{lo}, 2^32), not {v!r}")
+    return int(v)
+
+
+def _window(window):
+    """A (x0, y0, w, h) window checked on the host (four non-negative integers; the library checks
+    it against the image) as a pt_window, or None for the whole image."""
+    if window is None:
+        return None
+    try:
+        t = tuple(window)
+    except TypeError:
+        raise PtError(-1, f"window must be (x0, y0, w, h), not {window!r}") from None
+    if len(t) != 4:
+        raise PtError(-1, f"window must have four values (x0, y0, w, h), not {len(t)}")
+    return Window(*[_uint(v, f"window {n}") for v, n in zip(t, ("x0", "y0", "w", "h"))])
+
+
+def _extent(meta, win):
+    """(w, h) of a call's result: the window's, or the image's of meta[0..1]."""
+    return (int(win.w), int(win.h)) if win is not None else (int(meta[0]), int(meta[1]))
+
+
 class KernelTime(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char * 32), ("launches", ctypes.c_uint64), ("total_ms", ctypes.c_double),
                 ("min_ms", ctypes.c_double), ("max_ms", ctypes.c_double), ("busy_ms", ctypes.c_double)]
@@ -111,6 +144,10 @@ def load_library():
     L.pt_render.argtypes = [p, p, u32, u32, u32, i, i, p, p]
     L.pt_render_async.argtypes = [p, p, u32, u32, u32, i, i, p, p, p]
     L.pt_frame.argtypes = [p, p, u32, i, p]
+    wp = ctypes.POINTER(Window)
+    L.pt_render_window.argtypes = [p, p, wp, u32, u32, u32, i, i, p, p]
+    L.pt_render_window_async.argtypes = [p, p, wp, u32, u32, u32, i, i, p, sz, p, p]
+    L.pt_frame_window.argtypes = [p, p, wp, u32, i, p]
     L.pt_frame_async.argtypes = [p, p, u32, i, p, p]
     L.pt_tonemap.argtypes = [p, sz, u32, p]
     L.pt_selftest_math.argtypes = [i, i, p, p, p, sz]
@@ -136,7 +173,7 @@ def load_library():
     i32p = ctypes.POINTER(ctypes.c_int32)
     L.pt_scene_leaf_bvh.argtypes = [p, i, i32p, i32p, i32p]
     L.pt_selftest_leaf.argtypes = [p, i, i, u32, u32, p]
-    for fn in ("pt_scene_leaf_bvh", "pt_selftest_leaf", "pt_selftest_valu", "pt_set_option", "pt_get_option", "pt_release_communicators", "pt_scene_check", "pt_set_hw_queues", "pt_render_multi", "pt_bvh_build_sah", "pt_bvh_build_sah2", "pt_device_count", "pt_scene_create", "pt_scene_get_info", "pt_render", "pt_render_async", "pt_frame",
+    for fn in ("pt_render_window", "pt_render_window_async", "pt_frame_window", "pt_scene_leaf_bvh", "pt_selftest_leaf", "pt_selftest_valu", "pt_set_option", "pt_get_option", "pt_release_communicators", "pt_scene_check", "pt_set_hw_queues", "pt_render_multi", "pt_bvh_build_sah", "pt_bvh_build_sah2", "pt_device_count", "pt_scene_create", "pt_scene_get_info", "pt_render", "pt_render_async", "pt_frame",
                "pt_frame_async", "pt_tonemap", "pt_selftest_math", "pt_profile_enable", "pt_profile_select", "pt_profile_read", "pt_selftest_rcp", "pt_bvh_build", "pt_tonemap_async", "pt_readback_async", "pt_render_image",
                "pt_scene_set_vertex_normals"):
         getattr(L, fn).restype = i
@@ -291,26 +328,51 @@ class Scene:
         return out
 
     def render(self, meta, frame0: int, nframes: int, stride: int = 1, max_depth: int = -1, mode: int = MODE_AUTO,
-               accum: np.ndarray | None = None, counters: bool = False):
-        """Host-buffer render (blocking). Returns accum [H, W, 3] (and counters if requested)."""
+               accum: np.ndarray | None = None, counters: bool = False, window=None):
+        """Host-buffer render (blocking). Returns accum [H, W, 3] (and counters if requested).
+        window=(x0, y0, w, h): only that rectangle of the image (pt_render_window) — accum is
+        [h, w, 3] and holds the bits of accum_full[y0:y0+h, x0:x0+w] of the whole image's render."""
         meta = _f32(meta)
-        W, H = int(meta[0]), int(meta[1])
+        win = _window(window)
+        W, H = _extent(meta, win)
         if accum is None:
             accum = np.zeros((H, W, 3), np.float32)
         if accum.dtype != np.float32 or not accum.flags.c_contiguous or accum.size != W * H * 3:
-            raise ValueError("accum must be a contiguous float32 array of H*W*3 elements")
+            raise ValueError("accum must be a contiguous float32 array of H*W*3 elements (the window's h*w*3)")
         c = Counters()
-        _check(self._lib.pt_render(self._h, _ptr(meta), frame0, nframes, stride, max_depth, mode, _ptr(accum),
-                                   ctypes.byref(c) if counters else None))
+        cp = ctypes.byref(c) if counters else None
+        if win is None:
+            _check(self._lib.pt_render(self._h, _ptr(meta), frame0, nframes, stride, max_depth, mode, _ptr(accum), cp))
+        else:
+            _check(self._lib.pt_render_window(self._h, _ptr(meta), ctypes.byref(win), frame0, nframes, stride,
+                                              max_depth, mode, _ptr(accum), cp))
         return (accum, c.as_dict()) if counters else accum
 
     def render_async(self, meta, frame0: int, nframes: int, stride: int, max_depth: int, mode: int, d_accum_ptr: int,
-                     stream_ptr: int = 0, d_counters_ptr: int = 0):
-        """Device render into a caller-owned device buffer (e.g. a torch.cuda tensor's data_ptr())."""
+                     stream_ptr: int = 0, d_counters_ptr: int = 0, window=None, row_pitch=None):
+        """Device render into a caller-owned device buffer (e.g. a torch.cuda tensor's data_ptr()).
+        window=(x0, y0, w, h): only that rectangle (pt_render_window_async); d_accum_ptr then
+        addresses the window's FIRST pixel and row_pitch is the distance between its rows in pixels
+        (default w: a dense [h, w, 3] buffer; the image's W with d_accum_ptr = image + 12 * (y0 * W
+        + x0) bytes renders the window in place inside a full [H, W, 3] image)."""
         meta = _f32(meta)
-        _check(self._lib.pt_render_async(self._h, _ptr(meta), frame0, nframes, stride, max_depth, mode,
-                                         ctypes.c_void_p(d_accum_ptr), ctypes.c_void_p(d_counters_ptr or None),
-                                         ctypes.c_void_p(stream_ptr or None)))
+        win = _window(window)
+        if win is None and row_pitch is None:
+            _check(self._lib.pt_render_async(self._h, _ptr(meta), frame0, nframes, stride, max_depth, mode,
+                                             ctypes.c_void_p(d_accum_ptr), ctypes.c_void_p(d_counters_ptr or None),
+                                             ctypes.c_void_p(stream_ptr or None)))
+            return
+        pitch = _extent(meta, win)[0] if row_pitch is None else _uint(row_pitch, "row_pitch")
+        _check(self._lib.pt_render_window_async(self._h, _ptr(meta), ctypes.byref(win) if win is not None else None,
+                                                frame0, nframes, stride, max_depth, mode, ctypes.c_void_p(d_accum_ptr),
+                                                pitch, ctypes.c_void_p(d_counters_ptr or None),
+                                                ctypes.c_void_p(stream_ptr or None)))
+
+    def render_window_async(self, meta, window, frame0: int, nframes: int, stride: int, max_depth: int, mode: int,
+                            d_accum_ptr: int, row_pitch=None, stream_ptr: int = 0, d_counters_ptr: int = 0):
+        """pt_render_window_async under its own name: render_async with a window and a row pitch."""
+        self.render_async(meta, frame0, nframes, stride, max_depth, mode, d_accum_ptr, stream_ptr, d_counters_ptr,
+                          window=window, row_pitch=row_pitch)
 
     def render_image(self, meta, frame0: int, nframes: int, stride: int = 1, max_depth: int = -1,
                      mode: int = MODE_AUTO, counters: bool = False):
@@ -359,12 +421,17 @@ class Scene:
                                     "busy_ms": k.busy_ms}
         return out
 
-    def frame(self, meta, t: int, max_depth: int = -1) -> np.ndarray:
-        """One reference dispatch: raw radiance [H, W, 3] for RNG salt t."""
+    def frame(self, meta, t: int, max_depth: int = -1, window=None) -> np.ndarray:
+        """One reference dispatch: raw radiance [H, W, 3] for RNG salt t.  window=(x0, y0, w, h):
+        that rectangle only, [h, w, 3], the same bits (pt_frame_window)."""
         meta = _f32(meta)
-        W, H = int(meta[0]), int(meta[1])
+        win = _window(window)
+        W, H = _extent(meta, win)
         out = np.zeros((H, W, 3), np.float32)
-        _check(self._lib.pt_frame(self._h, _ptr(meta), t, max_depth, _ptr(out)))
+        if win is None:
+            _check(self._lib.pt_frame(self._h, _ptr(meta), t, max_depth, _ptr(out)))
+        else:
+            _check(self._lib.pt_frame_window(self._h, _ptr(meta), ctypes.byref(win), t, max_depth, _ptr(out)))
         return out
 
 
@@ -383,6 +450,34 @@ def render_multi(scenes, meta, frame0: int, nframes: int, stride: int = 1, max_d
     _check(load_library().pt_render_multi(handles, len(scenes), _ptr(meta), frame0, nframes, stride, max_depth, mode,
                                           _ptr(accum), ctypes.byref(c) if counters else None))
     return (accum, c.as_dict()) if counters else accum
+
+
+def render_tiled(scene, meta, frame0: int, nframes: int, stride: int = 1, max_depth: int = -1,
+                 mode: int = MODE_AUTO, tile=(256, 256), counters: bool = False):
+    """The whole image rendered tile by tile: one Scene.render(window=...) per tile of tile=(tw, th)
+    pixels (the right and bottom tiles are as small as the image leaves them), pasted into a full
+    [H, W, 3] accumulator — the same bits as Scene.render of the whole image.  counters: summed over
+    the tiles (samples and the query counts equal the whole image's; the traversal counts depend on
+    which rays share a batch)."""
+    meta = _f32(meta)
+    try:
+        tw, th = tile
+    except (TypeError, ValueError):
+        raise PtError(-1, f"tile must be (tw, th), not {tile!r}") from None
+    tw, th = _uint(tw, "tile width", 1), _uint(th, "tile height", 1)
+    W, H = int(meta[0]), int(meta[1])
+    accum = np.zeros((H, W, 3), np.float32)
+    total = Counters()
+    for y0 in range(0, H, th):
+        for x0 in range(0, W, tw):
+            w, h = min(tw, W - x0), min(th, H - y0)
+            r = scene.render(meta, frame0, nframes, stride, max_depth, mode, counters=counters, window=(x0, y0, w, h))
+            if counters:
+                r, c = r
+                for n, _ in Counters._fields_:
+                    setattr(total, n, getattr(total, n) + c[n])
+            accum[y0:y0 + h, x0:x0 + w] = r
+    return (accum, total.as_dict()) if counters else accum
 
 
 def tonemap(accum, sample_runs: int) -> np.ndarray:

@@ -127,6 +127,31 @@ int pt_render(pt_scene* scene, const float meta[48], uint32_t frame0, uint32_t n
 int pt_render_async(pt_scene* scene, const float meta[48], uint32_t frame0, uint32_t nframes, uint32_t frame_stride,
                     int max_depth, int mode, float* d_accum, pt_counters* d_counters, void* stream);
 
+/* A window of the image: pixels [x0, x0 + w) x [y0, y0 + h) of the W x H image of meta[0..1]
+ * (y0 = the image's top row, as in every [H][W][3] buffer here); w, h >= 1, x0 + w <= W,
+ * y0 + h <= H, else PT_ERR_INVALID.  NULL where a window is accepted = the whole image. */
+typedef struct { uint32_t x0, y0, w, h; } pt_window;
+
+/* pt_render for the pixels of a window only: accum is host f32 [h][w][3], in/out, the window's
+ * pixels row-major.  Frame salts, seeds, rays and results are those of the full image's pixels:
+ * the window's accumulator holds the same bits as that rectangle of a pt_render of the whole
+ * image started from the same values, whatever the window, pipeline or batch shape (a pixel
+ * depends on its image coordinates only).  AUTO chooses the pipeline by the window's paths
+ * (w * h * nframes).  counters: nullable, the window's paths only.  pt_render is this with
+ * win = NULL.  Blocking. */
+int pt_render_window(pt_scene* scene, const float meta[48], const pt_window* win, uint32_t frame0, uint32_t nframes,
+                     uint32_t frame_stride, int max_depth, int mode, float* accum, pt_counters* counters);
+
+/* pt_render_async for a window: d_accum points at the window's FIRST pixel in device memory and
+ * row_pitch is the distance between its rows in pixels (>= w, else PT_ERR_INVALID).  row_pitch = w
+ * is a dense [h][w][3] buffer; row_pitch = W with d_accum = image + 3 * (y0 * W + x0) renders the
+ * window in place inside a full [H][W][3] image, of which nothing outside the window is read or
+ * written — tiles of one image may be rendered by separate calls, on separate scenes or devices.
+ * Same bits as pt_render_window.  d_counters: device pt_counters or NULL (added to). */
+int pt_render_window_async(pt_scene* scene, const float meta[48], const pt_window* win, uint32_t frame0,
+                           uint32_t nframes, uint32_t frame_stride, int max_depth, int mode, float* d_accum,
+                           size_t row_pitch, pt_counters* d_counters, void* stream);
+
 /* Completion check of the asynchronous calls: waits for every render of the scene to finish
  * (blocking) and reports a device-side failure of any of them — a wavefront traversal wave that
  * gave up after its watchdog limit leaves a flag instead of hanging, and the accumulators of
@@ -209,6 +234,11 @@ int pt_render_multi(pt_scene* const* scenes, int n, const float meta[48], uint32
  * (the resultMatrix of program-raymarch.wgsl:82-84, before host clamping). */
 int pt_frame(pt_scene* scene, const float meta[48], uint32_t t, int max_depth, float* radiance);
 int pt_frame_async(pt_scene* scene, const float meta[48], uint32_t t, int max_depth, float* d_radiance, void* stream);
+
+/* pt_frame for a window: radiance is host f32 [h][w][3], the same bits as that rectangle of
+ * pt_frame's result (the salt t and each pixel's seed are the full image's). */
+int pt_frame_window(pt_scene* scene, const float meta[48], const pt_window* win, uint32_t t, int max_depth,
+                    float* radiance);
 
 /* Display transform of program-raymarch.ts:295-316 on the host (JS double semantics):
  * raw = acc/sample_runs, lum = mean(raw), out = raw * (lum/(lum+1))^0.01, u8 = ToInt32(out*255)
