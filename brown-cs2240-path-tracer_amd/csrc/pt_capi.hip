@@ -584,6 +584,14 @@ struct pt_scene {
     KernelProfiler prof;
     uint8_t* d_rgba = nullptr;  // pt_render_image scratch
     size_t rgba_cap = 0;
+    // scratch of the blocking moments, noise and adaptive calls: second moments, per-tile mean (floats),
+    // tile verdicts followed by tile frame counts (bytes)
+    float* d_m2 = nullptr;
+    size_t m2_cap = 0;
+    float* d_mean = nullptr;
+    size_t mean_cap = 0;
+    void* d_tiles = nullptr;
+    size_t tiles_cap = 0;
     WfStreams ws;  // dual-stream wavefront: aux stream + fork/join events (created with d_wf)
     // pinned mirror of the wavefront control words, copied after every wavefront render on its
     // stream: a watchdog flag set by an asynchronous render surfaces once that copy has landed
@@ -866,6 +874,9 @@ void pt_scene_destroy(pt_scene* s) {
     if (s->d_pres) hipFree(s->d_pres);
     if (s->d_peer) hipFree(s->d_peer);
     if (s->d_rgba) hipFree(s->d_rgba);
+    if (s->d_m2) hipFree(s->d_m2);
+    if (s->d_mean) hipFree(s->d_mean);
+    if (s->d_tiles) hipFree(s->d_tiles);
     if (s->h_ctl) hipHostFree(s->h_ctl);
     if (s->d_mem) hipFree(s->d_mem);
     s->prof.destroy();
@@ -1216,10 +1227,11 @@ int shape_view(pt_scene* s, const Opts& o, const FrameParams& fp, int mode, uint
     return PT_OK;
 }
 
-// d_out: the window's first pixel, rows row_pitch pixels apart (win NULL: the whole image)
+// d_out: the window's first pixel, rows row_pitch pixels apart (win NULL: the whole image); d_m2
+// (nullable, accumulating calls): the second moments, laid out like d_out
 int render_impl(pt_scene* s, const float* meta, uint32_t frame0, uint32_t nframes, uint32_t stride, int max_depth,
                 int mode, bool accum, float* d_out, Counters* d_cnt, hipStream_t stream, const pt_window* win = nullptr,
-                const size_t* pitch = nullptr) {
+                const size_t* pitch = nullptr, float* d_m2 = nullptr) {
     FrameParams fp{};
     int rc = make_params(meta, max_depth, fp, win, pitch);
     if (rc != PT_OK) return rc;
@@ -1269,11 +1281,11 @@ int render_impl(pt_scene* s, const float* meta, uint32_t frame0, uint32_t nframe
             s->wf.pres = nullptr;
         }
         HIP_TRY(launch_wavefront(lo, view, fp, s->wf, frame0, nframes, stride, accum, d_cnt != nullptr, d_out, d_cnt,
-                                 stream, s->ws));
+                                 stream, s->ws, d_m2));
         HIP_TRY(hipMemcpyAsync(s->h_ctl, s->wf.ctl, 4 * kMaxParts * WF_CTL_WORDS, hipMemcpyDeviceToHost, stream));
         return PT_OK;
     }
-    HIP_TRY(launch_megakernel(lo, view, fp, frame0, nframes, stride, accum, d_cnt != nullptr, d_out, d_cnt, stream));
+    HIP_TRY(launch_megakernel(lo, view, fp, frame0, nframes, stride, accum, d_cnt != nullptr, d_out, d_cnt, stream, d_m2));
     return PT_OK;
 }
 
@@ -1285,6 +1297,73 @@ int ensure_accum(pt_scene* s, size_t n) {
     if (hipMalloc(&s->d_accum, n * sizeof(float)) != hipSuccess) return fail(PT_ERR_NOMEM, "hipMalloc accumulator");
     s->accum_cap = n;
     return PT_OK;
+}
+
+// a scratch buffer of at least n units (T's), grown like ensure_accum
+template <class T>
+int ensure_scratch(T*& p, size_t& cap, size_t n, const char* what) {
+    if (cap >= n) return PT_OK;
+    if (p) hipFree(p);
+    p = nullptr;
+    cap = 0;
+    if (hipMalloc(reinterpret_cast<void**>(&p), n * sizeof(T)) != hipSuccess) return fail(PT_ERR_NOMEM, std::string("hipMalloc ") + what);
+    cap = n;
+    return PT_OK;
+}
+
+static_assert(sizeof(pt_tile_noise) == 16 && sizeof(TileNoise) == 16 && offsetof(pt_tile_noise, max_err) == 8 &&
+                  offsetof(TileNoise, max_err) == 8,
+              "pt_tile_noise is 16 bytes");
+
+// the tile grid of the noise and mean calls, checked (host only)
+int make_grid(uint32_t w, uint32_t h, size_t row_pitch, uint32_t tile_w, uint32_t tile_h, TileGrid& g) {
+    if (w < 1 || h < 1 || w > 32768 || h > 32768) return fail(PT_ERR_INVALID, "tiles: w and h must lie in [1, 32768]");
+    if (row_pitch < w) return fail(PT_ERR_INVALID, "row_pitch is smaller than the buffer's width");
+    if (row_pitch > 0xffffffffull) return fail(PT_ERR_INVALID, "row_pitch out of range");
+    if (tile_w < 1 || tile_h < 1) return fail(PT_ERR_INVALID, "tiles: tile_w and tile_h must be at least 1");
+    g = TileGrid{w, h, (uint32_t)row_pitch, tile_w, tile_h, (w - 1) / tile_w + 1, (h - 1) / tile_h + 1};
+    return PT_OK;
+}
+int check_tol(double tol, double floor) {
+    if (!(std::isfinite(tol) && tol > 0.0)) return fail(PT_ERR_INVALID, "tol must be finite and > 0");
+    if (!(std::isfinite(floor) && floor > 0.0)) return fail(PT_ERR_INVALID, "floor must be finite and > 0");
+    return PT_OK;
+}
+int check_adaptive(const pt_adaptive& a) {
+    if (a.tile_w < 1 || a.tile_h < 1) return fail(PT_ERR_INVALID, "pt_adaptive: tile_w and tile_h must be at least 1");
+    if (a.min_frames < 2) return fail(PT_ERR_INVALID, "pt_adaptive: min_frames must be at least 2");
+    if (a.step_frames < 1) return fail(PT_ERR_INVALID, "pt_adaptive: step_frames must be at least 1");
+    if (a.max_frames < a.min_frames) return fail(PT_ERR_INVALID, "pt_adaptive: max_frames must be at least min_frames");
+    if (!(std::isfinite(a.tol) && a.tol > 0.0)) return fail(PT_ERR_INVALID, "pt_adaptive: tol must be finite and > 0");
+    if (!(std::isfinite(a.floor) && a.floor > 0.0)) return fail(PT_ERR_INVALID, "pt_adaptive: floor must be finite and > 0");
+    if (!(a.noisy_fraction >= 0.0 && a.noisy_fraction < 1.0))
+        return fail(PT_ERR_INVALID, "pt_adaptive: noisy_fraction must lie in [0, 1)");
+    return PT_OK;
+}
+
+// The rectangles of a mask of active tiles (pt_selftest_tile_rects): tile rows top to bottom, the
+// maximal runs of active tiles in each; a run with the columns of a rectangle that reached the row
+// above extends it, any other opens a new one.  (tx0, ty0, width, height) in tiles, in opening order.
+void tile_rects(const uint8_t* active, uint32_t tx, uint32_t ty, std::vector<std::array<uint32_t, 4>>& out) {
+    out.clear();
+    std::vector<size_t> open, next;  // rectangles whose last row is the previous / this one
+    for (uint32_t y = 0; y < ty; ++y) {
+        next.clear();
+        const uint8_t* row = active + (size_t)y * tx;
+        for (uint32_t x = 0; x < tx;) {
+            if (!row[x]) { ++x; continue; }
+            uint32_t x1 = x;
+            while (x1 < tx && row[x1]) ++x1;
+            size_t k = out.size();
+            for (size_t c : open)
+                if (out[c][0] == x && out[c][2] == x1 - x) k = c;
+            if (k == out.size()) out.push_back({x, y, x1 - x, 1u});
+            else ++out[k][3];
+            next.push_back(k);
+            x = x1;
+        }
+        open.swap(next);
+    }
 }
 
 }  // namespace
@@ -1349,6 +1428,205 @@ int pt_render_window(pt_scene* s, const float meta[48], const pt_window* win, ui
     HIP_TRY(hipMemcpyAsync(accum, s->d_accum, n * sizeof(float), hipMemcpyDeviceToHost, s->stream));
     if (counters) HIP_TRY(hipMemcpyAsync(counters, s->d_counters, sizeof(Counters), hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
+    return check_watchdog(s);
+}
+
+int pt_render_moments_async(pt_scene* s, const float meta[48], const pt_window* win, uint32_t frame0, uint32_t nframes,
+                            uint32_t frame_stride, int max_depth, int mode, float* d_accum, float* d_m2,
+                            size_t row_pitch, pt_counters* d_counters, void* stream) {
+    if (!s || !d_accum || !d_m2 || !meta) return fail(PT_ERR_INVALID, "null argument");
+    return render_impl(s, meta, frame0, nframes, frame_stride, max_depth, mode, true, d_accum,
+                       reinterpret_cast<Counters*>(d_counters), static_cast<hipStream_t>(stream), win, &row_pitch, d_m2);
+}
+
+int pt_render_moments(pt_scene* s, const float meta[48], const pt_window* win, uint32_t frame0, uint32_t nframes,
+                      uint32_t frame_stride, int max_depth, int mode, float* accum, float* m2, pt_counters* counters) {
+    if (!s || !accum || !m2 || !meta) return fail(PT_ERR_INVALID, "null argument");
+    FrameParams fp{};
+    int rc = make_params(meta, max_depth, fp, win);
+    if (rc != PT_OK) return rc;
+    const size_t n = (size_t)fp.win_w * fp.win_h * 3;
+    HIP_TRY(hipSetDevice(s->device));
+    if ((rc = ensure_accum(s, n)) != PT_OK || (rc = ensure_scratch(s->d_m2, s->m2_cap, n, "second moments")) != PT_OK ||
+        (rc = blocking_stream(s)) != PT_OK)
+        return rc;
+    HIP_TRY(hipMemcpyAsync(s->d_accum, accum, n * sizeof(float), hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipMemcpyAsync(s->d_m2, m2, n * sizeof(float), hipMemcpyHostToDevice, s->stream));
+    if (counters) HIP_TRY(hipMemsetAsync(s->d_counters, 0, sizeof(Counters), s->stream));
+    rc = render_impl(s, meta, frame0, nframes, frame_stride, max_depth, mode, true, s->d_accum,
+                     counters ? s->d_counters : nullptr, s->stream, win, nullptr, s->d_m2);
+    if (rc != PT_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(accum, s->d_accum, n * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipMemcpyAsync(m2, s->d_m2, n * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+    if (counters) HIP_TRY(hipMemcpyAsync(counters, s->d_counters, sizeof(Counters), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return check_watchdog(s);
+}
+
+int pt_noise_tiles_async(pt_scene* s, const float* d_accum, const float* d_m2, uint32_t w, uint32_t h, size_t row_pitch,
+                         uint32_t tile_w, uint32_t tile_h, const uint32_t* d_frames, double tol, double floor,
+                         pt_tile_noise* d_out, void* stream) {
+    if (!s || !d_accum || !d_m2 || !d_frames || !d_out) return fail(PT_ERR_INVALID, "null argument");
+    TileGrid g{};
+    int rc = make_grid(w, h, row_pitch, tile_w, tile_h, g);
+    if (rc != PT_OK || (rc = check_tol(tol, floor)) != PT_OK) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    struct ProfScope {
+        explicit ProfScope(KernelProfiler* p) { t_prof = p; }
+        ~ProfScope() { t_prof = nullptr; }
+    } prof_scope(s->prof_on ? &s->prof : nullptr);
+    HIP_TRY(launch_noise_tiles(d_accum, d_m2, g, d_frames, tol, floor, reinterpret_cast<TileNoise*>(d_out),
+                               static_cast<hipStream_t>(stream)));
+    return PT_OK;
+}
+
+int pt_tile_mean_async(pt_scene* s, const float* d_accum, uint32_t w, uint32_t h, size_t row_pitch, uint32_t tile_w,
+                       uint32_t tile_h, const uint32_t* d_frames, float* d_mean, void* stream) {
+    if (!s || !d_accum || !d_frames || !d_mean) return fail(PT_ERR_INVALID, "null argument");
+    TileGrid g{};
+    const int rc = make_grid(w, h, row_pitch, tile_w, tile_h, g);
+    if (rc != PT_OK) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    struct ProfScope {
+        explicit ProfScope(KernelProfiler* p) { t_prof = p; }
+        ~ProfScope() { t_prof = nullptr; }
+    } prof_scope(s->prof_on ? &s->prof : nullptr);
+    HIP_TRY(launch_tile_mean(d_accum, g, d_frames, d_mean, static_cast<hipStream_t>(stream)));
+    return PT_OK;
+}
+
+// the tile scratch of the blocking calls: T verdicts, then T frame counts
+static int ensure_tiles(pt_scene* s, size_t T, pt_tile_noise*& d_noise, uint32_t*& d_frames) {
+    char* base = static_cast<char*>(s->d_tiles);
+    const int rc = ensure_scratch(base, s->tiles_cap, T * (sizeof(pt_tile_noise) + sizeof(uint32_t)), "tiles");
+    s->d_tiles = base;
+    if (rc != PT_OK) return rc;
+    d_noise = reinterpret_cast<pt_tile_noise*>(base);
+    d_frames = reinterpret_cast<uint32_t*>(base + T * sizeof(pt_tile_noise));
+    return PT_OK;
+}
+
+int pt_noise_tiles(pt_scene* s, const float* accum, const float* m2, uint32_t w, uint32_t h, uint32_t tile_w,
+                   uint32_t tile_h, const uint32_t* frames, double tol, double floor, pt_tile_noise* out) {
+    if (!s || !accum || !m2 || !frames || !out) return fail(PT_ERR_INVALID, "null argument");
+    TileGrid g{};
+    int rc = make_grid(w, h, w, tile_w, tile_h, g);
+    if (rc != PT_OK || (rc = check_tol(tol, floor)) != PT_OK) return rc;
+    const size_t n = (size_t)w * h * 3, T = (size_t)g.tx * g.ty;
+    HIP_TRY(hipSetDevice(s->device));
+    pt_tile_noise* d_noise = nullptr;
+    uint32_t* d_frames = nullptr;
+    if ((rc = ensure_accum(s, n)) != PT_OK || (rc = ensure_scratch(s->d_m2, s->m2_cap, n, "second moments")) != PT_OK ||
+        (rc = ensure_tiles(s, T, d_noise, d_frames)) != PT_OK || (rc = blocking_stream(s)) != PT_OK)
+        return rc;
+    HIP_TRY(hipMemcpyAsync(s->d_accum, accum, n * sizeof(float), hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipMemcpyAsync(s->d_m2, m2, n * sizeof(float), hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipMemcpyAsync(d_frames, frames, T * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
+    if ((rc = pt_noise_tiles_async(s, s->d_accum, s->d_m2, w, h, w, tile_w, tile_h, d_frames, tol, floor, d_noise,
+                                   s->stream)) != PT_OK)
+        return rc;
+    HIP_TRY(hipMemcpyAsync(out, d_noise, T * sizeof(pt_tile_noise), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return PT_OK;
+}
+
+int pt_selftest_tile_rects(const uint8_t* active, uint32_t tx, uint32_t ty, uint32_t* rects, size_t cap, size_t* n_out) {
+    if (!active || !n_out || (!rects && cap)) return fail(PT_ERR_INVALID, "null argument");
+    if (tx < 1 || ty < 1 || (uint64_t)tx * ty > (1ull << 30)) return fail(PT_ERR_INVALID, "tile counts out of range");
+    std::vector<std::array<uint32_t, 4>> r;
+    tile_rects(active, tx, ty, r);
+    *n_out = r.size();
+    for (size_t k = 0; k < std::min(cap, r.size()); ++k)
+        for (int c = 0; c < 4; ++c) rects[4 * k + c] = r[k][c];
+    if (r.size() > cap) return fail(PT_ERR_INVALID, "rects holds fewer rectangles than the mask has (*n_out)");
+    return PT_OK;
+}
+
+int pt_render_adaptive(pt_scene* s, const float meta[48], const pt_window* win, const pt_adaptive* ad, uint32_t frame0,
+                       int max_depth, int mode, float* accum, float* m2, uint32_t* tile_frames, pt_tile_noise* tile_noise,
+                       uint8_t* rgba, pt_counters* counters, uint32_t* passes) {
+    if (!s || !meta || !ad || !accum || !tile_frames) return fail(PT_ERR_INVALID, "null argument");
+    int rc = check_adaptive(*ad);
+    if (rc != PT_OK) return rc;
+    if ((uint64_t)frame0 + ad->max_frames > (1ull << 24))
+        return fail(PT_ERR_INVALID, "frame0 + max_frames exceeds 2^24 (t_k = u32(f32(k)) would round)");
+    FrameParams fp{};
+    if ((rc = make_params(meta, max_depth, fp, win)) != PT_OK) return rc;
+    const uint32_t W = fp.win_w, H = fp.win_h;
+    TileGrid g{};
+    if ((rc = make_grid(W, H, W, ad->tile_w, ad->tile_h, g)) != PT_OK) return rc;
+    const size_t npix = (size_t)W * H, n = 3 * npix, T = (size_t)g.tx * g.ty;
+    HIP_TRY(hipSetDevice(s->device));
+    pt_tile_noise* d_noise = nullptr;
+    uint32_t* d_frames = nullptr;
+    if ((rc = ensure_accum(s, n)) != PT_OK || (rc = ensure_scratch(s->d_m2, s->m2_cap, n, "second moments")) != PT_OK ||
+        (rc = ensure_tiles(s, T, d_noise, d_frames)) != PT_OK || (rc = blocking_stream(s)) != PT_OK)
+        return rc;
+    if (rgba && ((rc = ensure_scratch(s->d_mean, s->mean_cap, n, "tile mean")) != PT_OK ||
+                 (rc = ensure_scratch(s->d_rgba, s->rgba_cap, 4 * npix, "image")) != PT_OK))
+        return rc;
+    HIP_TRY(hipMemsetAsync(s->d_accum, 0, n * sizeof(float), s->stream));
+    HIP_TRY(hipMemsetAsync(s->d_m2, 0, n * sizeof(float), s->stream));
+    HIP_TRY(hipMemsetAsync(d_frames, 0, T * sizeof(uint32_t), s->stream));
+    if (counters) HIP_TRY(hipMemsetAsync(s->d_counters, 0, sizeof(Counters), s->stream));
+    Counters* d_cnt = counters ? s->d_counters : nullptr;
+    // pass 0: the whole window
+    const pt_window whole = {fp.win_x0, fp.win_y0, W, H};
+    if ((rc = render_impl(s, meta, frame0, ad->min_frames, 1, max_depth, mode, true, s->d_accum, d_cnt, s->stream, &whole,
+                          nullptr, s->d_m2)) != PT_OK)
+        return rc;
+    std::vector<uint32_t> frames(T, ad->min_frames);
+    std::vector<pt_tile_noise> noise(T);
+    std::vector<uint8_t> active(T);
+    std::vector<std::array<uint32_t, 4>> rects;
+    uint32_t done = ad->min_frames, npass = 1;  // done: the frames of every tile still active
+    for (;;) {
+        HIP_TRY(hipMemcpyAsync(d_frames, frames.data(), T * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
+        if ((rc = pt_noise_tiles_async(s, s->d_accum, s->d_m2, W, H, W, ad->tile_w, ad->tile_h, d_frames, ad->tol,
+                                       ad->floor, d_noise, s->stream)) != PT_OK)
+            return rc;
+        HIP_TRY(hipMemcpyAsync(noise.data(), d_noise, T * sizeof(pt_tile_noise), hipMemcpyDeviceToHost, s->stream));
+        HIP_TRY(hipStreamSynchronize(s->stream));
+        if ((rc = check_watchdog(s)) != PT_OK) return rc;
+        size_t nact = 0;
+        for (size_t t = 0; t < T; ++t) {
+            active[t] = noise[t].noisy > (uint32_t)(ad->noisy_fraction * noise[t].pixels) && frames[t] < ad->max_frames;
+            nact += active[t];
+        }
+        if (nact == 0) break;
+        // the active tiles' next frames: one frame range over the rectangles of the active set, each
+        // rendered in place inside the window's buffers
+        const uint32_t nf = std::min(ad->step_frames, ad->max_frames - done);
+        tile_rects(active.data(), g.tx, g.ty, rects);
+        const size_t pitch = W;
+        for (const auto& r : rects) {
+            const uint32_t px = r[0] * g.tile_w, py = r[1] * g.tile_h;
+            const uint32_t pw = (uint32_t)std::min<uint64_t>((uint64_t)r[2] * g.tile_w, W - px);
+            const uint32_t ph = (uint32_t)std::min<uint64_t>((uint64_t)r[3] * g.tile_h, H - py);
+            const pt_window rw = {fp.win_x0 + px, fp.win_y0 + py, pw, ph};
+            const size_t o = 3 * ((size_t)py * W + px);
+            if ((rc = render_impl(s, meta, frame0 + done, nf, 1, max_depth, mode, true, s->d_accum + o, d_cnt, s->stream,
+                                  &rw, &pitch, s->d_m2 + o)) != PT_OK)
+                return rc;
+        }
+        for (size_t t = 0; t < T; ++t)
+            if (active[t]) frames[t] += nf;
+        done += nf;
+        ++npass;
+    }
+    if (rgba) {  // the display transform of the per-tile mean (d_frames holds the final counts)
+        if ((rc = pt_tile_mean_async(s, s->d_accum, W, H, W, ad->tile_w, ad->tile_h, d_frames, s->d_mean, s->stream)) != PT_OK ||
+            (rc = pt_tonemap_async(s, s->d_mean, npix, 1, s->d_rgba, s->stream)) != PT_OK)
+            return rc;
+        HIP_TRY(hipMemcpyAsync(rgba, s->d_rgba, 4 * npix, hipMemcpyDeviceToHost, s->stream));
+    }
+    HIP_TRY(hipMemcpyAsync(accum, s->d_accum, n * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+    if (m2) HIP_TRY(hipMemcpyAsync(m2, s->d_m2, n * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+    if (counters) HIP_TRY(hipMemcpyAsync(counters, s->d_counters, sizeof(Counters), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    std::memcpy(tile_frames, frames.data(), T * sizeof(uint32_t));
+    if (tile_noise) std::memcpy(tile_noise, noise.data(), T * sizeof(pt_tile_noise));
+    if (passes) *passes = npass;
     return check_watchdog(s);
 }
 

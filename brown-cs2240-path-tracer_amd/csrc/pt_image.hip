@@ -36,6 +36,91 @@ hipError_t launch_tonemap(const float* acc, size_t npix, uint32_t runs, uint8_t*
     return hipGetLastError();
 }
 
+// Per-tile noise verdict from the first and second moments (pt_hip.h pt_noise_tiles_async, DESIGN.md
+// §5.8).  One workgroup per tile, its threads striding over the tile's pixels; per pixel, in double
+// and every operation rounded once (-ffp-contract=off), with S, Q the pixel's acc and m2 and n the
+// tile's frames:
+//   v_c = max(Q_c - S_c^2 / n, 0) (NaN -> 0), V = (v_r + v_g) + v_b, se = sqrt(V / (n (n - 1))),
+//   mu = ((S_r + S_g) + S_b) / n, err = se / max(mu, floor); noisy iff err > tol.
+// The tile's count of noisy pixels and the maximum of err (from 0; a NaN never replaces it) do not
+// depend on the order of the reduction: wave shuffles, then LDS across the waves, then one store.
+constexpr int kNoiseBlock = 256;
+__global__ __launch_bounds__(kNoiseBlock) void k_noise_tiles(const float* __restrict__ acc, const float* __restrict__ m2,
+                                                            TileGrid g, const uint32_t* __restrict__ frames, double tol,
+                                                            double floor, TileNoise* __restrict__ out) {
+    __shared__ uint32_t s_cnt[kNoiseBlock / 64];
+    __shared__ double s_max[kNoiseBlock / 64];
+    const uint32_t t = blockIdx.x, tx = t % g.tx, ty = t / g.tx;
+    const uint32_t x0 = tx * g.tile_w, y0 = ty * g.tile_h;
+    const uint32_t tw = min(g.tile_w, g.w - x0), th = min(g.tile_h, g.h - y0), npx = tw * th;
+    const uint32_t n = frames[t];
+    if (n < 2) {  // no variance estimate yet: every pixel counts as noisy
+        if (threadIdx.x == 0) out[t] = TileNoise{npx, npx, (double)__builtin_inff()};
+        return;
+    }
+    const double dn = (double)n, dd = dn * (dn - 1.0);
+    uint32_t cnt = 0;
+    double m = 0.0;
+    for (uint32_t k = threadIdx.x; k < npx; k += kNoiseBlock) {
+        const uint32_t j = k / tw, i = k - j * tw;
+        const size_t o = 3 * ((size_t)(y0 + j) * g.row_pitch + (x0 + i));
+        const double sr = (double)acc[o], sg = (double)acc[o + 1], sb = (double)acc[o + 2];
+        const double dr = (double)m2[o] - (sr * sr) / dn, dg = (double)m2[o + 1] - (sg * sg) / dn,
+                     db = (double)m2[o + 2] - (sb * sb) / dn;
+        const double vr = dr > 0.0 ? dr : 0.0, vg = dg > 0.0 ? dg : 0.0, vb = db > 0.0 ? db : 0.0;
+        const double V = (vr + vg) + vb;
+        const double se = sqrt(V / dd);
+        const double mu = ((sr + sg) + sb) / dn;
+        const double den = mu > floor ? mu : floor;
+        const double err = se / den;
+        if (err > tol) ++cnt;
+        m = err > m ? err : m;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        cnt += __shfl_xor(cnt, off, 64);
+        const double o = __shfl_xor(m, off, 64);
+        m = o > m ? o : m;
+    }
+    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    if (lane == 0) { s_cnt[wv] = cnt; s_max[wv] = m; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int k = 1; k < kNoiseBlock / 64; ++k) {
+            cnt += s_cnt[k];
+            m = s_max[k] > m ? s_max[k] : m;
+        }
+        out[t] = TileNoise{cnt, npx, m};
+    }
+}
+
+hipError_t launch_noise_tiles(const float* acc, const float* m2, const TileGrid& g, const uint32_t* frames, double tol,
+                              double floor, TileNoise* out, hipStream_t stream) {
+    PT_LAUNCH(KID_NOISE_TILES, stream, k_noise_tiles, dim3(g.tx * g.ty), dim3(kNoiseBlock), 0, stream, acc, m2, g, frames,
+              tol, floor, out);
+    return hipGetLastError();
+}
+
+// mean = acc / (float)frames of the pixel's tile, one f32 division (0 where the tile has no frames);
+// mean is laid out like acc
+__global__ __launch_bounds__(256) void k_tile_mean(const float* __restrict__ acc, TileGrid g,
+                                                  const uint32_t* __restrict__ frames, float* __restrict__ mean) {
+    const uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pix >= g.w * g.h) return;
+    const uint32_t j = pix / g.w, i = pix - j * g.w;
+    const uint32_t n = frames[(j / g.tile_h) * g.tx + i / g.tile_w];
+    const size_t o = 3 * ((size_t)j * g.row_pitch + i);
+    const float d = (float)n;
+    mean[o] = n ? acc[o] / d : 0.0f;
+    mean[o + 1] = n ? acc[o + 1] / d : 0.0f;
+    mean[o + 2] = n ? acc[o + 2] / d : 0.0f;
+}
+
+hipError_t launch_tile_mean(const float* acc, const TileGrid& g, const uint32_t* frames, float* mean, hipStream_t stream) {
+    PT_LAUNCH(KID_TILE_MEAN, stream, k_tile_mean, dim3((g.w * g.h + 255) / 256), dim3(256), 0, stream, acc, g, frames, mean);
+    return hipGetLastError();
+}
+
 // The accumulator to pinned host memory (pt_readback_async): a copy by a few blocks, each thread
 // storing 16-B words straight over PCIe.  The runtime's own copy of a 12 MB accumulator is a blit
 // kernel of 512 blocks that holds its CU slots for the whole PCIe transfer (0.2-1.2 ms in a kernel

@@ -19,12 +19,12 @@ namespace pt {
 // calling thread, every launch is bracketed by two HIP events on its stream.
 enum KernelId : int {
     KID_MEGA = 0, KID_REGEN, KID_WF_GENERATE, KID_WF_TRACE, KID_WF_SHADE_EXT, KID_WF_SHADE_SHADOW, KID_WF_ACCUM,
-    KID_TONEMAP, KID_WF_STEP, KID_WF_LEAF, KID_COUNT
+    KID_TONEMAP, KID_WF_STEP, KID_WF_LEAF, KID_NOISE_TILES, KID_TILE_MEAN, KID_COUNT
 };
 inline const char* kernel_name(int k) {
     static const char* const n[KID_COUNT] = {"k_mega",         "k_regen",           "k_wf_generate", "k_wf_trace",
                                              "k_wf_shade_ext", "k_wf_shade_shadow", "k_wf_accum",    "k_tonemap",
-                                             "k_wf_step",      "k_wf_leafpass"};
+                                             "k_wf_step",      "k_wf_leafpass",     "k_noise_tiles", "k_tile_mean"};
     return (k >= 0 && k < KID_COUNT) ? n[k] : "?";
 }
 struct KernelProfiler {
@@ -118,20 +118,28 @@ struct WfStreams {
 };
 hipError_t launch_wavefront(const LaunchOpts& lo, const SceneView& sc, const FrameParams& fp, const WfBuffers& wb,
                             uint32_t frame0, uint32_t nframes, uint32_t stride, bool accum, bool count, float* out,
-                            Counters* cnt, hipStream_t stream, const WfStreams& ws);
+                            Counters* cnt, hipStream_t stream, const WfStreams& ws, float* m2 = nullptr);
 
 // set width (32 / 64 bits) of the stackless replay in the fused kernel launched last in this process
 // (0: none yet, or the stack walk) — pt_last_bf_width, for the tests of the narrow instance
 int last_bf_width();
 
 // Megakernel render (accum=true: frames frame0 + i*stride, i < nframes, added to out) or one
-// dispatch (accum=false: raw radiance of salt frame0 written to out).
+// dispatch (accum=false: raw radiance of salt frame0 written to out).  m2 (accum only, as in
+// launch_wavefront): the second moments, m2 += clamp(L)^2 per frame, laid out like out.
 hipError_t launch_megakernel(const LaunchOpts& lo, const SceneView& sc, const FrameParams& fp, uint32_t frame0,
                              uint32_t nframes, uint32_t stride, bool accum, bool count, float* out, Counters* cnt,
-                             hipStream_t stream);
+                             hipStream_t stream, float* m2 = nullptr);
 
 // display transform of program-raymarch.ts:295-316 on device (pt_image.hip)
 hipError_t launch_tonemap(const float* acc, size_t npix, uint32_t runs, uint8_t* rgba, hipStream_t stream);
+// per-tile noise verdicts from the two accumulators, and the per-tile mean (pt_image.hip; pt_hip.h
+// pt_noise_tiles_async, pt_tile_mean_async)
+struct TileGrid { uint32_t w, h, row_pitch, tile_w, tile_h, tx, ty; };  // tx, ty: tiles across and down
+struct TileNoise { uint32_t noisy, pixels; double max_err; };              // pt_hip.h pt_tile_noise
+hipError_t launch_noise_tiles(const float* acc, const float* m2, const TileGrid& g, const uint32_t* frames, double tol,
+                              double floor, TileNoise* out, hipStream_t stream);
+hipError_t launch_tile_mean(const float* acc, const TileGrid& g, const uint32_t* frames, float* mean, hipStream_t stream);
 // n floats from device memory to pinned host memory (h_dst_dev: its device address; pt_image.hip)
 hipError_t launch_readback(const float* d_src, float* h_dst_dev, size_t n, hipStream_t stream);
 // dst[i] += src[i] for i < n (f32; both on the stream's device; pt_image.hip)

@@ -73,9 +73,22 @@ __device__ __forceinline__ bool pixel_of(const FrameParams& fp, uint32_t& x, uin
     return valid;
 }
 
-template <bool ACCUM, bool COUNT>
+// MOM (with ACCUM): the second moments too, m2 += c * c beside acc += c (c = clamp(L); the product
+// rounded, then the sum: -ffp-contract=off), in and out like the accumulator and at the same place.
+// M2 is empty (the plain instances, whose arguments and code stay as they were) or one float*.
+template <class... M2>
+__device__ __forceinline__ float* moments_of(M2... m2) {
+    static_assert(sizeof...(M2) <= 1, "at most the one second-moment buffer");
+    float* p[] = {m2..., nullptr};
+    return p[0];
+}
+template <bool ACCUM, bool COUNT, class... M2>
 __global__ __launch_bounds__(kMegaBlock) void k_mega(SceneView sc, FrameParams fp, uint32_t frame0, uint32_t nframes,
-                                                    uint32_t stride, float* __restrict__ out, Counters* cnt_out) {
+                                                    uint32_t stride, float* __restrict__ out, Counters* cnt_out,
+                                                    M2... m2_arg) {
+    constexpr bool MOM = sizeof...(M2) > 0;
+    static_assert(ACCUM || !MOM, "second moments are accumulated");
+    float* __restrict__ const m2 = moments_of(m2_arg...);
     __shared__ int32_t s_stack[kStackMax * kMegaBlock];
     const LStack32 stack = LStack32::make(reinterpret_cast<char*>(s_stack), kMegaBlock);
     uint32_t x, y;
@@ -85,15 +98,19 @@ __global__ __launch_bounds__(kMegaBlock) void k_mega(SceneView sc, FrameParams f
     if (valid) {
         float* o = out + oi;
         f3 acc = ACCUM ? mk(o[0], o[1], o[2]) : mk(0.0f, 0.0f, 0.0f);
+        f3 sq = mk(0.0f, 0.0f, 0.0f);
+        if constexpr (MOM) sq = mk(m2[oi], m2[oi + 1], m2[oi + 2]);
         for (uint32_t i = 0; i < nframes; ++i) {
             uint32_t t = ACCUM ? (uint32_t)(float)(frame0 + i * stride) : frame0;
             uint32_t seed;
             Ray r = camera_ray(fp, x, y, t, seed);
             if (COUNT) c.samples++;
             f3 L = radiance<COUNT>(sc, fp, r, seed, stack, c);
+            if (MOM) sq = add_clamped_sq(sq, L);
             acc = ACCUM ? add_clamped(acc, L) : L;
         }
         o[0] = acc.x; o[1] = acc.y; o[2] = acc.z;
+        if constexpr (MOM) { m2[oi] = sq.x; m2[oi + 1] = sq.y; m2[oi + 2] = sq.z; }
     }
     if (COUNT) flush_counters(c, cnt_out);
 }
@@ -101,9 +118,13 @@ __global__ __launch_bounds__(kMegaBlock) void k_mega(SceneView sc, FrameParams f
 // ---------------------------------------------------------------------------------------
 // Megakernel: path regeneration, one traversal site, optional LDS scene, flat traversal
 // ---------------------------------------------------------------------------------------
-template <bool LDS, int TRAV, bool ACCUM, bool COUNT>
+template <bool LDS, int TRAV, bool ACCUM, bool COUNT, class... M2>
 __global__ __launch_bounds__(kMegaBlock) void k_regen(SceneView sc, FrameParams fp, uint32_t frame0, uint32_t nframes,
-                                                     uint32_t stride, float* __restrict__ out, Counters* cnt_out) {
+                                                     uint32_t stride, float* __restrict__ out, Counters* cnt_out,
+                                                     M2... m2_arg) {
+    constexpr bool MOM = sizeof...(M2) > 0;
+    static_assert(ACCUM || !MOM, "second moments are accumulated");
+    float* __restrict__ const m2 = moments_of(m2_arg...);
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const LStack32 stack = LStack32::make(smem, kMegaBlock);  // [max_stack][256] int32, lane-minor
     if (LDS) stage_scene_lds(sc, smem + (uint32_t)sc.max_stack * kMegaBlock * 4u);
@@ -113,6 +134,10 @@ __global__ __launch_bounds__(kMegaBlock) void k_regen(SceneView sc, FrameParams 
     Counters c = {};
     float* o = out + oi;
     f3 acc = (ACCUM && valid) ? mk(o[0], o[1], o[2]) : mk(0.0f, 0.0f, 0.0f);
+    f3 sq = mk(0.0f, 0.0f, 0.0f);  // MOM: the pixel's second moments (k_mega)
+    if constexpr (MOM) {
+        if (valid) sq = mk(m2[oi], m2[oi + 1], m2[oi + 2]);
+    }
 
     enum { kIdle = 0, kExt = 1, kShadow = 2 };
     int phase = kIdle;
@@ -139,11 +164,15 @@ __global__ __launch_bounds__(kMegaBlock) void k_regen(SceneView sc, FrameParams 
             if (more) { phase = kExt; if (COUNT) c.ext_queries++; }
         }
         if (!more) {
+            if (MOM) sq = add_clamped_sq(sq, ps.L);
             acc = ACCUM ? add_clamped(acc, ps.L) : ps.L;
             phase = kIdle;
         }
     }
     if (valid) { o[0] = acc.x; o[1] = acc.y; o[2] = acc.z; }
+    if constexpr (MOM) {
+        if (valid) { m2[oi] = sq.x; m2[oi + 1] = sq.y; m2[oi + 2] = sq.z; }
+    }
     if (COUNT) flush_counters(c, cnt_out);
 }
 
@@ -385,19 +414,23 @@ bool scene_fits_lds(const SceneView& sc) {
     return (size_t)sc.max_stack * kMegaBlock * 4 + sc.span_bytes <= kLdsSceneBudget;
 }
 
-template <bool LDS, int TRAV, bool ACCUM, bool COUNT>
+// m2...: nothing, or the second-moment buffer (the moments flavour, k_regen<..., float*>)
+template <bool LDS, int TRAV, bool ACCUM, bool COUNT, class... M2>
 static void launch_regen_t(const SceneView& sc, const FrameParams& fp, uint32_t frame0, uint32_t nframes, uint32_t stride,
-                           float* out, Counters* cnt, hipStream_t stream) {
+                           float* out, Counters* cnt, hipStream_t stream, M2... m2) {
     dim3 grid((fp.win_w + 15) / 16, (fp.win_h + 15) / 16), block(kMegaBlock);
     size_t lds = (size_t)sc.max_stack * kMegaBlock * 4 + (LDS ? sc.span_bytes : 0);
-    PT_LAUNCH(KID_REGEN, stream, (k_regen<LDS, TRAV, ACCUM, COUNT>), grid, block, lds, stream, sc, fp, frame0, nframes, stride, out,
-                       cnt);
+    PT_LAUNCH(KID_REGEN, stream, (k_regen<LDS, TRAV, ACCUM, COUNT, M2...>), grid, block, lds, stream, sc, fp, frame0, nframes, stride, out,
+                       cnt, m2...);
 }
 
 template <bool LDS, int TRAV>
 static void launch_regen_a(const SceneView& sc, const FrameParams& fp, uint32_t frame0, uint32_t nframes, uint32_t stride,
-                           bool accum, bool count, float* out, Counters* cnt, hipStream_t stream) {
-    if (accum) {
+                           bool accum, bool count, float* out, Counters* cnt, hipStream_t stream, float* m2) {
+    if (m2) {  // the moments flavour (accumulating calls only: launch_megakernel)
+        if (count) launch_regen_t<LDS, TRAV, true, true>(sc, fp, frame0, nframes, stride, out, cnt, stream, m2);
+        else launch_regen_t<LDS, TRAV, true, false>(sc, fp, frame0, nframes, stride, out, cnt, stream, m2);
+    } else if (accum) {
         if (count) launch_regen_t<LDS, TRAV, true, true>(sc, fp, frame0, nframes, stride, out, cnt, stream);
         else launch_regen_t<LDS, TRAV, true, false>(sc, fp, frame0, nframes, stride, out, cnt, stream);
     } else {
@@ -410,7 +443,8 @@ constexpr int kMegaNodeBias = 8;  // measured with lean4: 1 -> 8 = +9 %
 
 hipError_t launch_megakernel(const LaunchOpts& lo, const SceneView& scene, const FrameParams& fp, uint32_t frame0,
                              uint32_t nframes, uint32_t stride, bool accum, bool count, float* out, Counters* cnt,
-                             hipStream_t stream) {
+                             hipStream_t stream, float* m2) {
+    if (m2 && !accum) return hipErrorInvalidValue;
     SceneView sc = scene;
     if (sc.node_bias <= 0) sc.node_bias = kMegaNodeBias;
     // one node step per turn: more lose in the megakernel (Glossy 256^2: 3 steps -9 %, 8 -15 %,
@@ -420,8 +454,12 @@ hipError_t launch_megakernel(const LaunchOpts& lo, const SceneView& scene, const
     if (lo.literal) {
         dim3 grid((fp.win_w + 15) / 16, (fp.win_h + 15) / 16), block(kMegaBlock);
 #define LIT(A, C) PT_LAUNCH(KID_MEGA, stream, (k_mega<A, C>), grid, block, 0, stream, sc, fp, frame0, nframes, stride, out, cnt)
-        if (accum) { if (count) LIT(true, true); else LIT(true, false); }
+#define LIT_M2(C) \
+    PT_LAUNCH(KID_MEGA, stream, (k_mega<true, C, float*>), grid, block, 0, stream, sc, fp, frame0, nframes, stride, out, cnt, m2)
+        if (m2) { if (count) LIT_M2(true); else LIT_M2(false); }
+        else if (accum) { if (count) LIT(true, true); else LIT(true, false); }
         else { if (count) LIT(false, true); else LIT(false, false); }
+#undef LIT_M2
 #undef LIT
         return hipGetLastError();
     }
@@ -429,8 +467,8 @@ hipError_t launch_megakernel(const LaunchOpts& lo, const SceneView& scene, const
     const int trav = select_megakernel(lo, sc.fast_rcp != 0, sc.mailbox != 0, sc.big_leaf > 0, false);
 #define RA(T)                                                                                             \
     case T:                                                                                               \
-        if (lds) launch_regen_a<true, T>(sc, fp, frame0, nframes, stride, accum, count, out, cnt, stream); \
-        else launch_regen_a<false, T>(sc, fp, frame0, nframes, stride, accum, count, out, cnt, stream);   \
+        if (lds) launch_regen_a<true, T>(sc, fp, frame0, nframes, stride, accum, count, out, cnt, stream, m2); \
+        else launch_regen_a<false, T>(sc, fp, frame0, nframes, stride, accum, count, out, cnt, stream, m2);   \
         break;
     switch (trav) { PT_MEGA_FLAVOURS(RA) }
 #undef RA

@@ -172,6 +172,13 @@ __device__ __forceinline__ f3 add_clamped(f3 acc, f3 L) {
     return mk(acc.x + (L.x >= 0.0f ? L.x : 0.0f), acc.y + (L.y >= 0.0f ? L.y : 0.0f), acc.z + (L.z >= 0.0f ? L.z : 0.0f));
 }
 
+// the second moments beside it: m2 + c * c of the same clamped c, the product rounded to f32 and then
+// the sum (the library builds with -ffp-contract=off: no FMA here)
+__device__ __forceinline__ f3 add_clamped_sq(f3 m2, f3 L) {
+    const float x = L.x >= 0.0f ? L.x : 0.0f, y = L.y >= 0.0f ? L.y : 0.0f, z = L.z >= 0.0f ? L.z : 0.0f;
+    return mk(m2.x + x * x, m2.y + y * y, m2.z + z * z);
+}
+
 __device__ __forceinline__ uint64_t wave_sum(uint64_t v) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);

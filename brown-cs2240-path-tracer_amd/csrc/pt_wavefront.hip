@@ -1086,18 +1086,34 @@ __global__ __launch_bounds__(kShadeBlock) void k_wf_shade(SceneView sc, FramePar
 }
 
 // acc += clamp(radiance) for the batch's frames in order (program-raymarch.ts:283-285); window
-// pixel pix = j * win_w + i lives at acc + 3 * (j * row_pitch + i)
+// pixel pix = j * win_w + i lives at acc + 3 * (j * row_pitch + i).  m2 (nullable, with accumulate):
+// the second moments at the same place, m2 += clamp(L)^2 in the same frame order, so a call's batches
+// continue them as they continue acc
 __global__ __launch_bounds__(256) void k_wf_accum(const float* __restrict__ rad, float* __restrict__ acc, uint32_t npix,
-                                                  uint32_t win_w, uint32_t row_pitch, uint32_t F, bool accumulate) {
+                                                  uint32_t win_w, uint32_t row_pitch, uint32_t F, bool accumulate,
+                                                  float* __restrict__ m2) {
     const uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x;
     if (pix >= npix) return;
     const uint32_t j = pix / win_w;
-    float* o = acc + 3 * ((size_t)j * row_pitch + (pix - j * win_w));
+    const size_t oi = 3 * ((size_t)j * row_pitch + (pix - j * win_w));
+    float* o = acc + oi;
     f3 a = accumulate ? mk(o[0], o[1], o[2]) : mk(0.0f, 0.0f, 0.0f);
-    for (uint32_t f = 0; f < F; ++f) {
-        const float* r = rad + 3 * ((size_t)f * npix + pix);
-        f3 L = mk(r[0], r[1], r[2]);
-        a = accumulate ? add_clamped(a, L) : L;
+    if (m2) {
+        float* q = m2 + oi;
+        f3 sq = mk(q[0], q[1], q[2]);
+        for (uint32_t f = 0; f < F; ++f) {
+            const float* r = rad + 3 * ((size_t)f * npix + pix);
+            const f3 L = mk(r[0], r[1], r[2]);
+            sq = add_clamped_sq(sq, L);
+            a = add_clamped(a, L);
+        }
+        q[0] = sq.x; q[1] = sq.y; q[2] = sq.z;
+    } else {
+        for (uint32_t f = 0; f < F; ++f) {
+            const float* r = rad + 3 * ((size_t)f * npix + pix);
+            f3 L = mk(r[0], r[1], r[2]);
+            a = accumulate ? add_clamped(a, L) : L;
+        }
     }
     o[0] = a.x; o[1] = a.y; o[2] = a.z;
 }
@@ -1199,7 +1215,7 @@ static SceneView bf_view(const SceneView& sc) {
 template <bool LDS, int TRAV, bool COUNT>
 static hipError_t wf_render_t(const SceneView& sc_in, const FrameParams& fp, const WfBuffers& wb, uint32_t frame0,
                               uint32_t nframes, uint32_t stride, bool accum, float* out, Counters* cnt,
-                              hipStream_t stream, const WfStreams& ws, const LaunchOpts& lo) {
+                              hipStream_t stream, const WfStreams& ws, const LaunchOpts& lo, float* m2) {
     SceneView sc = bf_view<TRAV, COUNT>(sc_in);
     const uint32_t npix = fp.win_w * fp.win_h;  // paths per frame: the window's
     // the batch in lo.parts parts on as many streams when a part holds at least a frame: one
@@ -1389,21 +1405,22 @@ static hipError_t wf_render_t(const SceneView& sc_in, const FrameParams& fp, con
             }
         }
         PT_LAUNCH(KID_WF_ACCUM, stream, k_wf_accum, dim3((npix + 255) / 256), dim3(256), 0, stream, wb.rad, out, npix, fp.win_w,
-                  fp.row_pitch, Fb, accum);
+                  fp.row_pitch, Fb, accum, m2);
     }
     return hipGetLastError();
 }
 
 hipError_t launch_wavefront(const LaunchOpts& lo, const SceneView& sc, const FrameParams& fp, const WfBuffers& wb,
                             uint32_t frame0, uint32_t nframes, uint32_t stride, bool accum, bool count, float* out,
-                            Counters* cnt, hipStream_t stream, const WfStreams& ws) {
+                            Counters* cnt, hipStream_t stream, const WfStreams& ws, float* m2) {
+    if (m2 && !accum) return hipErrorInvalidValue;
     if (!accum) { nframes = 1; stride = 1; }
     const bool lds = lo.lds && scene_fits_lds(sc);
     // the leaf pass (FLV_PRE) when the scene's table of pre-resolved leaves holds its big leaves
     // (pt_capi.hip shape_view: option leaf_pre, default on) and the buffers exist
     const int trav = select_wavefront(lo, sc.fast_rcp != 0, sc.mailbox != 0, sc.big_leaf > 0, sc.npre > 0 && sc.pre && wb.pres);
     // sc.node_bias <= 0: chosen per instance in wf_render_t
-#define WF_ARGS sc, fp, wb, frame0, nframes, stride, accum, out, cnt, stream, ws, lo
+#define WF_ARGS sc, fp, wb, frame0, nframes, stride, accum, out, cnt, stream, ws, lo, m2
 #define WF(T)                                                                                                        \
     case T:                                                                                                          \
         return lds ? (count ? wf_render_t<true, T, true>(WF_ARGS) : wf_render_t<true, T, false>(WF_ARGS))            \

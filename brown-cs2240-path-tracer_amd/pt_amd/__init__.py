@@ -12,6 +12,7 @@ no GPU is visible, calls raise `PtError`.
 """
 from ._lib import (  # noqa: F401
     ABI_VERSION,
+    Adaptive,
     MODE_AUTO,
     MODE_MEGAKERNEL,
     MODE_WAVEFRONT,
@@ -19,6 +20,8 @@ from ._lib import (  # noqa: F401
     PtError,
     Scene,
     SceneInfo,
+    TILE_NOISE_DTYPE,
+    TileNoise,
     Window,
     abi_version,
     build_id,
@@ -38,6 +41,7 @@ from ._lib import (  # noqa: F401
     set_hw_queues,
     set_option,
     source_hash,
+    tile_rects,
     tonemap,
 )
 from .host import PackedScene, load_scene, program_entry  # noqa: F401

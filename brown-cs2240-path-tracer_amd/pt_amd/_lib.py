@@ -74,6 +74,59 @@ def _window(window):
     return Window(*[_uint(v, f"window {n}") for v, n in zip(t, ("x0", "y0", "w", "h"))])
 
 
+class TileNoise(ctypes.Structure):
+    """pt_tile_noise: a tile's noisy pixels, its pixels and its largest error estimate (16 bytes)."""
+    _fields_ = [("noisy", ctypes.c_uint32), ("pixels", ctypes.c_uint32), ("max_err", ctypes.c_double)]
+
+
+# numpy's view of an array of pt_tile_noise
+TILE_NOISE_DTYPE = np.dtype([("noisy", "<u4"), ("pixels", "<u4"), ("max_err", "<f8")])
+
+
+class Adaptive(ctypes.Structure):
+    """pt_adaptive: the parameters of pt_render_adaptive."""
+    _fields_ = [("tile_w", ctypes.c_uint32), ("tile_h", ctypes.c_uint32), ("min_frames", ctypes.c_uint32),
+                ("step_frames", ctypes.c_uint32), ("max_frames", ctypes.c_uint32), ("tol", ctypes.c_double),
+                ("floor", ctypes.c_double), ("noisy_fraction", ctypes.c_double)]
+
+
+def _tile(tile):
+    """A (tile_w, tile_h) pair checked on the host: two integers >= 1."""
+    try:
+        t = tuple(tile)
+    except TypeError:
+        raise PtError(-1, f"tile must be (tile_w, tile_h), not {tile!r}") from None
+    if len(t) != 2:
+        raise PtError(-1, f"tile must have two values (tile_w, tile_h), not {len(t)}")
+    return _uint(t[0], "tile_w", 1), _uint(t[1], "tile_h", 1)
+
+
+def _real(v, what: str, positive: bool = True) -> float:
+    """v as a finite float (> 0 when positive), else PtError(-1)."""
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+        raise PtError(-1, f"{what} must be a number, not {v!r}")
+    f = float(v)
+    if not np.isfinite(f) or (positive and not f > 0.0):
+        raise PtError(-1, f"{what} must be finite{' and > 0' if positive else ''}, not {v!r}")
+    return f
+
+
+def _adaptive(tile, min_frames, step_frames, max_frames, tol, floor, noisy_fraction, frame0) -> Adaptive:
+    """pt_adaptive checked on the host, field by field (the library checks it again)."""
+    tw, th = _tile(tile)
+    lo = _uint(min_frames, "min_frames", 2)
+    step = _uint(step_frames, "step_frames", 1)
+    hi = _uint(max_frames, "max_frames", 1)
+    if hi < lo:
+        raise PtError(-1, f"max_frames must be at least min_frames ({lo}), not {hi}")
+    nf = _real(noisy_fraction, "noisy_fraction", positive=False)
+    if not 0.0 <= nf < 1.0:
+        raise PtError(-1, f"noisy_fraction must lie in [0, 1), not {noisy_fraction!r}")
+    if _uint(frame0, "frame0") + hi > 1 << 24:
+        raise PtError(-1, f"frame0 + max_frames must not exceed 2^24, not {frame0} + {hi}")
+    return Adaptive(tw, th, lo, step, hi, _real(tol, "tol"), _real(floor, "floor"), nf)
+
+
 def _extent(meta, win):
     """(w, h) of a call's result: the window's, or the image's of meta[0..1]."""
     return (int(win.w), int(win.h)) if win is not None else (int(meta[0]), int(meta[1]))
@@ -149,6 +202,14 @@ def load_library():
     L.pt_render_window_async.argtypes = [p, p, wp, u32, u32, u32, i, i, p, sz, p, p]
     L.pt_frame_window.argtypes = [p, p, wp, u32, i, p]
     L.pt_frame_async.argtypes = [p, p, u32, i, p, p]
+    dbl = ctypes.c_double
+    L.pt_render_moments.argtypes = [p, p, wp, u32, u32, u32, i, i, p, p, p]
+    L.pt_render_moments_async.argtypes = [p, p, wp, u32, u32, u32, i, i, p, p, sz, p, p]
+    L.pt_noise_tiles_async.argtypes = [p, p, p, u32, u32, sz, u32, u32, p, dbl, dbl, p, p]
+    L.pt_noise_tiles.argtypes = [p, p, p, u32, u32, u32, u32, p, dbl, dbl, p]
+    L.pt_tile_mean_async.argtypes = [p, p, u32, u32, sz, u32, u32, p, p, p]
+    L.pt_render_adaptive.argtypes = [p, p, wp, ctypes.POINTER(Adaptive), u32, i, i, p, p, p, p, p, p, ctypes.POINTER(u32)]
+    L.pt_selftest_tile_rects.argtypes = [p, u32, u32, p, sz, ctypes.POINTER(sz)]
     L.pt_tonemap.argtypes = [p, sz, u32, p]
     L.pt_selftest_math.argtypes = [i, i, p, p, p, sz]
     L.pt_profile_enable.argtypes = [p, i]
@@ -173,7 +234,8 @@ def load_library():
     i32p = ctypes.POINTER(ctypes.c_int32)
     L.pt_scene_leaf_bvh.argtypes = [p, i, i32p, i32p, i32p]
     L.pt_selftest_leaf.argtypes = [p, i, i, u32, u32, p]
-    for fn in ("pt_render_window", "pt_render_window_async", "pt_frame_window", "pt_scene_leaf_bvh", "pt_selftest_leaf", "pt_selftest_valu", "pt_set_option", "pt_get_option", "pt_release_communicators", "pt_scene_check", "pt_set_hw_queues", "pt_render_multi", "pt_bvh_build_sah", "pt_bvh_build_sah2", "pt_device_count", "pt_scene_create", "pt_scene_get_info", "pt_render", "pt_render_async", "pt_frame",
+    for fn in ("pt_render_moments", "pt_render_moments_async", "pt_noise_tiles_async", "pt_noise_tiles", "pt_tile_mean_async",
+               "pt_render_adaptive", "pt_selftest_tile_rects", "pt_render_window", "pt_render_window_async", "pt_frame_window", "pt_scene_leaf_bvh", "pt_selftest_leaf", "pt_selftest_valu", "pt_set_option", "pt_get_option", "pt_release_communicators", "pt_scene_check", "pt_set_hw_queues", "pt_render_multi", "pt_bvh_build_sah", "pt_bvh_build_sah2", "pt_device_count", "pt_scene_create", "pt_scene_get_info", "pt_render", "pt_render_async", "pt_frame",
                "pt_frame_async", "pt_tonemap", "pt_selftest_math", "pt_profile_enable", "pt_profile_select", "pt_profile_read", "pt_selftest_rcp", "pt_bvh_build", "pt_tonemap_async", "pt_readback_async", "pt_render_image",
                "pt_scene_set_vertex_normals"):
         getattr(L, fn).restype = i
@@ -374,6 +436,110 @@ class Scene:
         self.render_async(meta, frame0, nframes, stride, max_depth, mode, d_accum_ptr, stream_ptr, d_counters_ptr,
                           window=window, row_pitch=row_pitch)
 
+    def render_moments(self, meta, frame0: int, nframes: int, stride: int = 1, max_depth: int = -1,
+                       mode: int = MODE_AUTO, accum: np.ndarray | None = None, m2: np.ndarray | None = None,
+                       counters: bool = False, window=None):
+        """render that also accumulates the second moments (pt_render_moments): m2 += clamp(L)^2 per
+        frame, f32, in/out like accum and of its shape.  Returns (accum, m2) (and counters if
+        requested); accum holds the bits render gives from the same start."""
+        meta = _f32(meta)
+        win = _window(window)
+        W, H = _extent(meta, win)
+        bufs = []
+        for a, what in ((accum, "accum"), (m2, "m2")):
+            if a is None:
+                a = np.zeros((H, W, 3), np.float32)
+            if not isinstance(a, np.ndarray) or a.dtype != np.float32 or not a.flags.c_contiguous or a.size != W * H * 3:
+                raise ValueError(f"{what} must be a contiguous float32 array of H*W*3 elements (the window's h*w*3)")
+            bufs.append(a)
+        c = Counters()
+        _check(self._lib.pt_render_moments(self._h, _ptr(meta), ctypes.byref(win) if win is not None else None, frame0,
+                                           nframes, stride, max_depth, mode, _ptr(bufs[0]), _ptr(bufs[1]),
+                                           ctypes.byref(c) if counters else None))
+        return (bufs[0], bufs[1], c.as_dict()) if counters else (bufs[0], bufs[1])
+
+    def render_moments_async(self, meta, frame0: int, nframes: int, stride: int, max_depth: int, mode: int,
+                             d_accum_ptr: int, d_m2_ptr: int, stream_ptr: int = 0, d_counters_ptr: int = 0, window=None,
+                             row_pitch=None):
+        """render_async with the second moments (pt_render_moments_async): d_m2_ptr addresses a device
+        f32 buffer laid out like d_accum_ptr's (the window's first pixel, the same row_pitch)."""
+        meta = _f32(meta)
+        win = _window(window)
+        pitch = _extent(meta, win)[0] if row_pitch is None else _uint(row_pitch, "row_pitch")
+        _check(self._lib.pt_render_moments_async(self._h, _ptr(meta), ctypes.byref(win) if win is not None else None,
+                                                 frame0, nframes, stride, max_depth, mode, ctypes.c_void_p(d_accum_ptr),
+                                                 ctypes.c_void_p(d_m2_ptr or None), pitch,
+                                                 ctypes.c_void_p(d_counters_ptr or None),
+                                                 ctypes.c_void_p(stream_ptr or None)))
+
+    def noise_tiles(self, accum, m2, tile, frames, tol: float, floor: float) -> np.ndarray:
+        """pt_noise_tiles: the noise verdict of every tile of tile=(tile_w, tile_h) pixels over the host
+        accumulators accum and m2 [h, w, 3]; frames [TY, TX] are the tiles' sample counts.  Returns a
+        [TY, TX] array of TILE_NOISE_DTYPE (noisy, pixels, max_err)."""
+        acc, sq = _f32(accum), _f32(m2)
+        if acc.ndim != 3 or acc.shape[2] != 3 or sq.shape != acc.shape:
+            raise PtError(-1, f"accum and m2 must both be [h, w, 3], not {acc.shape} and {sq.shape}")
+        h, w = acc.shape[:2]
+        tw, th = _tile(tile)
+        tx, ty = -(-w // tw), -(-h // th)
+        fr = np.ascontiguousarray(frames, dtype=np.uint32)
+        if fr.size != tx * ty:
+            raise PtError(-1, f"frames must hold one count per tile ({ty} x {tx}), not {fr.shape}")
+        out = np.zeros((ty, tx), TILE_NOISE_DTYPE)
+        _check(self._lib.pt_noise_tiles(self._h, _ptr(acc), _ptr(sq), w, h, tw, th, _ptr(fr), _real(tol, "tol"),
+                                        _real(floor, "floor"), _ptr(out)))
+        return out
+
+    def noise_tiles_async(self, d_accum_ptr: int, d_m2_ptr: int, w: int, h: int, tile, d_frames_ptr: int, tol: float,
+                          floor: float, d_out_ptr: int, row_pitch=None, stream_ptr: int = 0):
+        """pt_noise_tiles_async between caller-owned device buffers: accumulators of w x h pixels, rows
+        row_pitch pixels apart (default w), u32 frames and 16-byte verdicts per tile."""
+        tw, th = _tile(tile)
+        w, h = _uint(w, "w", 1), _uint(h, "h", 1)
+        pitch = w if row_pitch is None else _uint(row_pitch, "row_pitch")
+        _check(self._lib.pt_noise_tiles_async(self._h, ctypes.c_void_p(d_accum_ptr or None), ctypes.c_void_p(d_m2_ptr or None),
+                                              w, h, pitch, tw, th, ctypes.c_void_p(d_frames_ptr or None), _real(tol, "tol"),
+                                              _real(floor, "floor"), ctypes.c_void_p(d_out_ptr or None),
+                                              ctypes.c_void_p(stream_ptr or None)))
+
+    def tile_mean_async(self, d_accum_ptr: int, w: int, h: int, tile, d_frames_ptr: int, d_mean_ptr: int, row_pitch=None,
+                        stream_ptr: int = 0):
+        """pt_tile_mean_async: mean = accum / f32(frames of the pixel's tile) (0 where that is 0), between
+        device buffers of the same layout."""
+        tw, th = _tile(tile)
+        w, h = _uint(w, "w", 1), _uint(h, "h", 1)
+        pitch = w if row_pitch is None else _uint(row_pitch, "row_pitch")
+        _check(self._lib.pt_tile_mean_async(self._h, ctypes.c_void_p(d_accum_ptr or None), w, h, pitch, tw, th,
+                                            ctypes.c_void_p(d_frames_ptr or None), ctypes.c_void_p(d_mean_ptr or None),
+                                            ctypes.c_void_p(stream_ptr or None)))
+
+    def render_adaptive(self, meta, frame0: int = 0, max_depth: int = -1, mode: int = MODE_AUTO, window=None,
+                        tile=(64, 64), min_frames: int = 16, step_frames: int = 16, max_frames: int = 256,
+                        tol: float = 0.05, floor: float = 0.05, noisy_fraction: float = 0.01, counters: bool = False) -> dict:
+        """pt_render_adaptive: min_frames frames everywhere, then step_frames more per pass on the tiles
+        where more than noisy_fraction of the pixels still have a relative standard error above tol,
+        up to max_frames per tile.  Returns {"accum", "m2": [h, w, 3] sums over each tile's frames,
+        "tile_frames": [TY, TX] u32, "tile_noise": [TY, TX] TILE_NOISE_DTYPE, "rgba": [h, w, 4] u8 of
+        the per-tile mean, "passes"} and "counters" if requested."""
+        meta = _f32(meta)
+        win = _window(window)
+        ad = _adaptive(tile, min_frames, step_frames, max_frames, tol, floor, noisy_fraction, frame0)
+        W, H = _extent(meta, win)
+        tx, ty = -(-W // ad.tile_w), -(-H // ad.tile_h)
+        out = {"accum": np.zeros((H, W, 3), np.float32), "m2": np.zeros((H, W, 3), np.float32),
+               "tile_frames": np.zeros((ty, tx), np.uint32), "tile_noise": np.zeros((ty, tx), TILE_NOISE_DTYPE),
+               "rgba": np.zeros((H, W, 4), np.uint8)}
+        c = Counters()
+        npass = ctypes.c_uint32(0)
+        _check(self._lib.pt_render_adaptive(self._h, _ptr(meta), ctypes.byref(win) if win is not None else None,
+                                            ctypes.byref(ad), frame0, max_depth, mode, _ptr(out["accum"]), _ptr(out["m2"]),
+                                            _ptr(out["tile_frames"]), _ptr(out["tile_noise"]), _ptr(out["rgba"]),
+                                            ctypes.byref(c) if counters else None, ctypes.byref(npass)))
+        out["passes"] = int(npass.value)
+        if counters:
+            out["counters"] = c.as_dict()
+        return out
+
     def render_image(self, meta, frame0: int, nframes: int, stride: int = 1, max_depth: int = -1,
                      mode: int = MODE_AUTO, counters: bool = False):
         """programEntry's displayed image in one call: RGBA u8 [H, W, 4] (device tone map)."""
@@ -478,6 +644,19 @@ def render_tiled(scene, meta, frame0: int, nframes: int, stride: int = 1, max_de
                     setattr(total, n, getattr(total, n) + c[n])
             accum[y0:y0 + h, x0:x0 + w] = r
     return (accum, total.as_dict()) if counters else accum
+
+
+def tile_rects(active) -> np.ndarray:
+    """pt_selftest_tile_rects (host only): the rectangles [n, 4] u32 (tx0, ty0, width, height, in tiles)
+    pt_render_adaptive renders for the [TY, TX] mask of active tiles."""
+    a = np.ascontiguousarray(np.asarray(active) != 0, dtype=np.uint8)
+    if a.ndim != 2 or a.size == 0:
+        raise PtError(-1, f"active must be a non-empty [TY, TX] mask, not shape {a.shape}")
+    ty, tx = a.shape
+    out = np.zeros((max(1, int(a.sum())), 4), np.uint32)
+    n = ctypes.c_size_t(0)
+    _check(load_library().pt_selftest_tile_rects(_ptr(a), tx, ty, _ptr(out), out.shape[0], ctypes.byref(n)))
+    return out[: n.value]
 
 
 def tonemap(accum, sample_runs: int) -> np.ndarray:

@@ -152,6 +152,75 @@ int pt_render_window_async(pt_scene* scene, const float meta[48], const pt_windo
                            uint32_t nframes, uint32_t frame_stride, int max_depth, int mode, float* d_accum,
                            size_t row_pitch, pt_counters* d_counters, void* stream);
 
+/* pt_render_window / pt_render_window_async that also accumulate the second moments: for every pixel
+ * and channel, beside accum += c with c = (L >= 0 ? L : 0), m2 = m2 + c * c (the product rounded to
+ * f32, then the sum), frame after frame from the value already in the buffer.  m2 / d_m2: f32, the
+ * accumulator's shape and pitch, in/out, not NULL.  The accumulator's bits and the counters are those
+ * of the call without moments.  win NULL = the whole image. */
+int pt_render_moments(pt_scene* scene, const float meta[48], const pt_window* win, uint32_t frame0, uint32_t nframes,
+                      uint32_t frame_stride, int max_depth, int mode, float* accum, float* m2, pt_counters* counters);
+int pt_render_moments_async(pt_scene* scene, const float meta[48], const pt_window* win, uint32_t frame0,
+                            uint32_t nframes, uint32_t frame_stride, int max_depth, int mode, float* d_accum,
+                            float* d_m2, size_t row_pitch, pt_counters* d_counters, void* stream);
+
+/* A tile's noise verdict: its pixels, how many of them are noisy, and the largest error estimate. */
+typedef struct { uint32_t noisy, pixels; double max_err; } pt_tile_noise; /* 16 B */
+
+/* Noise estimate per tile from the two accumulators.  Tiles of tile_w x tile_h over a w x h buffer
+ * (rows row_pitch pixels apart; w, h in [1, 32768]); the right and bottom tiles are as small as the
+ * buffer leaves them.  TX = ceil(w / tile_w), TY likewise.  frames[ty * TX + tx] is the tile's sample
+ * count n, out[ty * TX + tx] its verdict.  Per pixel, in double, every operation rounded once, with
+ * S_c, Q_c the pixel's accum and m2 values:
+ *   d_c = Q_c - (S_c * S_c) / n;  v_c = d_c > 0 ? d_c : 0  (NaN -> 0);  V = (v_r + v_g) + v_b
+ *   se = sqrt(V / (n * (n - 1)));  mu = ((S_r + S_g) + S_b) / n;  err = se / (mu > floor ? mu : floor)
+ * — the standard error of the pixel's mean relative to its brightness.  A pixel is noisy iff
+ * err > tol; max_err is the running (err > m ? err : m) from 0.  Tiles with n < 2 report noisy =
+ * pixels and max_err = +inf.  tol and floor: finite, > 0.  Asynchronous on `stream`. */
+int pt_noise_tiles_async(pt_scene* scene, const float* d_accum, const float* d_m2, uint32_t w, uint32_t h,
+                         size_t row_pitch, uint32_t tile_w, uint32_t tile_h, const uint32_t* d_frames, double tol,
+                         double floor, pt_tile_noise* d_out, void* stream);
+/* The same on dense host buffers.  Blocking. */
+int pt_noise_tiles(pt_scene* scene, const float* accum, const float* m2, uint32_t w, uint32_t h, uint32_t tile_w,
+                   uint32_t tile_h, const uint32_t* frames, double tol, double floor, pt_tile_noise* out);
+
+/* mean[p] = accum[p] / (float)frames[tile of p]: one correctly rounded f32 division; 0 where the
+ * tile's frames are 0.  d_mean is laid out like d_accum (row_pitch).  Asynchronous on `stream`. */
+int pt_tile_mean_async(pt_scene* scene, const float* d_accum, uint32_t w, uint32_t h, size_t row_pitch,
+                       uint32_t tile_w, uint32_t tile_h, const uint32_t* d_frames, float* d_mean, void* stream);
+
+/* Adaptive render: frames only where the image is still noisy. */
+typedef struct {
+    uint32_t tile_w, tile_h; /* >= 1 */
+    uint32_t min_frames;     /* >= 2: first pass, every tile */
+    uint32_t step_frames;    /* >= 1: per refinement pass */
+    uint32_t max_frames;     /* >= min_frames: cap per tile */
+    double tol, floor;       /* finite, > 0 (pt_noise_tiles_async) */
+    double noisy_fraction;   /* in [0, 1): a tile is done when noisy <= (uint32_t)(noisy_fraction * pixels) */
+} pt_adaptive;
+
+/* Pass 0 renders frames frame0 .. frame0 + min_frames - 1 of the whole window (NULL = the image)
+ * with moments.  After each pass pt_noise_tiles_async judges every tile; a tile stays active iff
+ * noisy > (uint32_t)(noisy_fraction * pixels) and its frames < max_frames, and every active tile gets
+ * the next min(step_frames, max_frames - frames) frames (a tile that stops never restarts, so the
+ * active tiles share one frame count) as in-place window renders of the active set's rectangles
+ * (pt_selftest_tile_rects).  A tile with n frames holds the bits of that rectangle of a plain n-frame
+ * render.  Outputs (host, written, not read): accum and m2 [h][w][3], tile_frames [TY][TX],
+ * tile_noise [TY][TX] (the last verdicts), rgba [h][w][4] = the display transform of the per-tile
+ * mean (pt_tile_mean_async, then sample_runs = 1), counters = the sum over all passes, passes = the
+ * number of render passes; m2, tile_noise, rgba, counters, passes: nullable.  frame0 + max_frames
+ * must not exceed 2^24.  Blocking. */
+int pt_render_adaptive(pt_scene* scene, const float meta[48], const pt_window* win, const pt_adaptive* ad,
+                       uint32_t frame0, int max_depth, int mode, float* accum, float* m2, uint32_t* tile_frames,
+                       pt_tile_noise* tile_noise, uint8_t* rgba, pt_counters* counters, uint32_t* passes);
+
+/* Host only, for tests: the rectangles pt_render_adaptive renders for a mask of active tiles
+ * (active[ty * tx_count + tx] != 0), four u32 per rectangle (tx0, ty0, width, height, in tiles).
+ * Tile rows top to bottom, the maximal runs of active tiles in each; a run with the same [tx0, tx1)
+ * as a rectangle still open from the row above extends it, any other opens a new one.  *n_out = the
+ * rectangles; more than cap: PT_ERR_INVALID (rects holds the first cap). */
+int pt_selftest_tile_rects(const uint8_t* active, uint32_t tx, uint32_t ty, uint32_t* rects, size_t cap,
+                           size_t* n_out);
+
 /* Completion check of the asynchronous calls: waits for every render of the scene to finish
  * (blocking) and reports a device-side failure of any of them — a wavefront traversal wave that
  * gave up after its watchdog limit leaves a flag instead of hanging, and the accumulators of
