@@ -1,11 +1,10 @@
-// pt_capi.hip — C ABI (include/pt_hip.h): scene upload/re-encoding, render entry points.
-// Host code only; kernels live in pt_kernels.hip.
+// pt_capi.hip — C ABI (include/pt_hip.h): options, scene upload, render entry points.
+// Host code only; kernels live in pt_kernels.hip, the scene's re-encoding in pt_scene_layout.cpp.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <algorithm>
 #include <array>
-#include <cfloat>
 #include <cstring>
 #include <map>
 #include <mutex>
@@ -18,7 +17,7 @@
 
 #include "../../include/pt_hip.h"
 #include "pt_kernels.h"
-#include "pt_leafbvh.h"
+#include "pt_scene_layout.h"
 
 using namespace pt;
 
@@ -36,26 +35,6 @@ int fail(int code, const std::string& msg) {
         hipError_t e_ = (expr);                                                                      \
         if (e_ != hipSuccess) return fail(PT_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
     } while (0)
-
-// WGSL i32(f32): truncate toward zero, saturating.
-int32_t wgsl_i32(float f) {
-    if (std::isnan(f)) return 0;
-    if (f >= 2147483647.0f) return INT32_MAX;
-    if (f <= -2147483648.0f) return INT32_MIN;
-    return (int32_t)f;
-}
-
-// Reads of the packed triangle buffer with Dawn/Tint robustness (index clamped to len-1),
-// as the WGSL reads primitive_0 in sample_area_lights (intersection-logic.wgsl:260-279).
-struct Packed {
-    const float* p;
-    size_t n;
-    float at(int32_t i) const {
-        uint32_t u = (uint32_t)i;
-        if (u >= n) u = (uint32_t)(n - 1);
-        return p[u];
-    }
-};
 
 // ---------------------------------------------------------------------------------------------
 // Options (pt_set_option): the process-wide table of kernel-selection switches.  Nothing is read
@@ -134,400 +113,10 @@ Opts opts_snapshot() {
     return o;
 }
 
-// leaves of at least this many entries get leaf chunks (option leaf_bvh, read by pt_scene_create;
-// the big-leaf threshold): exact (tests/test_gpu_leafbvh.py), MedievalBoat +10 % in process
-// (DESIGN.md §5.3); 0 = none
-constexpr long kLeafBvhDefault = 128;
 // the probe of the pre-resolvable leaves (probe_pre_leaves): a 32 x 32 raster (<= 4 Ki queries), at
 // most 2^23 triangle tests (MedievalBoat: ~4 k per query, ~30 ms)
 constexpr int kPreProbeGrid = 32;
-// the leaf pass's chunks: the builder's leaves of at most PT_PASS_LEAF entries, neighbours merged
-// while they fit PT_PASS_MERGE (<= kPassChunkMax; 0: no merging)
-#ifndef PT_PASS_LEAF
-#define PT_PASS_LEAF kPassChunkMax
-#endif
-#ifndef PT_PASS_MERGE
-#define PT_PASS_MERGE kPassChunkMax
-#endif
-static_assert(PT_PASS_LEAF <= kPassChunkMax && PT_PASS_MERGE <= kPassChunkMax, "pass chunks fit the pass's loops");
 constexpr uint64_t kPreProbeTests = 1ull << 23;
-// the leaf remainders' probe (build_leaf_skips): at most 2^24 triangle tests (Glossy ~1.7 M, ~20 ms)
-constexpr uint64_t kLeafSkipProbeTests = 1ull << 24;
-
-struct HostLayout {
-    std::vector<Node> nodes;
-    std::vector<Tri> tris;
-    std::vector<Material> mats;
-    std::vector<Light> lights;
-    std::vector<uint64_t> lmask;  // mailbox scenes: uid set per leaf, indexed by first record
-    std::vector<float4> tnorm;    // vertex-normal mode: 3 per record (SceneView::tnorm)
-    std::vector<BfNode> bfnode;   // mailbox scenes with <= 64 internal nodes, <= 63 entries (SceneView::bfnode)
-    std::vector<int32_t> bfmap;
-    std::vector<BfNode> bfnarrow; // ... of <= 32 internal nodes, <= 32 entries: the narrow payload (SceneView::bfnarrow)
-    std::vector<LNode> lnodes;    // leaf BVHs (SceneView::lnodes), and per such leaf (first record, entries, nodes)
-    std::vector<int32_t> lidx;
-    std::vector<Tri> ltris;       // per chunk slot: its entry's record, lbvh = the entry's position in its leaf
-    std::vector<LNode> pnodes;    // the leaf pass's chunks of the pre-resolvable leaves (SceneView::pnodes, PreLeaf c0 / c1)
-    std::vector<Tri> ptris;       // per pass chunk slot: its entry's record, lbvh = the entry's position in its leaf
-    std::vector<float4> pnorm;    // per pass chunk slot: its entry's unit normal
-    std::vector<std::array<int32_t, 3>> lleaves;
-    int32_t leaf_min = 0;         // leaves of at least this many entries have one (option leaf_bvh; 0: none)
-    std::vector<PreLeaf> pre;     // the kMaxPre largest leaves with their paths (SceneView::pre), largest first
-    std::vector<int32_t> leaf_sizes;  // every non-empty leaf's entries, largest first
-    std::vector<int2> nalt;       // leaf remainders (SceneView::nalt; empty: none)
-    LeafSkipStats skip{};
-    int32_t mb_base = 0;          // record of uid 0 (mailbox scenes)
-    bool mailbox = false;
-    pt_scene_info info{};
-    int32_t ntri = 0;
-    bool fast_rcp = false;  // SceneView::fast_rcp
-};
-
-// Re-encode packer.ts layouts into pt_layout.h.
-int build_layout(const float* tri, size_t tri_len, const float* bvh, size_t bvh_len, HostLayout& L) {
-    if (tri_len < 16 || tri_len > (size_t)INT32_MAX) return fail(PT_ERR_SCENE, "triangle_data shorter than its 16-float header");
-    if (bvh_len < 6 + 17 || bvh_len > (size_t)INT32_MAX) return fail(PT_ERR_SCENE, "bvh_data shorter than bounds + one node");
-    Packed P{tri, tri_len};
-    const float nverts_f = tri[0], nobj_f = tri[1];
-    if (!(nverts_f >= 0 && nverts_f == std::floor(nverts_f)) || !(nobj_f >= 1 && nobj_f == std::floor(nobj_f)))
-        return fail(PT_ERR_SCENE, "bad vertex/object counts in triangle_data header");
-    const int64_t nverts = (int64_t)nverts_f, nobj = (int64_t)nobj_f;
-    const int64_t v_start = wgsl_i32(tri[2]), m_start = wgsl_i32(tri[4]);
-    if (v_start < 0 || v_start + 3 * nverts > (int64_t)tri_len) return fail(PT_ERR_SCENE, "vertex section out of range");
-    if (m_start < 0 || m_start + 15 * nobj > (int64_t)tri_len) return fail(PT_ERR_SCENE, "material section out of range");
-    L.info.vertices = (uint32_t)nverts;
-
-    // materials (program-raymarch.wgsl:87-102): Ns Ni illum Ka Kd Ks Ke
-    L.mats.resize((size_t)nobj);
-    for (int64_t id = 0; id < nobj; ++id) {
-        const float* m = tri + m_start + 15 * id;
-        Material& o = L.mats[(size_t)id];
-        std::memset(&o, 0, sizeof o);
-        o.Ns = m[0]; o.Ni = m[1]; o.illum = m[2];
-        for (int c = 0; c < 3; ++c) { o.Kd[c] = m[6 + c]; o.Ks[c] = m[9 + c]; o.Ke[c] = m[12 + c]; }
-        // the material's constant quotients, once per scene instead of per path and bounce: the
-        // same correctly rounded f32 divisions the device would make (no contraction, no FTZ)
-        o.kd_pi0 = o.Kd[0] / kPI; o.kd_pi1 = o.Kd[1] / kPI; o.kd_pi2 = o.Kd[2] / kPI;
-        o.phong = (o.Ns + 2.0f) / (2.0f * kPI);
-    }
-    L.info.materials = (uint32_t)nobj;
-
-    auto vertex = [&](int64_t one_based, float out[3]) -> bool {
-        if (one_based < 1 || one_based > nverts) return false;
-        const float* v = tri + v_start + 3 * (one_based - 1);
-        out[0] = v[0]; out[1] = v[1]; out[2] = v[2];
-        return true;
-    };
-
-    // BVH: pre-order tree from offset 6 (intersection-logic.wgsl:4-16).
-    if (bvh[6] == 1.0f) return fail(PT_ERR_SCENE, "BVH root is a leaf (the reference never builds one)");
-    struct Item { int32_t off; int32_t node; int32_t depth; };
-    std::vector<Item> work;
-    // mailbox bookkeeping: each record's leaf entry (i0, i1, i2, material) and the leaves
-    std::vector<std::array<int32_t, 4>> entry;
-    std::vector<std::pair<int32_t, int32_t>> leaf_ranges;  // (first record, count)
-    L.nodes.push_back(Node{});
-    work.push_back({6, 0, 0});
-    const size_t node_cap = bvh_len / 17 + 1;
-    uint32_t max_depth = 0;
-    while (!work.empty()) {
-        Item it = work.back();
-        work.pop_back();
-        const int32_t o = it.off;
-        if (o < 0 || (size_t)o + 17 > bvh_len) return fail(PT_ERR_SCENE, "BVH node offset out of range");
-        max_depth = std::max<uint32_t>(max_depth, (uint32_t)it.depth);
-        Node nd{};
-        for (int c = 0; c < 3; ++c) {
-            nd.lmin[c] = bvh[o + 5 + c]; nd.lmax[c] = bvh[o + 8 + c];
-            nd.rmin[c] = bvh[o + 11 + c]; nd.rmax[c] = bvh[o + 14 + c];
-        }
-        int32_t child_off[2] = {wgsl_i32(bvh[o + 2]), wgsl_i32(bvh[o + 3])};
-        int32_t refs[2], cnts[2];
-        for (int side = 0; side < 2; ++side) {
-            const int32_t c = child_off[side];
-            if (c < 0 || (size_t)c + 17 > bvh_len) return fail(PT_ERR_SCENE, "BVH child pointer out of range");
-            if (bvh[c] == 1.0f) {  // leaf: (i0,i1,i2,mat) 1-based entries after the 17-float header
-                const float nf = bvh[c + 4];
-                if (!(nf >= 0) || std::fmod(nf, 4.0f) != 0.0f || (size_t)c + 17 + (size_t)nf > bvh_len)
-                    return fail(PT_ERR_SCENE, "BVH leaf payload malformed");
-                const int32_t n = (int32_t)(nf / 4.0f);
-                refs[side] = (int32_t)L.tris.size();
-                cnts[side] = n;
-                for (int32_t k = 0; k < n; ++k) {
-                    const float* e = bvh + c + 17 + 4 * k;
-                    float v0[3], v1[3], v2[3];
-                    if (!vertex(wgsl_i32(e[0]), v0) || !vertex(wgsl_i32(e[1]), v1) || !vertex(wgsl_i32(e[2]), v2))
-                        return fail(PT_ERR_SCENE, "BVH leaf references a vertex out of range");
-                    const int32_t mat = wgsl_i32(e[3]);
-                    if (mat < 0 || mat >= nobj) return fail(PT_ERR_SCENE, "BVH leaf references a material out of range");
-                    Tri t{};
-                    float e1[3], e2[3];
-                    for (int q = 0; q < 3; ++q) {
-                        e1[q] = v1[q] - v0[q];  // ray-triangle-intersection.wgsl:6
-                        e2[q] = v2[q] - v0[q];  // :7
-                    }
-                    tri_set(t, v0, e1, e2);
-                    t.mat = mat;
-                    t.uid = -1;
-                    L.tris.push_back(t);
-                    {   // vertex normals at vn_start + i (i = (index - 1) * 3, the vertex offsets;
-                        // intersection-logic.wgsl:81-97), reads clamped as Tint's
-                        const int32_t vi[3] = {(wgsl_i32(e[0]) - 1) * 3, (wgsl_i32(e[1]) - 1) * 3, (wgsl_i32(e[2]) - 1) * 3};
-                        const int32_t vn_start = wgsl_i32(tri[5]), vn_range = wgsl_i32(tri[6]);
-                        for (int q = 0; q < 3; ++q)
-                            L.tnorm.push_back(make_float4(P.at(vn_start + vi[q]), P.at(vn_start + vi[q] + 1),
-                                                          P.at(vn_start + vi[q] + 2),
-                                                          (q == 0 && vi[2] < vn_range) ? 1.0f : 0.0f));
-                    }
-                    entry.push_back({wgsl_i32(e[0]), wgsl_i32(e[1]), wgsl_i32(e[2]), mat});
-                }
-                leaf_ranges.emplace_back(refs[side], n);
-                L.info.leaves++;
-                L.info.leaf_refs += (uint32_t)n;
-                L.info.max_leaf = std::max<uint32_t>(L.info.max_leaf, (uint32_t)n);
-            } else {
-                if (L.nodes.size() >= node_cap) return fail(PT_ERR_SCENE, "BVH is not a tree (node count exceeds buffer)");
-                refs[side] = (int32_t)L.nodes.size();
-                cnts[side] = -1;
-                L.nodes.push_back(Node{});
-                work.push_back({c, refs[side], it.depth + 1});
-            }
-        }
-        nd.lref = refs[0]; nd.rref = refs[1]; nd.lcnt = cnts[0]; nd.rcnt = cnts[1];
-        L.nodes[(size_t)it.node] = nd;
-    }
-    L.info.nodes = (uint32_t)L.nodes.size();
-    // Mailboxing: a leaf entry tested twice by one query gives the same t both
-    // times and the closest-hit update is strict-<, so repeats never change the result.  With
-    // at most 64 distinct entries a query keeps the set it has tested in one 64-bit mask.
-    // uids follow first appearance (option mb_uid_order=reverse numbers them backwards: tests
-    // use it to exercise the tie-break of the uid-ordered leaf loop).
-    {
-        std::map<std::array<int32_t, 4>, int32_t> ids;
-        std::vector<int32_t> uid(entry.size());
-        std::vector<size_t> first;
-        for (size_t r = 0; r < entry.size(); ++r) {
-            auto it = ids.find(entry[r]);
-            if (it == ids.end()) {
-                it = ids.emplace(entry[r], (int32_t)first.size()).first;
-                first.push_back(r);
-            }
-            uid[r] = it->second;
-        }
-        const int32_t U = (int32_t)first.size();
-        L.mailbox = U >= 1 && U <= 64;
-        // every record carries its entry's uid (the mailbox scenes renumber below)
-        for (size_t r = 0; r < entry.size(); ++r) L.tris[r].uid = uid[r];
-        if (L.mailbox) {
-            const bool rev = opts_snapshot().is("mb_uid_order", "reverse");
-            for (auto& u : uid) u = rev ? U - 1 - u : u;
-            for (size_t r = 0; r < entry.size(); ++r) L.tris[r].uid = uid[r];
-            L.mb_base = (int32_t)L.tris.size();
-            std::vector<Tri> uniq((size_t)U);
-            for (size_t k = 0; k < first.size(); ++k) uniq[(size_t)uid[first[k]]] = L.tris[first[k]];
-            L.tris.insert(L.tris.end(), uniq.begin(), uniq.end());
-            std::vector<float4> un(3 * (size_t)U);
-            for (size_t k = 0; k < first.size(); ++k)
-                for (int q = 0; q < 3; ++q) un[3 * (size_t)uid[first[k]] + q] = L.tnorm[3 * first[k] + q];
-            L.tnorm.insert(L.tnorm.end(), un.begin(), un.end());
-            L.lmask.assign(std::max<size_t>(1, entry.size()), 0);
-            for (const auto& lr : leaf_ranges)
-                for (int32_t k = 0; k < lr.second; ++k) L.lmask[(size_t)lr.first] |= 1ull << uid[(size_t)(lr.first + k)];
-            // the stackless replay tree (BfNode): internal nodes in the reference's visiting
-            // order — pre-order with the right subtree first — so the next node to visit is always
-            // the smallest-numbered pending one
-            if (U <= 63 && L.nodes.size() <= 64) {
-                std::vector<int32_t> pre(L.nodes.size(), -1);
-                std::vector<int32_t> st{0};
-                int32_t next = 0;
-                while (!st.empty()) {
-                    const int32_t n = st.back();
-                    st.pop_back();
-                    pre[(size_t)n] = next++;
-                    L.bfmap.push_back(n);
-                    const Node& nd = L.nodes[(size_t)n];
-                    if (nd.lcnt < 0) st.push_back(nd.lref);  // popped after the right subtree
-                    if (nd.rcnt < 0) st.push_back(nd.rref);
-                }
-                L.bfnode.resize(L.nodes.size());
-                for (size_t i = 0; i < L.bfmap.size(); ++i) {
-                    const Node& nd = L.nodes[(size_t)L.bfmap[i]];
-                    BfNode& b = L.bfnode[i];
-                    for (int c = 0; c < 3; ++c) { b.lmin[c] = nd.lmin[c]; b.lmax[c] = nd.lmax[c]; b.rmin[c] = nd.rmin[c]; b.rmax[c] = nd.rmax[c]; }
-                    b.lm = nd.lcnt < 0 ? (1ull << 63) | (uint64_t)pre[(size_t)nd.lref] : (nd.lcnt > 0 ? L.lmask[(size_t)nd.lref] : 0ull);
-                    b.rm = nd.rcnt < 0 ? (1ull << 63) | (uint64_t)pre[(size_t)nd.rref] : (nd.rcnt > 0 ? L.lmask[(size_t)nd.rref] : 0ull);
-                }
-                // the narrow payload (pt_layout.h): per child the uid set beneath it in the low word
-                // (children are numbered after their parents, so a backward sweep has every subtree's
-                // union ready), the inner flag and pre-order number in the high word
-                if (U <= kBfNarrowMax && L.nodes.size() <= (size_t)kBfNarrowMax) {
-                    std::vector<uint64_t> below(L.nodes.size(), 0);
-                    auto child_set = [&](int32_t ref, int32_t cnt) {
-                        return cnt < 0 ? below[(size_t)ref] : (cnt > 0 ? L.lmask[(size_t)ref] : 0ull);
-                    };
-                    for (size_t n = L.nodes.size(); n-- > 0;) {
-                        const Node& nd = L.nodes[n];
-                        below[n] = child_set(nd.lref, nd.lcnt) | child_set(nd.rref, nd.rcnt);
-                    }
-                    L.bfnarrow = L.bfnode;
-                    for (size_t i = 0; i < L.bfmap.size(); ++i) {
-                        const Node& nd = L.nodes[(size_t)L.bfmap[i]];
-                        auto word = [&](int32_t ref, int32_t cnt) {
-                            const uint64_t hi = cnt < 0 ? (uint64_t)(kBfNarrowInner | (uint32_t)pre[(size_t)ref]) : 0ull;
-                            return hi << 32 | (child_set(ref, cnt) & 0xffffffffull);
-                        };
-                        L.bfnarrow[i].lm = word(nd.lref, nd.lcnt);
-                        L.bfnarrow[i].rm = word(nd.rref, nd.rcnt);
-                    }
-                }
-            }
-        }
-    }
-    // Leaf BVHs (pt_leafbvh.cpp): every leaf of at least leaf_bvh entries (option, read here;
-    // default kLeafBvhDefault, 0 = none).  The leaf's first record holds root + 1, its second the
-    // end of its nodes (Tri::lbvh).  The lean traversal's big-leaf step walks them (mailbox scenes:
-    // only with option mailbox=0, their default kernels test every entry once per ray anyway).
-    {
-        const long lmin = opts_snapshot().num("leaf_bvh", kLeafBvhDefault);
-        if (lmin >= 2) {
-            L.leaf_min = (int32_t)std::min<long>(lmin, INT32_MAX);
-            std::sort(leaf_ranges.begin(), leaf_ranges.end());
-            for (const auto& lr : leaf_ranges) {
-                if (lr.second < L.leaf_min || L.lidx.size() + (size_t)lr.second >= (1u << 24)) continue;
-                int32_t root = 0, end = 0;
-                const size_t slot0 = L.lidx.size();
-                build_leaf_bvh(L.tris.data(), lr.first, lr.second, L.lnodes, L.lidx, root, end);
-                for (size_t j = slot0; j < L.lidx.size(); ++j) {
-                    Tri t = L.tris[(size_t)(lr.first + L.lidx[j])];
-                    t.lbvh = L.lidx[j];
-                    L.ltris.push_back(t);
-                }
-                L.tris[(size_t)lr.first].lbvh = root + 1;
-                L.tris[(size_t)lr.first + 1].lbvh = end;
-                L.lleaves.push_back({lr.first, lr.second, end - root});
-            }
-            if (L.lleaves.empty()) L.leaf_min = 0;
-        }
-    }
-    // Leaves that k_wf_leafpass can resolve before the traversal: the kMaxPre largest, each with its
-    // path of child boxes from the root (node << 1 | side per step; PreLeaf)
-    {
-        std::vector<PreLeaf> all;
-        // iterative pre-order walk keeping the path: (node, depth) frames, path[depth] = the step in
-        std::vector<std::pair<int32_t, std::vector<int32_t>>> st;
-        st.push_back({0, {}});
-        bool deep = false;
-        while (!st.empty()) {
-            auto fr = std::move(st.back());
-            st.pop_back();
-            const Node& nd = L.nodes[(size_t)fr.first];
-            for (int side = 1; side >= 0; --side) {
-                const int32_t cnt = side ? nd.rcnt : nd.lcnt, ref = side ? nd.rref : nd.lref;
-                std::vector<int32_t> p2 = fr.second;
-                p2.push_back(fr.first << 1 | side);
-                if (cnt >= 0) {
-                    if (cnt == 0) continue;
-                    L.leaf_sizes.push_back(cnt);
-                    if ((int)p2.size() > kMaxPrePath) { deep = true; continue; }
-                    PreLeaf pl{};
-                    pl.rec0 = ref;
-                    pl.n = cnt;
-                    pl.npath = (int32_t)p2.size();
-                    for (size_t k = 0; k < p2.size(); ++k) pl.path[k] = p2[k];
-                    all.push_back(pl);
-                } else if (ref >= 0 && (size_t)ref < L.nodes.size()) {
-                    st.push_back({ref, std::move(p2)});
-                }
-            }
-        }
-        std::sort(L.leaf_sizes.begin(), L.leaf_sizes.end(), std::greater<int32_t>());
-        std::sort(all.begin(), all.end(), [](const PreLeaf& a, const PreLeaf& b) { return a.n > b.n || (a.n == b.n && a.rec0 < b.rec0); });
-        if (!deep) {  // (a leaf below kMaxPrePath steps could be among the largest: no table then)
-            for (size_t k = 0; k < all.size() && k < (size_t)kMaxPre; ++k) L.pre.push_back(all[k]);
-        }
-        // the leaf pass's own chunks (kPassChunkMax entries) of the leaves that have traversal chunks
-        std::vector<int32_t> plidx;
-        for (PreLeaf& pl : L.pre) {
-            pl.c0 = pl.c1 = 0;
-            if (L.leaf_min <= 0 || pl.n < L.leaf_min || L.ptris.size() + (size_t)pl.n >= (1u << 24)) continue;
-            const size_t slot0 = plidx.size();
-            int32_t root = 0, end = 0;
-            build_leaf_bvh(L.tris.data(), pl.rec0, pl.n, L.pnodes, plidx, root, end, nullptr, PT_PASS_LEAF, PT_PASS_MERGE);
-            for (size_t j = slot0; j < plidx.size(); ++j) {
-                Tri t = L.tris[(size_t)(pl.rec0 + plidx[j])];
-                t.lbvh = plidx[j];
-                L.ptris.push_back(t);
-                // the entry's normal in double, rounded (the pass's check allows 1e-5 for it)
-                const double e1[3] = {t.q0[3], t.q1[0], t.q1[1]}, e2[3] = {t.q1[2], t.q1[3], t.e2z};
-                const double nv[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2],
-                                      e1[0] * e2[1] - e1[1] * e2[0]};
-                const double ln = std::sqrt(nv[0] * nv[0] + nv[1] * nv[1] + nv[2] * nv[2]);
-                const bool ok = ln > 0.0 && std::isfinite(ln);
-                L.pnorm.push_back(make_float4(ok ? (float)(nv[0] / ln) : 0.0f, ok ? (float)(nv[1] / ln) : 0.0f,
-                                              ok ? (float)(nv[2] / ln) : 0.0f, 0.0f));
-            }
-            pl.c0 = root;
-            pl.c1 = end;
-        }
-        // the pass's check takes A and B times 1.00001 (pt_leafpass.hip pass_box_skip), rounded up;
-        // a degenerate chunk's FLT_MAX stays (its delta is never bounded)
-        for (LNode& nd : L.pnodes) {
-            auto up5 = [](float v) {
-                return v >= FLT_MAX ? v : std::nextafter((float)((double)v * 1.00001), FLT_MAX);
-            };
-            nd.A = up5(nd.A);
-            nd.B = up5(nd.B);
-        }
-    }
-    // Leaf remainders (pt_leafskip.cpp; option leaf_skip, read here and per render, default on):
-    // scenes without mailbox (their kernels test every distinct entry once per ray anyway)
-    if (!L.mailbox && opts_snapshot().flag("leaf_skip", 1) != 0)
-        build_leaf_skips(L.nodes, L.tris, L.tnorm, L.lights, kLeafSkipMaxLeaf, kLeafSkipProbeTests, L.nalt, &L.skip);
-    // |det| = |e1 . (d x e2)| <= |e1| |e2| |d| with |d| = 1 (every ray direction is normalised or
-    // a reflection/refraction of unit vectors; non-finite ones give no hit on either path)
-    double emax = 0.0;
-    bool finite = true;
-    for (const Tri& t : L.tris) {
-        const double e1[3] = {t.q0[3], t.q1[0], t.q1[1]}, e2[3] = {t.q1[2], t.q1[3], t.e2z};
-        const double a = std::sqrt(e1[0] * e1[0] + e1[1] * e1[1] + e1[2] * e1[2]);
-        const double b = std::sqrt(e2[0] * e2[0] + e2[1] * e2[1] + e2[2] * e2[2]);
-        finite = finite && std::isfinite(a) && std::isfinite(b);
-        emax = std::max(emax, a * b);
-    }
-    L.fast_rcp = finite && emax < std::ldexp(1.0, 124);
-    // The device stack parks at most one left child per internal ancestor.
-    L.info.max_stack = max_depth + 1;
-    if (L.info.max_stack >= (uint32_t)kStackMax) return fail(PT_ERR_SCENE, "BVH deeper than the device traversal stack");
-
-    // Light table (intersection-logic.wgsl:217-285): entry k for k in [0, Ntri].
-    int32_t es[4], ee[4], n[4];
-    int32_t ntri = 0;
-    for (int s = 0; s < 4; ++s) {
-        es[s] = wgsl_i32(tri[8 + 2 * s]);
-        ee[s] = wgsl_i32(tri[9 + 2 * s]);
-        n[s] = (es[s] != -1) ? (ee[s] - es[s]) / 4 : 0;
-        ntri += n[s];
-    }
-    if (ntri <= 0) return fail(PT_ERR_SCENE, "scene has no emissive triangles (sample_area_lights needs one)");
-    L.ntri = ntri;
-    const int32_t vs = wgsl_i32(P.at(2));
-    for (int32_t k = 0; k <= ntri; ++k) {
-        int32_t idx;
-        if (k < n[0]) idx = k * 4 + es[0];
-        else if (k < n[0] + n[1]) idx = (k - n[0]) * 4 + es[1];
-        else if (k < n[0] + n[1] + n[2]) idx = (k - n[0] - n[1]) * 4 + es[2];
-        else idx = (k - n[0] - n[1] - n[2]) * 4 + es[3];
-        Light lt{};
-        float* dst[3] = {lt.p0, lt.p1, lt.p2};
-        for (int j = 0; j < 3; ++j) {
-            const int32_t i = (wgsl_i32(P.at(idx + j)) - 1) * 3;
-            for (int c = 0; c < 3; ++c) dst[j][c] = P.at(vs + i + c);
-        }
-        L.lights.push_back(lt);
-    }
-    L.info.emissive_tris = (uint32_t)ntri;
-    return PT_OK;
-}
 
 size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
@@ -568,6 +157,20 @@ const char* pt_build_id(void) { return PT_SOURCE_HASH; }
 
 }  // extern "C"
 
+// A device scratch buffer kept with the scene and grown on demand (cap: T's)
+template <class T>
+struct Scratch {
+    T* p = nullptr;
+    size_t cap = 0;
+    int ensure(size_t n, const char* what) {
+        if (cap >= n) return PT_OK;
+        free();
+        if (hipMalloc(reinterpret_cast<void**>(&p), n * sizeof(T)) != hipSuccess) return fail(PT_ERR_NOMEM, std::string("hipMalloc ") + what);
+        cap = n;
+        return PT_OK;
+    }
+    void free() { if (p) hipFree(p); p = nullptr; cap = 0; }
+};
 
 struct pt_scene {
     int device = 0;
@@ -575,23 +178,17 @@ struct pt_scene {
     SceneView view{};
     pt_scene_info info{};
     hipStream_t stream = nullptr;
-    float* d_accum = nullptr;  // scratch for the blocking host-buffer calls
-    size_t accum_cap = 0;
+    Scratch<float> d_accum;  // scratch for the blocking host-buffer calls
     Counters* d_counters = nullptr;
     void* d_wf = nullptr;  // wavefront path state, allocated on first use
     WfBuffers wf{};
     bool prof_on = false;  // pt_profile_enable
     KernelProfiler prof;
-    uint8_t* d_rgba = nullptr;  // pt_render_image scratch
-    size_t rgba_cap = 0;
+    Scratch<uint8_t> d_rgba;  // pt_render_image scratch
     // scratch of the blocking moments, noise and adaptive calls: second moments, per-tile mean (floats),
     // tile verdicts followed by tile frame counts (bytes)
-    float* d_m2 = nullptr;
-    size_t m2_cap = 0;
-    float* d_mean = nullptr;
-    size_t mean_cap = 0;
-    void* d_tiles = nullptr;
-    size_t tiles_cap = 0;
+    Scratch<float> d_m2, d_mean;
+    Scratch<char> d_tiles;
     WfStreams ws;  // dual-stream wavefront: aux stream + fork/join events (created with d_wf)
     // pinned mirror of the wavefront control words, copied after every wavefront render on its
     // stream: a watchdog flag set by an asynchronous render surfaces once that copy has landed
@@ -599,8 +196,7 @@ struct pt_scene {
     uint32_t* h_ctl = nullptr;
     float* d_rad = nullptr;  // radiance of finished wavefront paths (ensure_rad)
     uint64_t rad_cap = 0;
-    float* d_peer = nullptr;  // pt_render_multi (ordered reduction): another device's partial accumulator
-    size_t peer_cap = 0;
+    Scratch<float> d_peer;  // pt_render_multi (ordered reduction): another device's partial accumulator
     int32_t leaf_min = 0;  // leaf BVHs: leaves of at least this many entries have one (0: none)
     std::vector<std::array<int32_t, 3>> lleaves;  // (first record, entries, nodes) per leaf BVH
     // big leaves resolved before the traversal (k_wf_leafpass): the table (device copy in d_mem at
@@ -659,6 +255,13 @@ void KernelProfiler::destroy() {
     pool.clear();
 }
 }  // namespace pt
+
+namespace {
+struct ProfScope {  // attach the scene's profiler to this thread for the launches of its scope
+    explicit ProfScope(pt_scene* s) { t_prof = s->prof_on ? &s->prof : nullptr; }
+    ~ProfScope() { t_prof = nullptr; }
+};
+}  // namespace
 
 extern "C" {
 
@@ -759,57 +362,33 @@ int pt_scene_create(const float* triangle_data, size_t triangle_len, const float
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(PT_ERR_NODEVICE, "no HIP device visible");
     if (device < 0 || device >= ndev) return fail(PT_ERR_NODEVICE, "device ordinal out of range");
+    const Opts o = opts_snapshot();
+    LayoutOptions lo;
+    lo.uid_reverse = o.is("mb_uid_order", "reverse");
+    lo.leaf_bvh = o.num("leaf_bvh", lo.leaf_bvh);
+    lo.leaf_skip = o.flag("leaf_skip", 1) != 0;
     HostLayout L;
-    int rc = build_layout(triangle_data, triangle_len, bvh_data, bvh_len, L);
-    if (rc != PT_OK) return rc;
+    std::string err;
+    const int rc = build_layout(triangle_data, triangle_len, bvh_data, bvh_len, lo, L, err);
+    if (rc != PT_OK) return fail(rc, err);
     HIP_TRY(hipSetDevice(device));
-    const size_t o_nodes = 0;
-    const size_t o_tris = align_up(o_nodes + L.nodes.size() * sizeof(Node), 256);
-    const size_t o_mats = align_up(o_tris + std::max<size_t>(1, L.tris.size()) * sizeof(Tri), 256);
-    const size_t o_lights = align_up(o_mats + L.mats.size() * sizeof(Material), 256);
-    const size_t o_lmask = align_up(o_lights + L.lights.size() * sizeof(Light), 16);
-    const size_t o_bfnode = align_up(o_lmask + L.lmask.size() * sizeof(uint64_t), 16);
-    const size_t o_bfmap = align_up(o_bfnode + L.bfnode.size() * sizeof(BfNode), 16);
-    const size_t o_bfnarrow = align_up(o_bfmap + L.bfmap.size() * sizeof(int32_t), 16);
-    const size_t span_end = o_bfnarrow + L.bfnarrow.size() * sizeof(BfNode);  // the LDS span ends here
-    const size_t o_cnt = align_up(span_end, 256);
-    const size_t o_tn = align_up(o_cnt + sizeof(Counters), 256);
-    const size_t o_lnode = align_up(o_tn + std::max<size_t>(1, L.tnorm.size()) * sizeof(float4), 256);
-    const size_t o_lidx = align_up(o_lnode + L.lnodes.size() * sizeof(LNode), 256);
-    const size_t o_pnode = align_up(o_lidx + std::max<size_t>(1, L.ltris.size()) * sizeof(Tri), 256);
-    const size_t o_ptris = align_up(o_pnode + std::max<size_t>(1, L.pnodes.size()) * sizeof(LNode), 256);
-    const size_t o_pnorm = align_up(o_ptris + std::max<size_t>(1, L.ptris.size()) * sizeof(Tri), 256);
-    const size_t o_pre = align_up(o_pnorm + std::max<size_t>(1, L.pnorm.size()) * sizeof(float4), 256);
-    const size_t o_nalt = align_up(o_pre + std::max<size_t>(1, L.pre.size()) * sizeof(PreLeaf), 256);
-    const size_t total = align_up(o_nalt + std::max<size_t>(2, L.nalt.size()) * sizeof(int2), 256);
+    const ScenePlan plan = plan_sections(L, sizeof(Counters));
     pt_scene* s = new pt_scene();
     s->device = device;
-    if (hipMalloc(&s->d_mem, total) != hipSuccess) { delete s; return fail(PT_ERR_NOMEM, "hipMalloc scene"); }
+    if (hipMalloc(&s->d_mem, plan.total) != hipSuccess) { delete s; return fail(PT_ERR_NOMEM, "hipMalloc scene"); }
     char* base = static_cast<char*>(s->d_mem);
-    auto up = [&](size_t off, const void* src, size_t bytes) { return bytes ? hipMemcpy(base + off, src, bytes, hipMemcpyHostToDevice) : hipSuccess; };
-    if (up(o_nodes, L.nodes.data(), L.nodes.size() * sizeof(Node)) != hipSuccess ||
-        up(o_tris, L.tris.data(), L.tris.size() * sizeof(Tri)) != hipSuccess ||
-        up(o_mats, L.mats.data(), L.mats.size() * sizeof(Material)) != hipSuccess ||
-        up(o_lights, L.lights.data(), L.lights.size() * sizeof(Light)) != hipSuccess ||
-        up(o_lmask, L.lmask.data(), L.lmask.size() * sizeof(uint64_t)) != hipSuccess ||
-        up(o_bfnode, L.bfnode.data(), L.bfnode.size() * sizeof(BfNode)) != hipSuccess ||
-        up(o_bfmap, L.bfmap.data(), L.bfmap.size() * sizeof(int32_t)) != hipSuccess ||
-        up(o_bfnarrow, L.bfnarrow.data(), L.bfnarrow.size() * sizeof(BfNode)) != hipSuccess ||
-        up(o_tn, L.tnorm.data(), L.tnorm.size() * sizeof(float4)) != hipSuccess ||
-        up(o_lnode, L.lnodes.data(), L.lnodes.size() * sizeof(LNode)) != hipSuccess ||
-        up(o_lidx, L.ltris.data(), L.ltris.size() * sizeof(Tri)) != hipSuccess ||
-        up(o_pnode, L.pnodes.data(), L.pnodes.size() * sizeof(LNode)) != hipSuccess ||
-        up(o_ptris, L.ptris.data(), L.ptris.size() * sizeof(Tri)) != hipSuccess ||
-        up(o_pnorm, L.pnorm.data(), L.pnorm.size() * sizeof(float4)) != hipSuccess ||
-        up(o_pre, L.pre.data(), L.pre.size() * sizeof(PreLeaf)) != hipSuccess ||
-        up(o_nalt, L.nalt.data(), L.nalt.size() * sizeof(int2)) != hipSuccess) {
-        pt_scene_destroy(s);
-        return fail(PT_ERR_HIP, "scene upload failed");
-    }
-    s->view.nodes = reinterpret_cast<const Node*>(base + o_nodes);
-    s->view.tris = reinterpret_cast<const Tri*>(base + o_tris);
-    s->view.mats = reinterpret_cast<const Material*>(base + o_mats);
-    s->view.lights = reinterpret_cast<const Light*>(base + o_lights);
+    for (const auto& sec : plan.sec)
+        if (sec.bytes && hipMemcpy(base + sec.off, sec.src, sec.bytes, hipMemcpyHostToDevice) != hipSuccess) {
+            pt_scene_destroy(s);
+            return fail(PT_ERR_HIP, "scene upload failed");
+        }
+    // a section's device address (nullptr where the scene has none of it) and its offset from the nodes
+    auto at = [&](Section k, bool have = true) -> const void* { return have ? base + plan.sec[k].off : nullptr; };
+    auto off = [&](Section k) { return (uint32_t)plan.sec[k].off; };
+    s->view.nodes = static_cast<const Node*>(at(SEC_NODES));
+    s->view.tris = static_cast<const Tri*>(at(SEC_TRIS));
+    s->view.mats = static_cast<const Material*>(at(SEC_MATS));
+    s->view.lights = static_cast<const Light*>(at(SEC_LIGHTS));
     s->view.n_nodes = (int32_t)L.nodes.size();
     s->view.n_tris = (int32_t)L.tris.size();
     s->view.n_mats = (int32_t)L.mats.size();
@@ -820,20 +399,20 @@ int pt_scene_create(const float* triangle_data, size_t triangle_len, const float
     s->view.fast_rcp = L.fast_rcp ? 1 : 0;
     s->view.node_bias = 0;  // per-pipeline default (launch_wavefront / launch_megakernel)
     s->view.node_steps = 0;  // per-pipeline default (launch_wavefront / launch_megakernel)
-    s->view.off_tris = (uint32_t)(o_tris - o_nodes);
-    s->view.off_mats = (uint32_t)(o_mats - o_nodes);
-    s->view.off_lights = (uint32_t)(o_lights - o_nodes);
-    s->view.off_lmask = (uint32_t)(o_lmask - o_nodes);
-    s->view.lmask = reinterpret_cast<const uint64_t*>(base + o_lmask);
+    s->view.off_tris = off(SEC_TRIS);
+    s->view.off_mats = off(SEC_MATS);
+    s->view.off_lights = off(SEC_LIGHTS);
+    s->view.off_lmask = off(SEC_LMASK);
+    s->view.lmask = static_cast<const uint64_t*>(at(SEC_LMASK));
     s->view.mailbox = L.mailbox ? 1 : 0;
-    s->view.tnorm = reinterpret_cast<const float4*>(base + o_tn);
+    s->view.tnorm = static_cast<const float4*>(at(SEC_TNORM));
     s->view.vnormals = 0;
-    s->view.lnodes = L.lnodes.empty() ? nullptr : reinterpret_cast<const LNode*>(base + o_lnode);
-    s->view.ltris = L.lnodes.empty() ? nullptr : reinterpret_cast<const Tri*>(base + o_lidx);
-    s->view.pnodes = L.pnodes.empty() ? nullptr : reinterpret_cast<const LNode*>(base + o_pnode);
-    s->view.ptris = L.pnodes.empty() ? nullptr : reinterpret_cast<const Tri*>(base + o_ptris);
-    s->view.pnorm = L.pnodes.empty() ? nullptr : reinterpret_cast<const float4*>(base + o_pnorm);
-    s->view.nalt = L.nalt.empty() ? nullptr : reinterpret_cast<const int4*>(base + o_nalt);
+    s->view.lnodes = static_cast<const LNode*>(at(SEC_LNODES, !L.lnodes.empty()));
+    s->view.ltris = static_cast<const Tri*>(at(SEC_LTRIS, !L.lnodes.empty()));
+    s->view.pnodes = static_cast<const LNode*>(at(SEC_PNODES, !L.pnodes.empty()));
+    s->view.ptris = static_cast<const Tri*>(at(SEC_PTRIS, !L.pnodes.empty()));
+    s->view.pnorm = static_cast<const float4*>(at(SEC_PNORM, !L.pnodes.empty()));
+    s->view.nalt = static_cast<const int4*>(at(SEC_NALT, !L.nalt.empty()));
     s->leaf_min = L.leaf_min;
     s->lleaves = L.lleaves;
     s->pre = L.pre;
@@ -843,18 +422,18 @@ int pt_scene_create(const float* triangle_data, size_t triangle_len, const float
         s->h_lights.assign(L.lights.begin(), L.lights.begin() + std::min<size_t>(L.lights.size(), L.info.emissive_tris));
     }
     s->leaf_sizes = L.leaf_sizes;
-    s->d_pre = L.pre.empty() ? nullptr : reinterpret_cast<const PreLeaf*>(base + o_pre);
+    s->d_pre = static_cast<const PreLeaf*>(at(SEC_PRE, !L.pre.empty()));
     s->view.mb_base = L.mb_base;
-    s->view.bfnode = L.bfnode.empty() ? nullptr : reinterpret_cast<const BfNode*>(base + o_bfnode);
-    s->view.bfmap = L.bfmap.empty() ? nullptr : reinterpret_cast<const int32_t*>(base + o_bfmap);
-    s->view.off_bfnode = (uint32_t)(o_bfnode - o_nodes);
-    s->view.off_bfmap = (uint32_t)(o_bfmap - o_nodes);
-    s->view.bfnarrow = L.bfnarrow.empty() ? nullptr : reinterpret_cast<const BfNode*>(base + o_bfnarrow);
-    s->view.off_bfnarrow = (uint32_t)(o_bfnarrow - o_nodes);
-    s->view.span_bytes = (uint32_t)align_up(span_end - o_nodes, 16);
-    s->d_counters = reinterpret_cast<Counters*>(base + o_cnt);
+    s->view.bfnode = static_cast<const BfNode*>(at(SEC_BFNODE, !L.bfnode.empty()));
+    s->view.bfmap = static_cast<const int32_t*>(at(SEC_BFMAP, !L.bfmap.empty()));
+    s->view.off_bfnode = off(SEC_BFNODE);
+    s->view.off_bfmap = off(SEC_BFMAP);
+    s->view.bfnarrow = static_cast<const BfNode*>(at(SEC_BFNARROW, !L.bfnarrow.empty()));
+    s->view.off_bfnarrow = off(SEC_BFNARROW);
+    s->view.span_bytes = (uint32_t)align_up(plan.span_end, 16);
+    s->d_counters = reinterpret_cast<Counters*>(base + plan.off_counters);
     s->info = L.info;
-    s->info.device_bytes = total;
+    s->info.device_bytes = plan.total;
     *scene_out = s;
     return PT_OK;
 }
@@ -863,7 +442,6 @@ void pt_scene_destroy(pt_scene* s) {
     if (!s) return;
     hipSetDevice(s->device);
     if (s->stream) { hipStreamSynchronize(s->stream); hipStreamDestroy(s->stream); }
-    if (s->d_accum) hipFree(s->d_accum);
     if (s->d_wf) hipFree(s->d_wf);
     for (int h = 0; h < kMaxParts; ++h) {
         if (s->ws.aux[h]) { hipStreamSynchronize(s->ws.aux[h]); hipStreamDestroy(s->ws.aux[h]); }
@@ -872,11 +450,7 @@ void pt_scene_destroy(pt_scene* s) {
     if (s->ws.fork) hipEventDestroy(s->ws.fork);
     if (s->d_rad) hipFree(s->d_rad);
     if (s->d_pres) hipFree(s->d_pres);
-    if (s->d_peer) hipFree(s->d_peer);
-    if (s->d_rgba) hipFree(s->d_rgba);
-    if (s->d_m2) hipFree(s->d_m2);
-    if (s->d_mean) hipFree(s->d_mean);
-    if (s->d_tiles) hipFree(s->d_tiles);
+    s->d_accum.free(); s->d_m2.free(); s->d_mean.free(); s->d_peer.free(); s->d_rgba.free(); s->d_tiles.free();
     if (s->h_ctl) hipHostFree(s->h_ctl);
     if (s->d_mem) hipFree(s->d_mem);
     s->prof.destroy();
@@ -1242,10 +816,7 @@ int render_impl(pt_scene* s, const float* meta, uint32_t frame0, uint32_t nframe
     HIP_TRY(hipSetDevice(s->device));
     if (nframes == 0) return PT_OK;
     const uint64_t npix = (uint64_t)fp.win_w * fp.win_h;  // paths per frame: the window's
-    struct ProfScope {  // attach the scene's profiler to this thread for the launches below
-        explicit ProfScope(KernelProfiler* p) { t_prof = p; }
-        ~ProfScope() { t_prof = nullptr; }
-    } prof_scope(s->prof_on ? &s->prof : nullptr);
+    ProfScope prof_scope(s);
     const Opts o = opts_snapshot();
     const uint64_t paths = npix * (accum ? nframes : 1);
     SceneView view;
@@ -1286,28 +857,6 @@ int render_impl(pt_scene* s, const float* meta, uint32_t frame0, uint32_t nframe
         return PT_OK;
     }
     HIP_TRY(launch_megakernel(lo, view, fp, frame0, nframes, stride, accum, d_cnt != nullptr, d_out, d_cnt, stream, d_m2));
-    return PT_OK;
-}
-
-int ensure_accum(pt_scene* s, size_t n) {
-    if (s->accum_cap >= n) return PT_OK;
-    if (s->d_accum) hipFree(s->d_accum);
-    s->d_accum = nullptr;
-    s->accum_cap = 0;
-    if (hipMalloc(&s->d_accum, n * sizeof(float)) != hipSuccess) return fail(PT_ERR_NOMEM, "hipMalloc accumulator");
-    s->accum_cap = n;
-    return PT_OK;
-}
-
-// a scratch buffer of at least n units (T's), grown like ensure_accum
-template <class T>
-int ensure_scratch(T*& p, size_t& cap, size_t n, const char* what) {
-    if (cap >= n) return PT_OK;
-    if (p) hipFree(p);
-    p = nullptr;
-    cap = 0;
-    if (hipMalloc(reinterpret_cast<void**>(&p), n * sizeof(T)) != hipSuccess) return fail(PT_ERR_NOMEM, std::string("hipMalloc ") + what);
-    cap = n;
     return PT_OK;
 }
 
@@ -1385,9 +934,6 @@ int pt_render_async(pt_scene* s, const float meta[48], uint32_t frame0, uint32_t
                        reinterpret_cast<Counters*>(d_counters), static_cast<hipStream_t>(stream));
 }
 
-// After a synchronised call: a trace wave that hit kTraceWatchdog left a flag (cleared here).
-static int check_watchdog(pt_scene* s) { return take_watchdog(s); }
-
 int pt_scene_check(pt_scene* s) {
     if (!s) return fail(PT_ERR_INVALID, "null scene");
     HIP_TRY(hipSetDevice(s->device));
@@ -1406,6 +952,41 @@ static int blocking_stream(pt_scene* s) {
     return PT_OK;
 }
 
+// The blocking render calls' body: the window's accumulators from the host (pt_render_image: zeroed;
+// a frame, accumulate false: neither), the render, the results back to the host — accum, or rgba
+// (nullable: the tone-mapped image instead), m2 and counters (nullable) — one synchronisation, and
+// the watchdog (a trace wave that hit kTraceWatchdog left a flag, cleared here).
+static int render_blocking(pt_scene* s, const float* meta, const pt_window* win, uint32_t frame0, uint32_t nframes,
+                           uint32_t stride, int max_depth, int mode, bool accumulate, float* accum, float* m2,
+                           uint8_t* rgba, pt_counters* counters) {
+    FrameParams fp{};
+    int rc = make_params(meta, max_depth, fp, win);
+    if (rc != PT_OK) return rc;
+    const size_t npix = (size_t)fp.win_w * fp.win_h, n = 3 * npix;
+    HIP_TRY(hipSetDevice(s->device));
+    if ((rc = s->d_accum.ensure(n, "accumulator")) != PT_OK || (m2 && (rc = s->d_m2.ensure(n, "second moments")) != PT_OK) ||
+        (rc = blocking_stream(s)) != PT_OK || (rgba && (rc = s->d_rgba.ensure(4 * npix, "image")) != PT_OK))
+        return rc;
+    Counters* d_cnt = counters ? s->d_counters : nullptr;
+    if (rgba) HIP_TRY(hipMemsetAsync(s->d_accum.p, 0, n * sizeof(float), s->stream));
+    else if (accumulate) HIP_TRY(hipMemcpyAsync(s->d_accum.p, accum, n * sizeof(float), hipMemcpyHostToDevice, s->stream));
+    if (m2) HIP_TRY(hipMemcpyAsync(s->d_m2.p, m2, n * sizeof(float), hipMemcpyHostToDevice, s->stream));
+    if (d_cnt) HIP_TRY(hipMemsetAsync(d_cnt, 0, sizeof(Counters), s->stream));
+    rc = render_impl(s, meta, frame0, nframes, stride, max_depth, mode, accumulate, s->d_accum.p, d_cnt, s->stream, win,
+                     nullptr, m2 ? s->d_m2.p : nullptr);
+    if (rc != PT_OK) return rc;
+    if (rgba) {
+        if ((rc = pt_tonemap_async(s, s->d_accum.p, npix, nframes, s->d_rgba.p, s->stream)) != PT_OK) return rc;
+        HIP_TRY(hipMemcpyAsync(rgba, s->d_rgba.p, 4 * npix, hipMemcpyDeviceToHost, s->stream));
+    } else {
+        HIP_TRY(hipMemcpyAsync(accum, s->d_accum.p, n * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+    }
+    if (m2) HIP_TRY(hipMemcpyAsync(m2, s->d_m2.p, n * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+    if (d_cnt) HIP_TRY(hipMemcpyAsync(counters, d_cnt, sizeof(Counters), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return take_watchdog(s);
+}
+
 int pt_render(pt_scene* s, const float meta[48], uint32_t frame0, uint32_t nframes, uint32_t frame_stride,
               int max_depth, int mode, float* accum, pt_counters* counters) {
     return pt_render_window(s, meta, nullptr, frame0, nframes, frame_stride, max_depth, mode, accum, counters);
@@ -1414,21 +995,7 @@ int pt_render(pt_scene* s, const float meta[48], uint32_t frame0, uint32_t nfram
 int pt_render_window(pt_scene* s, const float meta[48], const pt_window* win, uint32_t frame0, uint32_t nframes,
                      uint32_t frame_stride, int max_depth, int mode, float* accum, pt_counters* counters) {
     if (!s || !accum || !meta) return fail(PT_ERR_INVALID, "null argument");
-    FrameParams fp{};
-    int rc = make_params(meta, max_depth, fp, win);
-    if (rc != PT_OK) return rc;
-    const size_t n = (size_t)fp.win_w * fp.win_h * 3;
-    HIP_TRY(hipSetDevice(s->device));
-    if ((rc = ensure_accum(s, n)) != PT_OK || (rc = blocking_stream(s)) != PT_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(s->d_accum, accum, n * sizeof(float), hipMemcpyHostToDevice, s->stream));
-    if (counters) HIP_TRY(hipMemsetAsync(s->d_counters, 0, sizeof(Counters), s->stream));
-    rc = render_impl(s, meta, frame0, nframes, frame_stride, max_depth, mode, true, s->d_accum,
-                     counters ? s->d_counters : nullptr, s->stream, win);
-    if (rc != PT_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(accum, s->d_accum, n * sizeof(float), hipMemcpyDeviceToHost, s->stream));
-    if (counters) HIP_TRY(hipMemcpyAsync(counters, s->d_counters, sizeof(Counters), hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    return check_watchdog(s);
+    return render_blocking(s, meta, win, frame0, nframes, frame_stride, max_depth, mode, true, accum, nullptr, nullptr, counters);
 }
 
 int pt_render_moments_async(pt_scene* s, const float meta[48], const pt_window* win, uint32_t frame0, uint32_t nframes,
@@ -1442,25 +1009,7 @@ int pt_render_moments_async(pt_scene* s, const float meta[48], const pt_window* 
 int pt_render_moments(pt_scene* s, const float meta[48], const pt_window* win, uint32_t frame0, uint32_t nframes,
                       uint32_t frame_stride, int max_depth, int mode, float* accum, float* m2, pt_counters* counters) {
     if (!s || !accum || !m2 || !meta) return fail(PT_ERR_INVALID, "null argument");
-    FrameParams fp{};
-    int rc = make_params(meta, max_depth, fp, win);
-    if (rc != PT_OK) return rc;
-    const size_t n = (size_t)fp.win_w * fp.win_h * 3;
-    HIP_TRY(hipSetDevice(s->device));
-    if ((rc = ensure_accum(s, n)) != PT_OK || (rc = ensure_scratch(s->d_m2, s->m2_cap, n, "second moments")) != PT_OK ||
-        (rc = blocking_stream(s)) != PT_OK)
-        return rc;
-    HIP_TRY(hipMemcpyAsync(s->d_accum, accum, n * sizeof(float), hipMemcpyHostToDevice, s->stream));
-    HIP_TRY(hipMemcpyAsync(s->d_m2, m2, n * sizeof(float), hipMemcpyHostToDevice, s->stream));
-    if (counters) HIP_TRY(hipMemsetAsync(s->d_counters, 0, sizeof(Counters), s->stream));
-    rc = render_impl(s, meta, frame0, nframes, frame_stride, max_depth, mode, true, s->d_accum,
-                     counters ? s->d_counters : nullptr, s->stream, win, nullptr, s->d_m2);
-    if (rc != PT_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(accum, s->d_accum, n * sizeof(float), hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipMemcpyAsync(m2, s->d_m2, n * sizeof(float), hipMemcpyDeviceToHost, s->stream));
-    if (counters) HIP_TRY(hipMemcpyAsync(counters, s->d_counters, sizeof(Counters), hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    return check_watchdog(s);
+    return render_blocking(s, meta, win, frame0, nframes, frame_stride, max_depth, mode, true, accum, m2, nullptr, counters);
 }
 
 int pt_noise_tiles_async(pt_scene* s, const float* d_accum, const float* d_m2, uint32_t w, uint32_t h, size_t row_pitch,
@@ -1471,10 +1020,7 @@ int pt_noise_tiles_async(pt_scene* s, const float* d_accum, const float* d_m2, u
     int rc = make_grid(w, h, row_pitch, tile_w, tile_h, g);
     if (rc != PT_OK || (rc = check_tol(tol, floor)) != PT_OK) return rc;
     HIP_TRY(hipSetDevice(s->device));
-    struct ProfScope {
-        explicit ProfScope(KernelProfiler* p) { t_prof = p; }
-        ~ProfScope() { t_prof = nullptr; }
-    } prof_scope(s->prof_on ? &s->prof : nullptr);
+    ProfScope prof_scope(s);
     HIP_TRY(launch_noise_tiles(d_accum, d_m2, g, d_frames, tol, floor, reinterpret_cast<TileNoise*>(d_out),
                                static_cast<hipStream_t>(stream)));
     return PT_OK;
@@ -1487,22 +1033,17 @@ int pt_tile_mean_async(pt_scene* s, const float* d_accum, uint32_t w, uint32_t h
     const int rc = make_grid(w, h, row_pitch, tile_w, tile_h, g);
     if (rc != PT_OK) return rc;
     HIP_TRY(hipSetDevice(s->device));
-    struct ProfScope {
-        explicit ProfScope(KernelProfiler* p) { t_prof = p; }
-        ~ProfScope() { t_prof = nullptr; }
-    } prof_scope(s->prof_on ? &s->prof : nullptr);
+    ProfScope prof_scope(s);
     HIP_TRY(launch_tile_mean(d_accum, g, d_frames, d_mean, static_cast<hipStream_t>(stream)));
     return PT_OK;
 }
 
 // the tile scratch of the blocking calls: T verdicts, then T frame counts
 static int ensure_tiles(pt_scene* s, size_t T, pt_tile_noise*& d_noise, uint32_t*& d_frames) {
-    char* base = static_cast<char*>(s->d_tiles);
-    const int rc = ensure_scratch(base, s->tiles_cap, T * (sizeof(pt_tile_noise) + sizeof(uint32_t)), "tiles");
-    s->d_tiles = base;
+    const int rc = s->d_tiles.ensure(T * (sizeof(pt_tile_noise) + sizeof(uint32_t)), "tiles");
     if (rc != PT_OK) return rc;
-    d_noise = reinterpret_cast<pt_tile_noise*>(base);
-    d_frames = reinterpret_cast<uint32_t*>(base + T * sizeof(pt_tile_noise));
+    d_noise = reinterpret_cast<pt_tile_noise*>(s->d_tiles.p);
+    d_frames = reinterpret_cast<uint32_t*>(s->d_tiles.p + T * sizeof(pt_tile_noise));
     return PT_OK;
 }
 
@@ -1516,13 +1057,13 @@ int pt_noise_tiles(pt_scene* s, const float* accum, const float* m2, uint32_t w,
     HIP_TRY(hipSetDevice(s->device));
     pt_tile_noise* d_noise = nullptr;
     uint32_t* d_frames = nullptr;
-    if ((rc = ensure_accum(s, n)) != PT_OK || (rc = ensure_scratch(s->d_m2, s->m2_cap, n, "second moments")) != PT_OK ||
+    if ((rc = s->d_accum.ensure(n, "accumulator")) != PT_OK || (rc = s->d_m2.ensure(n, "second moments")) != PT_OK ||
         (rc = ensure_tiles(s, T, d_noise, d_frames)) != PT_OK || (rc = blocking_stream(s)) != PT_OK)
         return rc;
-    HIP_TRY(hipMemcpyAsync(s->d_accum, accum, n * sizeof(float), hipMemcpyHostToDevice, s->stream));
-    HIP_TRY(hipMemcpyAsync(s->d_m2, m2, n * sizeof(float), hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipMemcpyAsync(s->d_accum.p, accum, n * sizeof(float), hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipMemcpyAsync(s->d_m2.p, m2, n * sizeof(float), hipMemcpyHostToDevice, s->stream));
     HIP_TRY(hipMemcpyAsync(d_frames, frames, T * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
-    if ((rc = pt_noise_tiles_async(s, s->d_accum, s->d_m2, w, h, w, tile_w, tile_h, d_frames, tol, floor, d_noise,
+    if ((rc = pt_noise_tiles_async(s, s->d_accum.p, s->d_m2.p, w, h, w, tile_w, tile_h, d_frames, tol, floor, d_noise,
                                    s->stream)) != PT_OK)
         return rc;
     HIP_TRY(hipMemcpyAsync(out, d_noise, T * sizeof(pt_tile_noise), hipMemcpyDeviceToHost, s->stream));
@@ -1559,21 +1100,21 @@ int pt_render_adaptive(pt_scene* s, const float meta[48], const pt_window* win, 
     HIP_TRY(hipSetDevice(s->device));
     pt_tile_noise* d_noise = nullptr;
     uint32_t* d_frames = nullptr;
-    if ((rc = ensure_accum(s, n)) != PT_OK || (rc = ensure_scratch(s->d_m2, s->m2_cap, n, "second moments")) != PT_OK ||
+    if ((rc = s->d_accum.ensure(n, "accumulator")) != PT_OK || (rc = s->d_m2.ensure(n, "second moments")) != PT_OK ||
         (rc = ensure_tiles(s, T, d_noise, d_frames)) != PT_OK || (rc = blocking_stream(s)) != PT_OK)
         return rc;
-    if (rgba && ((rc = ensure_scratch(s->d_mean, s->mean_cap, n, "tile mean")) != PT_OK ||
-                 (rc = ensure_scratch(s->d_rgba, s->rgba_cap, 4 * npix, "image")) != PT_OK))
+    if (rgba && ((rc = s->d_mean.ensure(n, "tile mean")) != PT_OK ||
+                 (rc = s->d_rgba.ensure(4 * npix, "image")) != PT_OK))
         return rc;
-    HIP_TRY(hipMemsetAsync(s->d_accum, 0, n * sizeof(float), s->stream));
-    HIP_TRY(hipMemsetAsync(s->d_m2, 0, n * sizeof(float), s->stream));
+    HIP_TRY(hipMemsetAsync(s->d_accum.p, 0, n * sizeof(float), s->stream));
+    HIP_TRY(hipMemsetAsync(s->d_m2.p, 0, n * sizeof(float), s->stream));
     HIP_TRY(hipMemsetAsync(d_frames, 0, T * sizeof(uint32_t), s->stream));
     if (counters) HIP_TRY(hipMemsetAsync(s->d_counters, 0, sizeof(Counters), s->stream));
     Counters* d_cnt = counters ? s->d_counters : nullptr;
     // pass 0: the whole window
     const pt_window whole = {fp.win_x0, fp.win_y0, W, H};
-    if ((rc = render_impl(s, meta, frame0, ad->min_frames, 1, max_depth, mode, true, s->d_accum, d_cnt, s->stream, &whole,
-                          nullptr, s->d_m2)) != PT_OK)
+    if ((rc = render_impl(s, meta, frame0, ad->min_frames, 1, max_depth, mode, true, s->d_accum.p, d_cnt, s->stream, &whole,
+                          nullptr, s->d_m2.p)) != PT_OK)
         return rc;
     std::vector<uint32_t> frames(T, ad->min_frames);
     std::vector<pt_tile_noise> noise(T);
@@ -1582,12 +1123,12 @@ int pt_render_adaptive(pt_scene* s, const float meta[48], const pt_window* win, 
     uint32_t done = ad->min_frames, npass = 1;  // done: the frames of every tile still active
     for (;;) {
         HIP_TRY(hipMemcpyAsync(d_frames, frames.data(), T * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
-        if ((rc = pt_noise_tiles_async(s, s->d_accum, s->d_m2, W, H, W, ad->tile_w, ad->tile_h, d_frames, ad->tol,
+        if ((rc = pt_noise_tiles_async(s, s->d_accum.p, s->d_m2.p, W, H, W, ad->tile_w, ad->tile_h, d_frames, ad->tol,
                                        ad->floor, d_noise, s->stream)) != PT_OK)
             return rc;
         HIP_TRY(hipMemcpyAsync(noise.data(), d_noise, T * sizeof(pt_tile_noise), hipMemcpyDeviceToHost, s->stream));
         HIP_TRY(hipStreamSynchronize(s->stream));
-        if ((rc = check_watchdog(s)) != PT_OK) return rc;
+        if ((rc = take_watchdog(s)) != PT_OK) return rc;
         size_t nact = 0;
         for (size_t t = 0; t < T; ++t) {
             active[t] = noise[t].noisy > (uint32_t)(ad->noisy_fraction * noise[t].pixels) && frames[t] < ad->max_frames;
@@ -1605,8 +1146,8 @@ int pt_render_adaptive(pt_scene* s, const float meta[48], const pt_window* win, 
             const uint32_t ph = (uint32_t)std::min<uint64_t>((uint64_t)r[3] * g.tile_h, H - py);
             const pt_window rw = {fp.win_x0 + px, fp.win_y0 + py, pw, ph};
             const size_t o = 3 * ((size_t)py * W + px);
-            if ((rc = render_impl(s, meta, frame0 + done, nf, 1, max_depth, mode, true, s->d_accum + o, d_cnt, s->stream,
-                                  &rw, &pitch, s->d_m2 + o)) != PT_OK)
+            if ((rc = render_impl(s, meta, frame0 + done, nf, 1, max_depth, mode, true, s->d_accum.p + o, d_cnt, s->stream,
+                                  &rw, &pitch, s->d_m2.p + o)) != PT_OK)
                 return rc;
         }
         for (size_t t = 0; t < T; ++t)
@@ -1615,19 +1156,19 @@ int pt_render_adaptive(pt_scene* s, const float meta[48], const pt_window* win, 
         ++npass;
     }
     if (rgba) {  // the display transform of the per-tile mean (d_frames holds the final counts)
-        if ((rc = pt_tile_mean_async(s, s->d_accum, W, H, W, ad->tile_w, ad->tile_h, d_frames, s->d_mean, s->stream)) != PT_OK ||
-            (rc = pt_tonemap_async(s, s->d_mean, npix, 1, s->d_rgba, s->stream)) != PT_OK)
+        if ((rc = pt_tile_mean_async(s, s->d_accum.p, W, H, W, ad->tile_w, ad->tile_h, d_frames, s->d_mean.p, s->stream)) != PT_OK ||
+            (rc = pt_tonemap_async(s, s->d_mean.p, npix, 1, s->d_rgba.p, s->stream)) != PT_OK)
             return rc;
-        HIP_TRY(hipMemcpyAsync(rgba, s->d_rgba, 4 * npix, hipMemcpyDeviceToHost, s->stream));
+        HIP_TRY(hipMemcpyAsync(rgba, s->d_rgba.p, 4 * npix, hipMemcpyDeviceToHost, s->stream));
     }
-    HIP_TRY(hipMemcpyAsync(accum, s->d_accum, n * sizeof(float), hipMemcpyDeviceToHost, s->stream));
-    if (m2) HIP_TRY(hipMemcpyAsync(m2, s->d_m2, n * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipMemcpyAsync(accum, s->d_accum.p, n * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+    if (m2) HIP_TRY(hipMemcpyAsync(m2, s->d_m2.p, n * sizeof(float), hipMemcpyDeviceToHost, s->stream));
     if (counters) HIP_TRY(hipMemcpyAsync(counters, s->d_counters, sizeof(Counters), hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
     std::memcpy(tile_frames, frames.data(), T * sizeof(uint32_t));
     if (tile_noise) std::memcpy(tile_noise, noise.data(), T * sizeof(pt_tile_noise));
     if (passes) *passes = npass;
-    return check_watchdog(s);
+    return take_watchdog(s);
 }
 
 int pt_frame_async(pt_scene* s, const float meta[48], uint32_t t, int max_depth, float* d_radiance, void* stream) {
@@ -1642,27 +1183,14 @@ int pt_frame(pt_scene* s, const float meta[48], uint32_t t, int max_depth, float
 
 int pt_frame_window(pt_scene* s, const float meta[48], const pt_window* win, uint32_t t, int max_depth, float* radiance) {
     if (!s || !radiance || !meta) return fail(PT_ERR_INVALID, "null argument");
-    FrameParams fp{};
-    int rc = make_params(meta, max_depth, fp, win);
-    if (rc != PT_OK) return rc;
-    const size_t n = (size_t)fp.win_w * fp.win_h * 3;
-    HIP_TRY(hipSetDevice(s->device));
-    if ((rc = ensure_accum(s, n)) != PT_OK || (rc = blocking_stream(s)) != PT_OK) return rc;
-    rc = render_impl(s, meta, t, 1, 1, max_depth, PT_MODE_AUTO, false, s->d_accum, nullptr, s->stream, win);
-    if (rc != PT_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(radiance, s->d_accum, n * sizeof(float), hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    return check_watchdog(s);
+    return render_blocking(s, meta, win, t, 1, 1, max_depth, PT_MODE_AUTO, false, radiance, nullptr, nullptr, nullptr);
 }
 
 int pt_tonemap_async(pt_scene* s, const float* d_accum, size_t npix, uint32_t sample_runs, uint8_t* d_rgba,
                      void* stream) {
     if (!s || !d_accum || !d_rgba || sample_runs == 0) return fail(PT_ERR_INVALID, "null argument or zero sample_runs");
     HIP_TRY(hipSetDevice(s->device));
-    struct ProfScope {
-        explicit ProfScope(KernelProfiler* p) { t_prof = p; }
-        ~ProfScope() { t_prof = nullptr; }
-    } prof_scope(s->prof_on ? &s->prof : nullptr);
+    ProfScope prof_scope(s);
     HIP_TRY(launch_tonemap(d_accum, npix, sample_runs, d_rgba, static_cast<hipStream_t>(stream)));
     return PT_OK;
 }
@@ -1686,29 +1214,7 @@ int pt_render_image(pt_scene* s, const float meta[48], uint32_t frame0, uint32_t
                     int max_depth, int mode, uint8_t* rgba, pt_counters* counters) {
     if (!s || !rgba || !meta) return fail(PT_ERR_INVALID, "null argument");
     if (nframes == 0) return fail(PT_ERR_INVALID, "nframes == 0 (the image divides by the sample count)");
-    FrameParams fp{};
-    int rc = make_params(meta, max_depth, fp);
-    if (rc != PT_OK) return rc;
-    const size_t npix = (size_t)fp.width * fp.height;
-    HIP_TRY(hipSetDevice(s->device));
-    if ((rc = ensure_accum(s, 3 * npix)) != PT_OK || (rc = blocking_stream(s)) != PT_OK) return rc;
-    if (s->rgba_cap < 4 * npix) {
-        if (s->d_rgba) hipFree(s->d_rgba);
-        s->d_rgba = nullptr;
-        s->rgba_cap = 0;
-        if (hipMalloc(&s->d_rgba, 4 * npix) != hipSuccess) return fail(PT_ERR_NOMEM, "hipMalloc image");
-        s->rgba_cap = 4 * npix;
-    }
-    HIP_TRY(hipMemsetAsync(s->d_accum, 0, 3 * npix * sizeof(float), s->stream));
-    if (counters) HIP_TRY(hipMemsetAsync(s->d_counters, 0, sizeof(Counters), s->stream));
-    rc = render_impl(s, meta, frame0, nframes, frame_stride, max_depth, mode, true, s->d_accum,
-                     counters ? s->d_counters : nullptr, s->stream);
-    if (rc != PT_OK) return rc;
-    if ((rc = pt_tonemap_async(s, s->d_accum, npix, nframes, s->d_rgba, s->stream)) != PT_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(rgba, s->d_rgba, 4 * npix, hipMemcpyDeviceToHost, s->stream));
-    if (counters) HIP_TRY(hipMemcpyAsync(counters, s->d_counters, sizeof(Counters), hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    return check_watchdog(s);
+    return render_blocking(s, meta, nullptr, frame0, nframes, frame_stride, max_depth, mode, true, nullptr, nullptr, rgba, counters);
 }
 
 int pt_tonemap(const float* acc, size_t npix, uint32_t sample_runs, uint8_t* rgba) {
@@ -1922,7 +1428,7 @@ int rccl_reduce(pt_scene* const* sc, int n, size_t count) {
     ncclResult_t r = a.group_start();
     if (r == ncclSuccess) {
         for (int g = 0; g < n && r == ncclSuccess; ++g)
-            r = a.reduce(sc[g]->d_accum, sc[g]->d_accum, count, ncclFloat32, ncclSum, 0, it->second[g], sc[g]->stream);
+            r = a.reduce(sc[g]->d_accum.p, sc[g]->d_accum.p, count, ncclFloat32, ncclSum, 0, it->second[g], sc[g]->stream);
         const ncclResult_t r2 = a.group_end();
         if (r == ncclSuccess) r = r2;
     }
@@ -1938,20 +1444,15 @@ int rccl_reduce(pt_scene* const* sc, int n, size_t count) {
 int ordered_reduce(pt_scene* const* sc, int n, size_t count) {
     pt_scene* s0 = sc[0];
     HIP_TRY(hipSetDevice(s0->device));
-    if (s0->peer_cap < count) {
-        if (s0->d_peer) hipFree(s0->d_peer);
-        s0->d_peer = nullptr;
-        s0->peer_cap = 0;
-        if (hipMalloc(&s0->d_peer, count * sizeof(float)) != hipSuccess) return fail(PT_ERR_NOMEM, "hipMalloc peer accumulator");
-        s0->peer_cap = count;
-    }
+    const int rc = s0->d_peer.ensure(count, "peer accumulator");
+    if (rc != PT_OK) return rc;
     for (int g = 1; g < n; ++g) {
         if (sc[g]->device == s0->device)
-            HIP_TRY(launch_accum_add(s0->d_accum, sc[g]->d_accum, count, s0->stream));
+            HIP_TRY(launch_accum_add(s0->d_accum.p, sc[g]->d_accum.p, count, s0->stream));
         else {
-            HIP_TRY(hipMemcpyPeerAsync(s0->d_peer, s0->device, sc[g]->d_accum, sc[g]->device, count * sizeof(float),
+            HIP_TRY(hipMemcpyPeerAsync(s0->d_peer.p, s0->device, sc[g]->d_accum.p, sc[g]->device, count * sizeof(float),
                                        s0->stream));
-            HIP_TRY(launch_accum_add(s0->d_accum, s0->d_peer, count, s0->stream));
+            HIP_TRY(launch_accum_add(s0->d_accum.p, s0->d_peer.p, count, s0->stream));
         }
     }
     HIP_TRY(hipStreamSynchronize(s0->stream));
@@ -1988,9 +1489,9 @@ extern "C" int pt_render_multi(pt_scene* const* scenes, int n, const float meta[
     for (int g = 0; g < n; ++g) {  // accumulators: scenes[0]'s from accum, the others zero
         pt_scene* s = scenes[g];
         HIP_TRY(hipSetDevice(s->device));
-        if ((rc = ensure_accum(s, count)) != PT_OK || (rc = blocking_stream(s)) != PT_OK) return rc;
-        if (g == 0) HIP_TRY(hipMemcpyAsync(s->d_accum, accum, count * sizeof(float), hipMemcpyHostToDevice, s->stream));
-        else HIP_TRY(hipMemsetAsync(s->d_accum, 0, count * sizeof(float), s->stream));
+        if ((rc = s->d_accum.ensure(count, "accumulator")) != PT_OK || (rc = blocking_stream(s)) != PT_OK) return rc;
+        if (g == 0) HIP_TRY(hipMemcpyAsync(s->d_accum.p, accum, count * sizeof(float), hipMemcpyHostToDevice, s->stream));
+        else HIP_TRY(hipMemsetAsync(s->d_accum.p, 0, count * sizeof(float), s->stream));
         if (counters) HIP_TRY(hipMemsetAsync(s->d_counters, 0, sizeof(Counters), s->stream));
     }
     // frames i = g, g + n, ... on scene g, each device on a host thread of its own (the wavefront's
@@ -2005,9 +1506,9 @@ extern "C" int pt_render_multi(pt_scene* const* scenes, int n, const float meta[
             int r = hipSetDevice(s->device) == hipSuccess ? PT_OK : fail(PT_ERR_HIP, "hipSetDevice");
             if (r == PT_OK)
                 r = render_impl(s, meta, frame0 + (uint32_t)g * frame_stride, cnt, (uint32_t)n * frame_stride, max_depth,
-                                mode, true, s->d_accum, counters ? s->d_counters : nullptr, s->stream);
+                                mode, true, s->d_accum.p, counters ? s->d_counters : nullptr, s->stream);
             if (r == PT_OK && hipStreamSynchronize(s->stream) != hipSuccess) r = fail(PT_ERR_HIP, "render stream");
-            if (r == PT_OK) r = check_watchdog(s);
+            if (r == PT_OK) r = take_watchdog(s);
             rcs[g] = r;
             if (r != PT_OK) errs[g] = pt_last_error();
         });
@@ -2018,7 +1519,7 @@ extern "C" int pt_render_multi(pt_scene* const* scenes, int n, const float meta[
     if (rc != PT_OK) return rc;
     pt_scene* s0 = scenes[0];
     HIP_TRY(hipSetDevice(s0->device));
-    HIP_TRY(hipMemcpyAsync(accum, s0->d_accum, count * sizeof(float), hipMemcpyDeviceToHost, s0->stream));
+    HIP_TRY(hipMemcpyAsync(accum, s0->d_accum.p, count * sizeof(float), hipMemcpyDeviceToHost, s0->stream));
     HIP_TRY(hipStreamSynchronize(s0->stream));
     if (counters) {
         pt_counters sum{};

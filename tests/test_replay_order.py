@@ -2,7 +2,7 @@
 nodes in the same order as the reference's stack walk (program-raymarch.wgsl traversal, restated
 by lean_decide: right child first, the left one stacked when both are taken), for any
 decisions — the claim its comment makes.  Internal nodes are numbered in pre-order, right
-subtree first (pt_capi.hip build_layout), and the pending set is walked smallest number first.
+subtree first (pt_scene_layout.cpp build_replay_tree), and the pending set is walked smallest number first.
 Checked on random trees with random, history-dependent decisions (host logic, no GPU)."""
 import random
 
