@@ -189,6 +189,9 @@ struct pt_scene {
     // tile verdicts followed by tile frame counts (bytes)
     Scratch<float> d_m2, d_mean;
     Scratch<char> d_tiles;
+    // a rectangle-list render's table (pt_render_rects): the rows, then the megakernel's blocks; written
+    // on the call's stream before its first launch, so calls in stream order may share it
+    Scratch<char> d_rects;
     WfStreams ws;  // dual-stream wavefront: aux stream + fork/join events (created with d_wf)
     // pinned mirror of the wavefront control words, copied after every wavefront render on its
     // stream: a watchdog flag set by an asynchronous render surfaces once that copy has landed
@@ -450,7 +453,7 @@ void pt_scene_destroy(pt_scene* s) {
     if (s->ws.fork) hipEventDestroy(s->ws.fork);
     if (s->d_rad) hipFree(s->d_rad);
     if (s->d_pres) hipFree(s->d_pres);
-    s->d_accum.free(); s->d_m2.free(); s->d_mean.free(); s->d_peer.free(); s->d_rgba.free(); s->d_tiles.free();
+    s->d_accum.free(); s->d_m2.free(); s->d_mean.free(); s->d_peer.free(); s->d_rgba.free(); s->d_tiles.free(); s->d_rects.free();
     if (s->h_ctl) hipHostFree(s->h_ctl);
     if (s->d_mem) hipFree(s->d_mem);
     s->prof.destroy();
@@ -801,21 +804,54 @@ int shape_view(pt_scene* s, const Opts& o, const FrameParams& fp, int mode, uint
     return PT_OK;
 }
 
+// The device table of a list render in the scene's scratch, uploaded on the call's stream: the rows and,
+// for the megakernel, its blocks.  The host copies are pageable, so the runtime has read them when
+// hipMemcpyAsync returns; the device copy is ordered with the call's launches on its stream.
+int upload_rects(pt_scene* s, const RectPlan& plan, const FrameParams& fp, bool blocks, hipStream_t stream, RectList& rl) {
+    const size_t row_bytes = align_up(plan.rows.size() * sizeof(RectRow), 256);
+    std::vector<RectBlock> hb;
+    if (blocks) {
+        if (plan.nblocks > 0x7fffffffull) return fail(PT_ERR_INVALID, "rects: too many 16x16 blocks for one megakernel grid");
+        plan_blocks(plan, hb);
+    }
+    const int rc = s->d_rects.ensure(row_bytes + hb.size() * sizeof(RectBlock), "rectangle table");
+    if (rc != PT_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(s->d_rects.p, plan.rows.data(), plan.rows.size() * sizeof(RectRow), hipMemcpyHostToDevice, stream));
+    if (!hb.empty())
+        HIP_TRY(hipMemcpyAsync(s->d_rects.p + row_bytes, hb.data(), hb.size() * sizeof(RectBlock), hipMemcpyHostToDevice, stream));
+    rl.rows = reinterpret_cast<const RectRow*>(s->d_rects.p);
+    rl.blocks = hb.empty() ? nullptr : reinterpret_cast<const RectBlock*>(s->d_rects.p + row_bytes);
+    rl.n = (uint32_t)plan.rows.size();
+    rl.npix = (uint32_t)plan.npix;
+    rl.nblocks = (uint32_t)hb.size();
+    rl.fx0 = fp.win_x0;
+    rl.fy0 = fp.win_y0;
+    return PT_OK;
+}
+
 // d_out: the window's first pixel, rows row_pitch pixels apart (win NULL: the whole image); d_m2
-// (nullable, accumulating calls): the second moments, laid out like d_out
+// (nullable, accumulating calls): the second moments, laid out like d_out.  rects (nullable,
+// accumulating calls): the call renders these nrects rectangles of the window instead of all of it
+// (pt_render_rects: win is its frame) — "paths per frame" is then the list's pixels everywhere below
 int render_impl(pt_scene* s, const float* meta, uint32_t frame0, uint32_t nframes, uint32_t stride, int max_depth,
                 int mode, bool accum, float* d_out, Counters* d_cnt, hipStream_t stream, const pt_window* win = nullptr,
-                const size_t* pitch = nullptr, float* d_m2 = nullptr) {
+                const size_t* pitch = nullptr, float* d_m2 = nullptr, const pt_window* rects = nullptr, size_t nrects = 0) {
     FrameParams fp{};
     int rc = make_params(meta, max_depth, fp, win, pitch);
     if (rc != PT_OK) return rc;
+    RectPlan plan;
+    const bool list = rects != nullptr || nrects != 0;
+    if (list) {
+        std::string err;
+        if ((rc = plan_rects(win, fp.width, fp.height, rects, nrects, plan, err)) != PT_OK) return fail(rc, err);
+    }
     if (mode != PT_MODE_AUTO && mode != PT_MODE_MEGAKERNEL && mode != PT_MODE_WAVEFRONT)
         return fail(PT_ERR_INVALID, "unknown mode");
     if (accum && (uint64_t)frame0 + (uint64_t)(nframes ? nframes - 1 : 0) * stride >= (1ull << 24))
         return fail(PT_ERR_INVALID, "frame index >= 2^24 (t_k = u32(f32(k)) would round)");
     HIP_TRY(hipSetDevice(s->device));
     if (nframes == 0) return PT_OK;
-    const uint64_t npix = (uint64_t)fp.win_w * fp.win_h;  // paths per frame: the window's
+    const uint64_t npix = list ? plan.npix : (uint64_t)fp.win_w * fp.win_h;  // paths per frame: the list's or the window's
     ProfScope prof_scope(s);
     const Opts o = opts_snapshot();
     const uint64_t paths = npix * (accum ? nframes : 1);
@@ -823,6 +859,9 @@ int render_impl(pt_scene* s, const float* meta, uint32_t frame0, uint32_t nframe
     if ((rc = shape_view(s, o, fp, mode, paths, view)) != PT_OK) return rc;
     const LaunchOpts lo = launch_opts(o, mode, paths, view);
     if ((rc = take_watchdog(s)) != PT_OK) return rc;  // an earlier asynchronous render failed
+    RectList rl{};
+    if (list && (rc = upload_rects(s, plan, fp, !lo.wavefront, stream, rl)) != PT_OK) return rc;
+    const RectList* const prl = list ? &rl : nullptr;
     if (lo.wavefront) {
         // the target in whole pairs of frames (a batch's two parts take whole frames each): 4096^2
         // holds 4 frames (67 M paths), not 2 of the 3.8 that 64 M would hold
@@ -852,11 +891,11 @@ int render_impl(pt_scene* s, const float* meta, uint32_t frame0, uint32_t nframe
             s->wf.pres = nullptr;
         }
         HIP_TRY(launch_wavefront(lo, view, fp, s->wf, frame0, nframes, stride, accum, d_cnt != nullptr, d_out, d_cnt,
-                                 stream, s->ws, d_m2));
+                                 stream, s->ws, d_m2, prl));
         HIP_TRY(hipMemcpyAsync(s->h_ctl, s->wf.ctl, 4 * kMaxParts * WF_CTL_WORDS, hipMemcpyDeviceToHost, stream));
         return PT_OK;
     }
-    HIP_TRY(launch_megakernel(lo, view, fp, frame0, nframes, stride, accum, d_cnt != nullptr, d_out, d_cnt, stream, d_m2));
+    HIP_TRY(launch_megakernel(lo, view, fp, frame0, nframes, stride, accum, d_cnt != nullptr, d_out, d_cnt, stream, d_m2, prl));
     return PT_OK;
 }
 
@@ -956,12 +995,19 @@ static int blocking_stream(pt_scene* s) {
 // a frame, accumulate false: neither), the render, the results back to the host — accum, or rgba
 // (nullable: the tone-mapped image instead), m2 and counters (nullable) — one synchronisation, and
 // the watchdog (a trace wave that hit kTraceWatchdog left a flag, cleared here).
+// rects (nullable): a list render of the window (pt_render_rects: win is its frame) — the list is
+// checked before anything is copied, so a rejected call leaves the host buffers alone.
 static int render_blocking(pt_scene* s, const float* meta, const pt_window* win, uint32_t frame0, uint32_t nframes,
                            uint32_t stride, int max_depth, int mode, bool accumulate, float* accum, float* m2,
-                           uint8_t* rgba, pt_counters* counters) {
+                           uint8_t* rgba, pt_counters* counters, const pt_window* rects = nullptr, size_t nrects = 0) {
     FrameParams fp{};
     int rc = make_params(meta, max_depth, fp, win);
     if (rc != PT_OK) return rc;
+    if (rects != nullptr || nrects != 0) {
+        RectPlan plan;
+        std::string err;
+        if ((rc = plan_rects(win, fp.width, fp.height, rects, nrects, plan, err)) != PT_OK) return fail(rc, err);
+    }
     const size_t npix = (size_t)fp.win_w * fp.win_h, n = 3 * npix;
     HIP_TRY(hipSetDevice(s->device));
     if ((rc = s->d_accum.ensure(n, "accumulator")) != PT_OK || (m2 && (rc = s->d_m2.ensure(n, "second moments")) != PT_OK) ||
@@ -973,7 +1019,7 @@ static int render_blocking(pt_scene* s, const float* meta, const pt_window* win,
     if (m2) HIP_TRY(hipMemcpyAsync(s->d_m2.p, m2, n * sizeof(float), hipMemcpyHostToDevice, s->stream));
     if (d_cnt) HIP_TRY(hipMemsetAsync(d_cnt, 0, sizeof(Counters), s->stream));
     rc = render_impl(s, meta, frame0, nframes, stride, max_depth, mode, accumulate, s->d_accum.p, d_cnt, s->stream, win,
-                     nullptr, m2 ? s->d_m2.p : nullptr);
+                     nullptr, m2 ? s->d_m2.p : nullptr, rects, nrects);
     if (rc != PT_OK) return rc;
     if (rgba) {
         if ((rc = pt_tonemap_async(s, s->d_accum.p, npix, nframes, s->d_rgba.p, s->stream)) != PT_OK) return rc;
@@ -1010,6 +1056,36 @@ int pt_render_moments(pt_scene* s, const float meta[48], const pt_window* win, u
                       uint32_t frame_stride, int max_depth, int mode, float* accum, float* m2, pt_counters* counters) {
     if (!s || !accum || !m2 || !meta) return fail(PT_ERR_INVALID, "null argument");
     return render_blocking(s, meta, win, frame0, nframes, frame_stride, max_depth, mode, true, accum, m2, nullptr, counters);
+}
+
+int pt_render_rects_async(pt_scene* s, const float meta[48], const pt_window* frame, const pt_window* rects, size_t n,
+                          uint32_t frame0, uint32_t nframes, uint32_t frame_stride, int max_depth, int mode, float* d_accum,
+                          float* d_m2, size_t row_pitch, pt_counters* d_counters, void* stream) {
+    if (!s || !d_accum || !meta) return fail(PT_ERR_INVALID, "null argument");
+    if (!rects || !n) return fail(PT_ERR_INVALID, n ? "rects is NULL" : "rects: the list is empty (n must be at least 1)");
+    return render_impl(s, meta, frame0, nframes, frame_stride, max_depth, mode, true, d_accum,
+                       reinterpret_cast<Counters*>(d_counters), static_cast<hipStream_t>(stream), frame, &row_pitch, d_m2,
+                       rects, n);
+}
+
+int pt_render_rects(pt_scene* s, const float meta[48], const pt_window* frame, const pt_window* rects, size_t n,
+                    uint32_t frame0, uint32_t nframes, uint32_t frame_stride, int max_depth, int mode, float* accum,
+                    float* m2, pt_counters* counters) {
+    if (!s || !accum || !meta) return fail(PT_ERR_INVALID, "null argument");
+    if (!rects || !n) return fail(PT_ERR_INVALID, n ? "rects is NULL" : "rects: the list is empty (n must be at least 1)");
+    return render_blocking(s, meta, frame, frame0, nframes, frame_stride, max_depth, mode, true, accum, m2, nullptr, counters,
+                           rects, n);
+}
+
+int pt_selftest_rect_plan(const pt_window* frame, uint32_t W, uint32_t H, const pt_window* rects, size_t n,
+                          uint64_t* first_out, uint64_t* npix_out) {
+    RectPlan plan;
+    std::string err;
+    const int rc = plan_rects(frame, W, H, rects, n, plan, err);
+    if (rc != PT_OK) return fail(rc, err);
+    for (size_t k = 0; first_out && k < n; ++k) first_out[k] = plan.rows[k].first;
+    if (npix_out) *npix_out = plan.npix;
+    return PT_OK;
 }
 
 int pt_noise_tiles_async(pt_scene* s, const float* d_accum, const float* d_m2, uint32_t w, uint32_t h, size_t row_pitch,
@@ -1120,6 +1196,7 @@ int pt_render_adaptive(pt_scene* s, const float meta[48], const pt_window* win, 
     std::vector<pt_tile_noise> noise(T);
     std::vector<uint8_t> active(T);
     std::vector<std::array<uint32_t, 4>> rects;
+    std::vector<pt_window> list;
     uint32_t done = ad->min_frames, npass = 1;  // done: the frames of every tile still active
     for (;;) {
         HIP_TRY(hipMemcpyAsync(d_frames, frames.data(), T * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
@@ -1135,21 +1212,21 @@ int pt_render_adaptive(pt_scene* s, const float meta[48], const pt_window* win, 
             nact += active[t];
         }
         if (nact == 0) break;
-        // the active tiles' next frames: one frame range over the rectangles of the active set, each
-        // rendered in place inside the window's buffers
+        // the active tiles' next frames: one frame range over the rectangles of the active set, clipped
+        // to the window, as ONE list render in place inside the window's buffers
         const uint32_t nf = std::min(ad->step_frames, ad->max_frames - done);
         tile_rects(active.data(), g.tx, g.ty, rects);
-        const size_t pitch = W;
+        list.clear();
         for (const auto& r : rects) {
             const uint32_t px = r[0] * g.tile_w, py = r[1] * g.tile_h;
             const uint32_t pw = (uint32_t)std::min<uint64_t>((uint64_t)r[2] * g.tile_w, W - px);
             const uint32_t ph = (uint32_t)std::min<uint64_t>((uint64_t)r[3] * g.tile_h, H - py);
-            const pt_window rw = {fp.win_x0 + px, fp.win_y0 + py, pw, ph};
-            const size_t o = 3 * ((size_t)py * W + px);
-            if ((rc = render_impl(s, meta, frame0 + done, nf, 1, max_depth, mode, true, s->d_accum.p + o, d_cnt, s->stream,
-                                  &rw, &pitch, s->d_m2.p + o)) != PT_OK)
-                return rc;
+            list.push_back(pt_window{fp.win_x0 + px, fp.win_y0 + py, pw, ph});
         }
+        for (size_t k = 0; k < list.size(); k += kMaxRects)  // (a list call takes kMaxRects rectangles)
+            if ((rc = render_impl(s, meta, frame0 + done, nf, 1, max_depth, mode, true, s->d_accum.p, d_cnt, s->stream, &whole,
+                                  nullptr, s->d_m2.p, list.data() + k, std::min(kMaxRects, list.size() - k))) != PT_OK)
+                return rc;
         for (size_t t = 0; t < T; ++t)
             if (active[t]) frames[t] += nf;
         done += nf;

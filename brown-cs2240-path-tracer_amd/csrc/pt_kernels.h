@@ -6,6 +6,7 @@
 
 #include "pt_device.h"
 #include "pt_flavour.h"
+#include "pt_rect_plan.h"
 
 // ids for k_selftest_math (also used by pt_selftest_math in the C-ABI)
 enum {
@@ -116,9 +117,23 @@ struct WfStreams {
     hipStream_t aux[kMaxParts] = {};
     hipEvent_t fork = nullptr, join[kMaxParts] = {};
 };
+// A rectangle list on the device (pt_render_rects; pt_rect_plan.h): the third slot -> pixel map beside
+// the window's two (slot_path, pixel_of).  A list render's FrameParams window is the call's frame: a
+// pixel (x, y) of a rectangle is stored at out + 3 * ((y - win_y0) * row_pitch + (x - win_x0)).
+struct RectList {
+    const RectRow* rows;      // n, list order
+    const RectBlock* blocks;  // the megakernel's grid, one entry per 16 x 16 block (nullptr: a wavefront render)
+    uint32_t n, npix;         // rectangles, pixels per frame
+    uint32_t nblocks;
+    uint32_t fx0, fy0;        // the frame's origin (FrameParams::win_x0, win_y0)
+};
+// rl (nullable, accumulating calls): the call renders the rectangles of the list instead of fp's
+// window — paths per frame rl->npix, camera paths by k_wf_generate's list instance (whatever
+// lo.fuse_gen and lo.regen say), k_wf_accum's list instance
 hipError_t launch_wavefront(const LaunchOpts& lo, const SceneView& sc, const FrameParams& fp, const WfBuffers& wb,
                             uint32_t frame0, uint32_t nframes, uint32_t stride, bool accum, bool count, float* out,
-                            Counters* cnt, hipStream_t stream, const WfStreams& ws, float* m2 = nullptr);
+                            Counters* cnt, hipStream_t stream, const WfStreams& ws, float* m2 = nullptr,
+                            const RectList* rl = nullptr);
 
 // set width (32 / 64 bits) of the stackless replay in the fused kernel launched last in this process
 // (0: none yet, or the stack walk) — pt_last_bf_width, for the tests of the narrow instance
@@ -127,9 +142,10 @@ int last_bf_width();
 // Megakernel render (accum=true: frames frame0 + i*stride, i < nframes, added to out) or one
 // dispatch (accum=false: raw radiance of salt frame0 written to out).  m2 (accum only, as in
 // launch_wavefront): the second moments, m2 += clamp(L)^2 per frame, laid out like out.
+// rl (nullable, accum only): the rectangles of the list instead of fp's window, a grid of rl->nblocks blocks.
 hipError_t launch_megakernel(const LaunchOpts& lo, const SceneView& sc, const FrameParams& fp, uint32_t frame0,
                              uint32_t nframes, uint32_t stride, bool accum, bool count, float* out, Counters* cnt,
-                             hipStream_t stream, float* m2 = nullptr);
+                             hipStream_t stream, float* m2 = nullptr, const RectList* rl = nullptr);
 
 // display transform of program-raymarch.ts:295-316 on device (pt_image.hip)
 hipError_t launch_tonemap(const float* acc, size_t npix, uint32_t runs, uint8_t* rgba, hipStream_t stream);

@@ -12,6 +12,8 @@
 //   k_mega<ACCUM, COUNT>   the same integrator written with the reference's control flow
 //       (radiance() as one loop per sample); kept as the structural twin for A/B tests.
 //   k_selftest_math        exposes pt_math.h on device for the numerics tests.
+#include <type_traits>
+
 #include "pt_kernels.h"
 #include "pt_path.h"
 
@@ -73,27 +75,53 @@ __device__ __forceinline__ bool pixel_of(const FrameParams& fp, uint32_t& x, uin
     return valid;
 }
 
+// The lane's pixel in a rectangle list (pt_render_rects): every rectangle has 16x16 blocks of its own
+// in a one-dimensional grid, rl.blocks says which rectangle a block belongs to and which block of it
+// it is, and the bound is the rectangle's; the place in the destination is relative to the call's
+// frame (fp's window).
+__device__ __forceinline__ bool pixel_of(const FrameParams& fp, uint32_t& x, uint32_t& y, size_t& o, const RectList& rl) {
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const RectBlock b = rl.blocks[blockIdx.x];
+    const RectRow r = rl.rows[b.rect];
+    const uint32_t i = (b.bxy & 0xffffu) * 16 + (w & 1) * 8 + (lane & 7);
+    const uint32_t j = (b.bxy >> 16) * 16 + (w >> 1) * 8 + (lane >> 3);
+    const bool valid = i < r.w && j < r.h;
+    x = valid ? r.x0 + i : 0;
+    y = valid ? r.y0 + j : 0;
+    o = valid ? 3 * ((size_t)(y - fp.win_y0) * fp.row_pitch + (x - fp.win_x0)) : 0;
+    return valid;
+}
+// ... of a kernel's extra arguments (below): the list's when they hold one, else the window's
+template <class... R>
+__device__ __forceinline__ bool pixel_of(const FrameParams& fp, uint32_t& x, uint32_t& y, size_t& o, float*, R... r) {
+    return pixel_of(fp, x, y, o, r...);
+}
+
+// The megakernels' extra arguments X: nothing (the plain instances, whose arguments and code stay as
+// they were), the second-moment buffer (float*), the call's RectList, or both in that order.
 // MOM (with ACCUM): the second moments too, m2 += c * c beside acc += c (c = clamp(L); the product
 // rounded, then the sum: -ffp-contract=off), in and out like the accumulator and at the same place.
-// M2 is empty (the plain instances, whose arguments and code stay as they were) or one float*.
-template <class... M2>
-__device__ __forceinline__ float* moments_of(M2... m2) {
-    static_assert(sizeof...(M2) <= 1, "at most the one second-moment buffer");
-    float* p[] = {m2..., nullptr};
-    return p[0];
+template <class... X>
+constexpr bool has_moments = (std::is_same_v<X, float*> || ...);
+__device__ __forceinline__ float* moments_of() { return nullptr; }
+__device__ __forceinline__ float* moments_of(const RectList&) { return nullptr; }
+template <class... R>
+__device__ __forceinline__ float* moments_of(float* m2, R...) {
+    static_assert(sizeof...(R) <= 1, "the second-moment buffer, then at most the rectangle list");
+    return m2;
 }
-template <bool ACCUM, bool COUNT, class... M2>
+template <bool ACCUM, bool COUNT, class... X>
 __global__ __launch_bounds__(kMegaBlock) void k_mega(SceneView sc, FrameParams fp, uint32_t frame0, uint32_t nframes,
                                                     uint32_t stride, float* __restrict__ out, Counters* cnt_out,
-                                                    M2... m2_arg) {
-    constexpr bool MOM = sizeof...(M2) > 0;
-    static_assert(ACCUM || !MOM, "second moments are accumulated");
-    float* __restrict__ const m2 = moments_of(m2_arg...);
+                                                    X... extra) {
+    constexpr bool MOM = has_moments<X...>;
+    static_assert(ACCUM || sizeof...(X) == 0, "second moments and rectangle lists belong to accumulating calls");
+    float* __restrict__ const m2 = moments_of(extra...);
     __shared__ int32_t s_stack[kStackMax * kMegaBlock];
     const LStack32 stack = LStack32::make(reinterpret_cast<char*>(s_stack), kMegaBlock);
     uint32_t x, y;
     size_t oi;
-    const bool valid = pixel_of(fp, x, y, oi);
+    const bool valid = pixel_of(fp, x, y, oi, extra...);
     Counters c = {};
     if (valid) {
         float* o = out + oi;
@@ -118,19 +146,19 @@ __global__ __launch_bounds__(kMegaBlock) void k_mega(SceneView sc, FrameParams f
 // ---------------------------------------------------------------------------------------
 // Megakernel: path regeneration, one traversal site, optional LDS scene, flat traversal
 // ---------------------------------------------------------------------------------------
-template <bool LDS, int TRAV, bool ACCUM, bool COUNT, class... M2>
+template <bool LDS, int TRAV, bool ACCUM, bool COUNT, class... X>
 __global__ __launch_bounds__(kMegaBlock) void k_regen(SceneView sc, FrameParams fp, uint32_t frame0, uint32_t nframes,
                                                      uint32_t stride, float* __restrict__ out, Counters* cnt_out,
-                                                     M2... m2_arg) {
-    constexpr bool MOM = sizeof...(M2) > 0;
-    static_assert(ACCUM || !MOM, "second moments are accumulated");
-    float* __restrict__ const m2 = moments_of(m2_arg...);
+                                                     X... extra) {
+    constexpr bool MOM = has_moments<X...>;
+    static_assert(ACCUM || sizeof...(X) == 0, "second moments and rectangle lists belong to accumulating calls");
+    float* __restrict__ const m2 = moments_of(extra...);
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const LStack32 stack = LStack32::make(smem, kMegaBlock);  // [max_stack][256] int32, lane-minor
     if (LDS) stage_scene_lds(sc, smem + (uint32_t)sc.max_stack * kMegaBlock * 4u);
     uint32_t x, y;
     size_t oi;
-    const bool valid = pixel_of(fp, x, y, oi);
+    const bool valid = pixel_of(fp, x, y, oi, extra...);
     Counters c = {};
     float* o = out + oi;
     f3 acc = (ACCUM && valid) ? mk(o[0], o[1], o[2]) : mk(0.0f, 0.0f, 0.0f);
@@ -414,28 +442,43 @@ bool scene_fits_lds(const SceneView& sc) {
     return (size_t)sc.max_stack * kMegaBlock * 4 + sc.span_bytes <= kLdsSceneBudget;
 }
 
-// m2...: nothing, or the second-moment buffer (the moments flavour, k_regen<..., float*>)
-template <bool LDS, int TRAV, bool ACCUM, bool COUNT, class... M2>
+// the megakernels' grid: 16x16 blocks over the window, or the blocks of the list
+static dim3 mega_grid(const FrameParams& fp, const RectList* rl) {
+    return rl ? dim3(rl->nblocks) : dim3((fp.win_w + 15) / 16, (fp.win_h + 15) / 16);
+}
+
+// extra...: nothing, the second-moment buffer (the moments flavour, k_regen<..., float*>), the
+// rectangle list, or both (k_regen's X)
+template <bool LDS, int TRAV, bool ACCUM, bool COUNT, class... X>
 static void launch_regen_t(const SceneView& sc, const FrameParams& fp, uint32_t frame0, uint32_t nframes, uint32_t stride,
-                           float* out, Counters* cnt, hipStream_t stream, M2... m2) {
-    dim3 grid((fp.win_w + 15) / 16, (fp.win_h + 15) / 16), block(kMegaBlock);
+                           float* out, Counters* cnt, hipStream_t stream, const RectList* rl, X... extra) {
+    const dim3 grid = mega_grid(fp, rl), block(kMegaBlock);
     size_t lds = (size_t)sc.max_stack * kMegaBlock * 4 + (LDS ? sc.span_bytes : 0);
-    PT_LAUNCH(KID_REGEN, stream, (k_regen<LDS, TRAV, ACCUM, COUNT, M2...>), grid, block, lds, stream, sc, fp, frame0, nframes, stride, out,
-                       cnt, m2...);
+    PT_LAUNCH(KID_REGEN, stream, (k_regen<LDS, TRAV, ACCUM, COUNT, X...>), grid, block, lds, stream, sc, fp, frame0, nframes, stride, out,
+                       cnt, extra...);
 }
 
 template <bool LDS, int TRAV>
 static void launch_regen_a(const SceneView& sc, const FrameParams& fp, uint32_t frame0, uint32_t nframes, uint32_t stride,
-                           bool accum, bool count, float* out, Counters* cnt, hipStream_t stream, float* m2) {
-    if (m2) {  // the moments flavour (accumulating calls only: launch_megakernel)
-        if (count) launch_regen_t<LDS, TRAV, true, true>(sc, fp, frame0, nframes, stride, out, cnt, stream, m2);
-        else launch_regen_t<LDS, TRAV, true, false>(sc, fp, frame0, nframes, stride, out, cnt, stream, m2);
+                           bool accum, bool count, float* out, Counters* cnt, hipStream_t stream, float* m2,
+                           const RectList* rl) {
+    if (rl) {  // the list flavours (accumulating calls only: launch_megakernel), with and without moments
+        if (m2) {
+            if (count) launch_regen_t<LDS, TRAV, true, true>(sc, fp, frame0, nframes, stride, out, cnt, stream, rl, m2, *rl);
+            else launch_regen_t<LDS, TRAV, true, false>(sc, fp, frame0, nframes, stride, out, cnt, stream, rl, m2, *rl);
+        } else {
+            if (count) launch_regen_t<LDS, TRAV, true, true>(sc, fp, frame0, nframes, stride, out, cnt, stream, rl, *rl);
+            else launch_regen_t<LDS, TRAV, true, false>(sc, fp, frame0, nframes, stride, out, cnt, stream, rl, *rl);
+        }
+    } else if (m2) {  // the moments flavour (accumulating calls only: launch_megakernel)
+        if (count) launch_regen_t<LDS, TRAV, true, true>(sc, fp, frame0, nframes, stride, out, cnt, stream, nullptr, m2);
+        else launch_regen_t<LDS, TRAV, true, false>(sc, fp, frame0, nframes, stride, out, cnt, stream, nullptr, m2);
     } else if (accum) {
-        if (count) launch_regen_t<LDS, TRAV, true, true>(sc, fp, frame0, nframes, stride, out, cnt, stream);
-        else launch_regen_t<LDS, TRAV, true, false>(sc, fp, frame0, nframes, stride, out, cnt, stream);
+        if (count) launch_regen_t<LDS, TRAV, true, true>(sc, fp, frame0, nframes, stride, out, cnt, stream, nullptr);
+        else launch_regen_t<LDS, TRAV, true, false>(sc, fp, frame0, nframes, stride, out, cnt, stream, nullptr);
     } else {
-        if (count) launch_regen_t<LDS, TRAV, false, true>(sc, fp, frame0, nframes, stride, out, cnt, stream);
-        else launch_regen_t<LDS, TRAV, false, false>(sc, fp, frame0, nframes, stride, out, cnt, stream);
+        if (count) launch_regen_t<LDS, TRAV, false, true>(sc, fp, frame0, nframes, stride, out, cnt, stream, nullptr);
+        else launch_regen_t<LDS, TRAV, false, false>(sc, fp, frame0, nframes, stride, out, cnt, stream, nullptr);
     }
 }
 
@@ -443,8 +486,9 @@ constexpr int kMegaNodeBias = 8;  // measured with lean4: 1 -> 8 = +9 %
 
 hipError_t launch_megakernel(const LaunchOpts& lo, const SceneView& scene, const FrameParams& fp, uint32_t frame0,
                              uint32_t nframes, uint32_t stride, bool accum, bool count, float* out, Counters* cnt,
-                             hipStream_t stream, float* m2) {
-    if (m2 && !accum) return hipErrorInvalidValue;
+                             hipStream_t stream, float* m2, const RectList* rl) {
+    if ((m2 || rl) && !accum) return hipErrorInvalidValue;
+    if (rl && (!rl->blocks || rl->nblocks == 0)) return hipErrorInvalidValue;
     SceneView sc = scene;
     if (sc.node_bias <= 0) sc.node_bias = kMegaNodeBias;
     // one node step per turn: more lose in the megakernel (Glossy 256^2: 3 steps -9 %, 8 -15 %,
@@ -452,13 +496,22 @@ hipError_t launch_megakernel(const LaunchOpts& lo, const SceneView& scene, const
     if (sc.node_steps <= 0) sc.node_steps = 1;
     if (!accum) { nframes = 1; stride = 1; }
     if (lo.literal) {
-        dim3 grid((fp.win_w + 15) / 16, (fp.win_h + 15) / 16), block(kMegaBlock);
+        const dim3 grid = mega_grid(fp, rl), block(kMegaBlock);
 #define LIT(A, C) PT_LAUNCH(KID_MEGA, stream, (k_mega<A, C>), grid, block, 0, stream, sc, fp, frame0, nframes, stride, out, cnt)
 #define LIT_M2(C) \
     PT_LAUNCH(KID_MEGA, stream, (k_mega<true, C, float*>), grid, block, 0, stream, sc, fp, frame0, nframes, stride, out, cnt, m2)
-        if (m2) { if (count) LIT_M2(true); else LIT_M2(false); }
+#define LIT_RL(C) \
+    PT_LAUNCH(KID_MEGA, stream, (k_mega<true, C, RectList>), grid, block, 0, stream, sc, fp, frame0, nframes, stride, out, cnt, *rl)
+#define LIT_M2_RL(C)                                                                                                    \
+    PT_LAUNCH(KID_MEGA, stream, (k_mega<true, C, float*, RectList>), grid, block, 0, stream, sc, fp, frame0, nframes, stride, out, \
+              cnt, m2, *rl)
+        if (rl && m2) { if (count) LIT_M2_RL(true); else LIT_M2_RL(false); }
+        else if (rl) { if (count) LIT_RL(true); else LIT_RL(false); }
+        else if (m2) { if (count) LIT_M2(true); else LIT_M2(false); }
         else if (accum) { if (count) LIT(true, true); else LIT(true, false); }
         else { if (count) LIT(false, true); else LIT(false, false); }
+#undef LIT_M2_RL
+#undef LIT_RL
 #undef LIT_M2
 #undef LIT
         return hipGetLastError();
@@ -467,8 +520,8 @@ hipError_t launch_megakernel(const LaunchOpts& lo, const SceneView& scene, const
     const int trav = select_megakernel(lo, sc.fast_rcp != 0, sc.mailbox != 0, sc.big_leaf > 0, false);
 #define RA(T)                                                                                             \
     case T:                                                                                               \
-        if (lds) launch_regen_a<true, T>(sc, fp, frame0, nframes, stride, accum, count, out, cnt, stream, m2); \
-        else launch_regen_a<false, T>(sc, fp, frame0, nframes, stride, accum, count, out, cnt, stream, m2);   \
+        if (lds) launch_regen_a<true, T>(sc, fp, frame0, nframes, stride, accum, count, out, cnt, stream, m2, rl); \
+        else launch_regen_a<false, T>(sc, fp, frame0, nframes, stride, accum, count, out, cnt, stream, m2, rl);   \
         break;
     switch (trav) { PT_MEGA_FLAVOURS(RA) }
 #undef RA

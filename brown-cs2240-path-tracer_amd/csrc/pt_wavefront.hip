@@ -161,9 +161,41 @@ __device__ __forceinline__ uint32_t slot_path(uint32_t s, const FrameParams& fp,
     return s;
 }
 
-template <bool COUNT>
+// The rectangle of a list that holds pixel q of its frame (q < rl.npix), and q's place inside it:
+// the last row whose first slot is <= q, by bisection (<= 17 steps; neighbouring lanes nearly always
+// agree on every one).
+__device__ __forceinline__ RectRow rect_of(const RectList& rl, uint32_t q, uint32_t& i, uint32_t& j) {
+    uint32_t lo = 0, hi = rl.n;
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (rl.rows[mid].first <= q) lo = mid;
+        else hi = mid;
+    }
+    const RectRow r = rl.rows[lo];
+    const uint32_t k = q - r.first;
+    j = k / r.w;
+    i = k - j * r.w;
+    return r;
+}
+
+// slot_path of a rectangle list (pt_render_rects): path id p = f * npix + q with npix the list's
+// pixels and q the pixel's position in the concatenation of the rectangles, row-major inside each
+__device__ __forceinline__ uint32_t slot_path(uint32_t s, const RectList& rl, uint32_t& x, uint32_t& y, uint32_t& f) {
+    f = s / rl.npix;
+    uint32_t i, j;
+    const RectRow r = rect_of(rl, s - f * rl.npix, i, j);
+    x = r.x0 + i;
+    y = r.y0 + j;
+    return s;
+}
+
+// RL: nothing (the window's instances, whose arguments and code stay as they were), or the call's
+// RectList (its slot -> pixel map instead of the window's)
+template <bool COUNT, class... RL>
 __global__ __launch_bounds__(256) void k_wf_generate(FrameParams fp, WfBuffers wb, uint32_t frame0, uint32_t stride,
-                                                     uint32_t fbase, uint32_t P, bool raw_salt, Counters* cnt_out) {
+                                                     uint32_t fbase, uint32_t P, bool raw_salt, Counters* cnt_out,
+                                                     RL... rl) {
+    static_assert(sizeof...(RL) <= 1, "at most the one rectangle list");
     const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p == 0) {
         wb.ctl[WF_COUNT0] = P;
@@ -182,7 +214,9 @@ __global__ __launch_bounds__(256) void k_wf_generate(FrameParams fp, WfBuffers w
     Counters c = {};
     if (p < P) {  // p: the queue slot; pid: the path made there (slot_path)
         uint32_t x, y, f;
-        const uint32_t pid = slot_path(p, fp, x, y, f);
+        uint32_t pid;
+        if constexpr (sizeof...(RL) > 0) pid = slot_path(p, rl..., x, y, f);
+        else pid = slot_path(p, fp, x, y, f);
         const uint32_t t = raw_salt ? frame0 : (uint32_t)(float)(frame0 + (fbase + f) * stride);
         PathState ps;
         Ray r = path_begin(fp, x, y, t, ps);
@@ -1088,14 +1122,25 @@ __global__ __launch_bounds__(kShadeBlock) void k_wf_shade(SceneView sc, FramePar
 // acc += clamp(radiance) for the batch's frames in order (program-raymarch.ts:283-285); window
 // pixel pix = j * win_w + i lives at acc + 3 * (j * row_pitch + i).  m2 (nullable, with accumulate):
 // the second moments at the same place, m2 += clamp(L)^2 in the same frame order, so a call's batches
-// continue them as they continue acc
+// continue them as they continue acc.  RL: nothing, or the call's RectList — pix is then the pixel's
+// position in the list, and its place the frame-relative one of its rectangle's pixel (win_w unused)
+template <class... RL>
 __global__ __launch_bounds__(256) void k_wf_accum(const float* __restrict__ rad, float* __restrict__ acc, uint32_t npix,
                                                   uint32_t win_w, uint32_t row_pitch, uint32_t F, bool accumulate,
-                                                  float* __restrict__ m2) {
+                                                  float* __restrict__ m2, RL... rl) {
+    static_assert(sizeof...(RL) <= 1, "at most the one rectangle list");
     const uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x;
     if (pix >= npix) return;
-    const uint32_t j = pix / win_w;
-    const size_t oi = 3 * ((size_t)j * row_pitch + (pix - j * win_w));
+    size_t oi;
+    if constexpr (sizeof...(RL) > 0) {
+        const RectList& l = (rl, ...);
+        uint32_t i, j;
+        const RectRow r = rect_of(l, pix, i, j);
+        oi = 3 * ((size_t)(r.y0 + j - l.fy0) * row_pitch + (r.x0 + i - l.fx0));
+    } else {
+        const uint32_t j = pix / win_w;
+        oi = 3 * ((size_t)j * row_pitch + (pix - j * win_w));
+    }
     float* o = acc + oi;
     f3 a = accumulate ? mk(o[0], o[1], o[2]) : mk(0.0f, 0.0f, 0.0f);
     if (m2) {
@@ -1215,9 +1260,9 @@ static SceneView bf_view(const SceneView& sc) {
 template <bool LDS, int TRAV, bool COUNT>
 static hipError_t wf_render_t(const SceneView& sc_in, const FrameParams& fp, const WfBuffers& wb, uint32_t frame0,
                               uint32_t nframes, uint32_t stride, bool accum, float* out, Counters* cnt,
-                              hipStream_t stream, const WfStreams& ws, const LaunchOpts& lo, float* m2) {
+                              hipStream_t stream, const WfStreams& ws, const LaunchOpts& lo, float* m2, const RectList* rl) {
     SceneView sc = bf_view<TRAV, COUNT>(sc_in);
-    const uint32_t npix = fp.win_w * fp.win_h;  // paths per frame: the window's
+    const uint32_t npix = rl ? rl->npix : fp.win_w * fp.win_h;  // paths per frame: the list's, else the window's
     // the batch in lo.parts parts on as many streams when a part holds at least a frame: one
     // part's kernel fills the others' launch tails and boundaries (and, with separate trace and
     // shade kernels, a VALU-bound trace runs beside an HBM-bound shade)
@@ -1261,7 +1306,7 @@ static hipError_t wf_render_t(const SceneView& sc_in, const FrameParams& fp, con
     constexpr bool kNarrowOk = flv_fused(TRAV) && LDS && !COUNT;
     const bool narrow = kNarrowOk && sc.bfnode && sc.bfnarrow;
     if constexpr (flv_fused(TRAV)) {  // the camera batches' table (k_wf_camtab), before every part's GEN launch
-        if (lo.fuse_gen) {
+        if (lo.fuse_gen && !rl) {
             if (sc.n_tris - sc.mb_base > 64) return hipErrorInvalidValue;  // mailbox scenes: <= 64 entries
             hipLaunchKernelGGL(k_wf_camtab, dim3(1), dim3(64), 0, stream, sc, fp, wb.camtab);
         }
@@ -1306,7 +1351,8 @@ static hipError_t wf_render_t(const SceneView& sc_in, const FrameParams& fp, con
         // before the fork: on a part's stream the second part's memset waited ~0.5 ms for a CU slot
         // behind the first part's first launch, and the parts ran that far apart (a kernel trace of
         // the bench, r06m)
-        const bool fgen = flv_fused(TRAV) && lo.fuse_gen;
+        // (a rectangle list's camera paths come from k_wf_generate's list instance: the fuse_gen = 0 route)
+        const bool fgen = flv_fused(TRAV) && lo.fuse_gen && !rl;
         if (fgen)
             for (int h = 0; h < nh; ++h)
                 HIP_RETURN_IF(hipMemsetAsync(pv[h].w.rcnt + kRegions, 0, kRegions * sizeof(uint32_t), stream));
@@ -1329,10 +1375,15 @@ static hipError_t wf_render_t(const SceneView& sc_in, const FrameParams& fp, con
             else
                 regen_q = 0;  // one launch admits them all: the plain first launch
         }
-        for (int h = 0; h < nh && !fgen; ++h)
-            PT_LAUNCH(KID_WF_GENERATE, pv[h].st, (k_wf_generate<COUNT>),
-                      dim3((std::max(pv[h].P, pv[h].w.nreg) + 255) / 256), dim3(256), 0, pv[h].st,
-                      fp, pv[h].w, frame0, stride, pv[h].fbase, pv[h].P, !accum, cnt);
+        for (int h = 0; h < nh && !fgen; ++h) {
+            const dim3 ggrid((std::max(pv[h].P, pv[h].w.nreg) + 255) / 256);
+            if (rl)
+                PT_LAUNCH(KID_WF_GENERATE, pv[h].st, (k_wf_generate<COUNT, RectList>), ggrid, dim3(256), 0, pv[h].st,
+                          fp, pv[h].w, frame0, stride, pv[h].fbase, pv[h].P, !accum, cnt, *rl);
+            else
+                PT_LAUNCH(KID_WF_GENERATE, pv[h].st, (k_wf_generate<COUNT>), ggrid, dim3(256), 0, pv[h].st,
+                          fp, pv[h].w, frame0, stride, pv[h].fbase, pv[h].P, !accum, cnt);
+        }
         // launch `it` of part h (in_q: the queue the trace kernels read, it & 1)
         auto step = [&](int h, int it) -> hipError_t {
             const int in_q = it & 1;
@@ -1404,23 +1455,27 @@ static hipError_t wf_render_t(const SceneView& sc_in, const FrameParams& fp, con
                 HIP_RETURN_IF(hipStreamWaitEvent(stream, ws.join[h], 0));
             }
         }
-        PT_LAUNCH(KID_WF_ACCUM, stream, k_wf_accum, dim3((npix + 255) / 256), dim3(256), 0, stream, wb.rad, out, npix, fp.win_w,
-                  fp.row_pitch, Fb, accum, m2);
+        if (rl)
+            PT_LAUNCH(KID_WF_ACCUM, stream, (k_wf_accum<RectList>), dim3((npix + 255) / 256), dim3(256), 0, stream, wb.rad, out,
+                      npix, fp.win_w, fp.row_pitch, Fb, accum, m2, *rl);
+        else
+            PT_LAUNCH(KID_WF_ACCUM, stream, (k_wf_accum<>), dim3((npix + 255) / 256), dim3(256), 0, stream, wb.rad, out, npix,
+                      fp.win_w, fp.row_pitch, Fb, accum, m2);
     }
     return hipGetLastError();
 }
 
 hipError_t launch_wavefront(const LaunchOpts& lo, const SceneView& sc, const FrameParams& fp, const WfBuffers& wb,
                             uint32_t frame0, uint32_t nframes, uint32_t stride, bool accum, bool count, float* out,
-                            Counters* cnt, hipStream_t stream, const WfStreams& ws, float* m2) {
-    if (m2 && !accum) return hipErrorInvalidValue;
+                            Counters* cnt, hipStream_t stream, const WfStreams& ws, float* m2, const RectList* rl) {
+    if ((m2 || rl) && !accum) return hipErrorInvalidValue;
     if (!accum) { nframes = 1; stride = 1; }
     const bool lds = lo.lds && scene_fits_lds(sc);
     // the leaf pass (FLV_PRE) when the scene's table of pre-resolved leaves holds its big leaves
     // (pt_capi.hip shape_view: option leaf_pre, default on) and the buffers exist
     const int trav = select_wavefront(lo, sc.fast_rcp != 0, sc.mailbox != 0, sc.big_leaf > 0, sc.npre > 0 && sc.pre && wb.pres);
     // sc.node_bias <= 0: chosen per instance in wf_render_t
-#define WF_ARGS sc, fp, wb, frame0, nframes, stride, accum, out, cnt, stream, ws, lo, m2
+#define WF_ARGS sc, fp, wb, frame0, nframes, stride, accum, out, cnt, stream, ws, lo, m2, rl
 #define WF(T)                                                                                                        \
     case T:                                                                                                          \
         return lds ? (count ? wf_render_t<true, T, true>(WF_ARGS) : wf_render_t<true, T, false>(WF_ARGS))            \

@@ -245,6 +245,8 @@ typedef struct {
     uint8_t* rgba; /* renderImage: the displayed image instead of the accumulator */
     pt_window win; /* renderWindow: the rectangle of the image to render (has_win) */
     int has_win;
+    pt_window* rects; /* renderRects: the list (malloc'd; win is then its frame), nrects > 0 */
+    size_t nrects;
     pt_counters counters;
     int want_counters; /* optional last argument (default true): counting builds of the kernels */
     int rc;
@@ -256,6 +258,8 @@ static void render_execute(napi_env env, void* data) {
     render_job* j = (render_job*)data;
     pt_counters* c = j->want_counters ? &j->counters : NULL;
     j->rc = j->rgba ? pt_render_image(j->scene, j->meta, j->frame0, j->nframes, j->stride, j->max_depth, j->mode, j->rgba, c)
+            : j->rects ? pt_render_rects(j->scene, j->meta, j->has_win ? &j->win : NULL, j->rects, j->nrects, j->frame0,
+                                         j->nframes, j->stride, j->max_depth, j->mode, j->accum, NULL, c)
                     : pt_render_window(j->scene, j->meta, j->has_win ? &j->win : NULL, j->frame0, j->nframes, j->stride,
                                        j->max_depth, j->mode, j->accum, c);
     if (j->rc) snprintf(j->err, sizeof j->err, "pt_hip error %d: %s", j->rc, pt_last_error());
@@ -276,6 +280,7 @@ static void render_complete(napi_env env, napi_status status, void* data) {
     }
     for (int i = 0; i < 3; ++i) napi_delete_reference(env, j->refs[i]);
     napi_delete_async_work(env, j->work);
+    free(j->rects);
     free(j);
 }
 
@@ -348,18 +353,59 @@ static int parse_render_window_args(napi_env env, napi_callback_info info, rende
     return parse_render_argv(env, argc - 1, argv, j);
 }
 
+/* renderRects' (scene, meta, frame | null, [[x0, y0, w, h], ...], frame0, ...): the frame (null or
+ * undefined: the whole image; the accumulator is the frame's, w*h*3) and a non-empty list of at most
+ * 65536 rectangles; argv comes back without the two, in render()'s order.  The library checks the
+ * list against the frame and for overlaps. */
+#define PT_NODE_MAX_RECTS 65536u
+static int parse_render_rects_args(napi_env env, napi_callback_info info, render_job* j, napi_value argv[9]) {
+    napi_value a[11];
+    size_t argc = 11;
+    if (napi_get_cb_info(env, info, &argc, a, NULL, NULL) != napi_ok || argc < 10 || argc > 11) return 0;
+    napi_valuetype t;
+    if (napi_typeof(env, a[2], &t) != napi_ok) return 0;
+    if (t != napi_null && t != napi_undefined) {
+        if (!parse_window(env, a[2], &j->win)) return 0;
+        j->has_win = 1;
+    }
+    bool is_arr = false;
+    uint32_t n = 0;
+    if (napi_is_array(env, a[3], &is_arr) != napi_ok || !is_arr || napi_get_array_length(env, a[3], &n) != napi_ok ||
+        n < 1 || n > PT_NODE_MAX_RECTS)
+        return 0;
+    j->rects = (pt_window*)malloc((size_t)n * sizeof(pt_window));
+    if (!j->rects) return 0;
+    j->nrects = n;
+    for (uint32_t k = 0; k < n; ++k) {
+        napi_value e;
+        if (napi_get_element(env, a[3], k, &e) != napi_ok || !parse_window(env, e, &j->rects[k])) return 0;
+    }
+    argv[0] = a[0];
+    argv[1] = a[1];
+    for (size_t i = 4; i < argc; ++i) argv[i - 2] = a[i];
+    return parse_render_argv(env, argc - 2, argv, j);
+}
+
 /* render(scene, meta, frame0, nframes, stride, maxDepth, mode, accum[, counters=true]) -> Promise<counters|null>
  * renderWindow(scene, meta, [x0, y0, w, h], frame0, nframes, stride, maxDepth, mode, accum[w*h*3][, counters=true]):
- * the same for a rectangle of the image (pt_render_window) */
+ * the same for a rectangle of the image (pt_render_window)
+ * renderRects(scene, meta, [x0, y0, w, h] | null, [[x0, y0, w, h], ...], frame0, nframes, stride, maxDepth, mode,
+ * accum[frame w*h*3][, counters=true]): the rectangles of the list in one pass, in place inside the
+ * frame's accumulator (pt_render_rects); window: 0 render, 1 renderWindow, 2 renderRects */
 static napi_value render_start(napi_env env, napi_callback_info info, int window) {
     napi_value argv[9];
     render_job* j = (render_job*)calloc(1, sizeof(render_job));
     if (!j) { napi_throw_error(env, NULL, "out of memory"); return NULL; }
-    if (!(window ? parse_render_window_args(env, info, j, argv) : parse_render_args(env, info, j, argv))) {
+    if (!(window == 2   ? parse_render_rects_args(env, info, j, argv)
+          : window == 1 ? parse_render_window_args(env, info, j, argv)
+                        : parse_render_args(env, info, j, argv))) {
+        free(j->rects);
         free(j);
         if (!pending_exception(env))
             napi_throw_type_error(env, NULL,
-                                  window ? "renderWindow(scene, Float32Array meta[48], [x0, y0, w, h], frame0, nframes, stride, "
+                                  window == 2 ? "renderRects(scene, Float32Array meta[48], [x0, y0, w, h] | null, [[x0, y0, w, h], ...], "
+                                                "frame0, nframes, stride, maxDepth, mode, Float32Array accum[frame w*h*3], counters?)"
+                                  : window ? "renderWindow(scene, Float32Array meta[48], [x0, y0, w, h], frame0, nframes, stride, "
                                            "maxDepth, mode, Float32Array accum[w*h*3], counters?)"
                                          : "render(scene, Float32Array meta[48], frame0, nframes, stride, maxDepth, mode, "
                                            "Float32Array accum[W*H*3], counters?)");
@@ -379,6 +425,7 @@ static napi_value render_start(napi_env env, napi_callback_info info, int window
 
 static napi_value js_render(napi_env env, napi_callback_info info) { return render_start(env, info, 0); }
 static napi_value js_render_window(napi_env env, napi_callback_info info) { return render_start(env, info, 1); }
+static napi_value js_render_rects(napi_env env, napi_callback_info info) { return render_start(env, info, 2); }
 
 /* renderMulti([scene, ...], meta, frame0, nframes, stride, maxDepth, mode, accum[, counters=true])
  * -> Promise<counters|null>: one image over one scene per device (pt_render_multi: frames dealt
@@ -708,6 +755,7 @@ static napi_value init(napi_env env, napi_value exports) {
         /* added after the ABI 3 surface: callable by name but not enumerable, so Object.keys(addon) —
          * which tests/test_host_node.py pins — still lists exactly the original set */
         {"renderWindow", NULL, js_render_window, NULL, NULL, NULL, napi_default, NULL},
+        {"renderRects", NULL, js_render_rects, NULL, NULL, NULL, napi_default, NULL},
         {"renderSync", NULL, js_render_sync, NULL, NULL, NULL, napi_enumerable, NULL},
         {"renderMulti", NULL, js_render_multi, NULL, NULL, NULL, napi_enumerable, NULL},
         {"renderImage", NULL, js_render_image, NULL, NULL, NULL, napi_enumerable, NULL},

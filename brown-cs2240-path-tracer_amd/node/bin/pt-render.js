@@ -7,6 +7,8 @@
 // [--vertex-normals 1] (smooth shading from the OBJ normals: the reference's commented-out branch)
 // [--counters 1] (work counters in the JSON line; runs the kernels' counting builds)
 // [--window x0,y0,w,h] (render and write only that rectangle of the image: the crop of the full PNG)
+// [--window "x0,y0,w,h;x0,y0,w,h;..."] (several disjoint rectangles, rendered in one pass: the PNG keeps the
+//  image's size, the rectangles hold the full PNG's pixels and everything else is black)
 const fs = require('fs');
 const path = require('path');
 const host = require('..');
@@ -18,14 +20,18 @@ async function main(argv) {
         else args._.push(argv[i]);
     }
     if (!args._.length) { console.error('usage: pt-render.js <scene.ini> [options]'); process.exit(2); }
-    let window = null;
+    let window = null, rects = null;
     if (args.window !== undefined) {
-        const parts = String(args.window).split(',');
         try {
-            if (!parts.every((v) => /^\d+$/.test(v))) throw Error(`--window ${args.window}`);
-            window = host.check_window(parts.map(Number));
+            const list = String(args.window).split(';').map((one) => {
+                const parts = one.split(',');
+                if (!parts.every((v) => /^\d+$/.test(v))) throw Error(`--window ${args.window}`);
+                return host.check_window(parts.map(Number));
+            });
+            if (list.length > 1) rects = list;
+            else window = list[0];
         } catch (e) {
-            console.error(`usage: pt-render.js <scene.ini> --window x0,y0,w,h (four non-negative integers, w and h at least 1): ${e.message}`);
+            console.error(`usage: pt-render.js <scene.ini> --window x0,y0,w,h[;x0,y0,w,h...] (four non-negative integers, w and h at least 1): ${e.message}`);
             process.exit(2);
         }
     }
@@ -35,15 +41,15 @@ async function main(argv) {
     const t1 = Date.now();
     const r = await host.programEntry(s.screenDimension, s.primitive_data, s.camera_data, s.scene_description, {
         device: parseInt(args.device || '0'), maxDepth: parseInt(args.max_depth || '16'), mode: args.mode || 'auto',
-        vertexNormals: args.vertex_normals === '1', counters: args.counters === '1', window,
+        vertexNormals: args.vertex_normals === '1', counters: args.counters === '1', window, rects,
     });
     const t2 = Date.now();
     const [W, H] = window ? [window[2], window[3]] : s.screenDimension;
     const out = path.join(args.out_root || '.', s.scene_description.IO.output || 'out.png');
     fs.mkdirSync(path.dirname(out), { recursive: true });
     fs.writeFileSync(out, host.encode_png(r.rgba, W, H));
-    const samples = W * H * r.sample_runs;
-    console.log(JSON.stringify({ output: out, width: W, height: H, window, spp: r.sample_runs, scene_ms: t1 - t0,
+    const samples = (rects ? rects.reduce((a, w) => a + w[2] * w[3], 0) : W * H) * r.sample_runs;
+    console.log(JSON.stringify({ output: out, width: W, height: H, window, rects, spp: r.sample_runs, scene_ms: t1 - t0,
         render_ms: t2 - t1, msamples_per_s: samples / ((t2 - t1) / 1000) / 1e6, counters: r.counters }));
 }
 main(process.argv.slice(2)).catch((e) => { console.error(e.stack || String(e)); process.exit(1); });

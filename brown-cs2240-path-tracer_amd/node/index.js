@@ -10,7 +10,7 @@ const { mat4_rot_axis, bounds_of_vec3, chunk_into_3, bounds_bounds_intersection_
 const geometry = require('./lib/geometry');
 const { xml2js } = require('./lib/xml');
 const scene = require('./lib/scene');
-const { programEntry, make_meta, check_window, MODE } = require('./lib/program-entry');
+const { programEntry, make_meta, check_window, check_rects, MODE } = require('./lib/program-entry');
 const { encode_png } = require('./lib/png');
 const addon = require('./lib/addon');
 
@@ -21,5 +21,5 @@ module.exports = {
     parse_scene_xml: scene.parse_scene_xml, pack_primitive: scene.pack_primitive,
     screen_dimension: scene.screen_dimension, load_scene_from_ini: scene.load_scene_from_ini,
     load_scene_xml_file: scene.load_scene_xml_file,
-    programEntry, make_meta, check_window, MODE, encode_png, native: addon.load,
+    programEntry, make_meta, check_window, check_rects, MODE, encode_png, native: addon.load,
 };

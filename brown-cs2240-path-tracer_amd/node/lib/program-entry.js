@@ -38,6 +38,16 @@ function check_window(window) {
     return window.slice();
 }
 
+/** [[x0, y0, w, h], ...]: a non-empty list of windows (the library checks them against the image and for
+ *  overlaps), else an Error; null/undefined: none */
+function check_rects(rects) {
+    if (rects === undefined || rects === null) return null;
+    if (!Array.isArray(rects) || rects.length < 1) throw Error(`rects must be a non-empty list of [x0, y0, w, h], not ${JSON.stringify(rects)}`);
+    return rects.map((r) => {
+        try { return check_window(r || []); } catch (e) { throw Error('rects: ' + e.message); }
+    });
+}
+
 /**
  * programEntry(screenDimension, primitive_data, camera_data, scene_description, options?)
  *   -> Promise<{accum: Float32Array(W*H*3), sample_runs, rgba: Uint8ClampedArray(W*H*4), counters, scene_info}>
@@ -47,7 +57,10 @@ function check_window(window) {
  *           counters=false (work counters: the kernels' counting builds, slower; counters is null without),
  *           window=[x0, y0, w, h] (render that rectangle of the image only: accum is w*h*3 and rgba w*h*4, the
  *           crop of the windowless result — every pixel's samples and its tone map are the full image's; not
- *           with imageOnly or several devices)}
+ *           with imageOnly or several devices),
+ *           rects=[[x0, y0, w, h], ...] (render those disjoint rectangles of the image only, all in one pass per
+ *           chunk (pt_render_rects): accum and rgba stay the full image's size, the rectangles hold the windowless
+ *           result's pixels and everything else is black; not with window, imageOnly or several devices)}
  * imageOnly: render and tone-map on the device in one call and return only {rgba, counters, ...}
  * (no accumulator crosses PCIe; pt_render_image).
  * As in the reference only primitive_data[0] is rendered (program-raymarch.wgsl:31,33).
@@ -61,6 +74,8 @@ async function programEntry(screenDimension, primitive_data, camera_data, scene_
     if (mode === undefined) throw Error(`unknown mode ${o.mode}`);
     const win = check_window(o.window);
     if (win && (o.imageOnly || (o.devices && o.devices.length > 1))) throw Error('window: not with imageOnly or several devices');
+    const rects = check_rects(o.rects);
+    if (rects && (win || o.imageOnly || (o.devices && o.devices.length > 1))) throw Error('rects: not with window, imageOnly or several devices');
     if (o.devices && o.devices.length > 1) return programEntryMulti(pt, meta, W, H, primitive_data, scene_description, o, mode);
     const scene = pt.sceneCreate(primitive_data[0].triangle_data, primitive_data[0].bvh_data,
                                  o.devices && o.devices.length ? o.devices[0] : o.device);
@@ -82,14 +97,15 @@ async function programEntry(screenDimension, primitive_data, camera_data, scene_
         const counters = { samples: 0, ext_queries: 0, shadow_queries: 0, nodes: 0, tri_tests: 0, box_tests: 0 };
         for (let done = 0; done < spp; done += chunk) {
             const n = Math.min(chunk, spp - done);
-            const c = win ? await pt.renderWindow(scene, meta, win, o.frame0 + done, n, 1, o.maxDepth, mode, accum, !!o.counters)
+            const c = rects ? await pt.renderRects(scene, meta, null, rects, o.frame0 + done, n, 1, o.maxDepth, mode, accum, !!o.counters)
+                    : win ? await pt.renderWindow(scene, meta, win, o.frame0 + done, n, 1, o.maxDepth, mode, accum, !!o.counters)
                           : await pt.render(scene, meta, o.frame0 + done, n, 1, o.maxDepth, mode, accum, !!o.counters);
             if (c) for (const k of Object.keys(counters)) counters[k] += c[k];
             if (o.onFrames) o.onFrames(done + n, spp);
         }
         const rgba = new Uint8ClampedArray(npix * 4);
         pt.tonemap(accum, spp, rgba);
-        return { accum, sample_runs: spp, rgba, counters: o.counters ? counters : null, scene_info, window: win };
+        return { accum, sample_runs: spp, rgba, counters: o.counters ? counters : null, scene_info, window: win, rects };
     } finally {
         pt.sceneDestroy(scene);
     }
@@ -115,4 +131,4 @@ async function programEntryMulti(pt, meta, W, H, primitive_data, scene_descripti
     }
 }
 
-module.exports = { programEntry, make_meta, check_window, MODE };
+module.exports = { programEntry, make_meta, check_window, check_rects, MODE };

@@ -31,6 +31,7 @@ from ._lib import (  # noqa: F401
     lib_path,
     load_library,
     options,
+    rect_plan,
     release_communicators,
     render_multi,
     render_tiled,

@@ -14,7 +14,8 @@ _CSRC = os.path.join(_PKG_ROOT, "csrc")
 # csrc/Makefile BUILD_SRCS: the sources whose SHA-256 the library carries as pt_build_id()
 _BUILD_SRCS = ["pt_kernels.hip", "pt_wavefront.hip", "pt_leafpass.hip", "pt_image.hip", "pt_capi.hip", "pt_math.h", "pt_flavour.h", "pt_layout.h",
                "pt_device.h", "pt_path.h", "pt_kernels.h", "../../include/pt_hip.h", "pt_bvh.cpp", "pt_leafbvh.h",
-               "pt_leafbvh.cpp", "pt_leafskip.cpp", "pt_scene_layout.h", "pt_scene_layout.cpp", "Makefile"]
+               "pt_leafbvh.cpp", "pt_leafskip.cpp", "pt_scene_layout.h", "pt_scene_layout.cpp", "pt_rect_plan.h",
+               "pt_rect_plan.cpp", "Makefile"]
 MODE_AUTO, MODE_MEGAKERNEL, MODE_WAVEFRONT = 0, 1, 2
 MATH_FNS = ["sin", "cos", "tan", "acos", "log2", "exp2", "pow", "sqrt", "div", "hash1u", "hash1", "hash2x",
             "hash2y", "min", "max"]
@@ -72,6 +73,21 @@ def _window(window):
     if len(t) != 4:
         raise PtError(-1, f"window must have four values (x0, y0, w, h), not {len(t)}")
     return Window(*[_uint(v, f"window {n}") for v, n in zip(t, ("x0", "y0", "w", "h"))])
+
+
+def _rects(rects):
+    """A list of (x0, y0, w, h) rectangles checked on the host like _window (the library checks the
+    list itself: its length, the areas, the frame, overlaps) as a pt_window array and its length."""
+    try:
+        items = [tuple(r) for r in rects]
+    except TypeError:
+        raise PtError(-1, f"rects must be a sequence of (x0, y0, w, h), not {rects!r}") from None
+    arr = (Window * max(1, len(items)))()
+    for k, t in enumerate(items):
+        if len(t) != 4:
+            raise PtError(-1, f"rects[{k}] must have four values (x0, y0, w, h), not {len(t)}")
+        arr[k] = Window(*[_uint(v, f"rects[{k}] {n}") for v, n in zip(t, ("x0", "y0", "w", "h"))])
+    return arr, len(items)
 
 
 class TileNoise(ctypes.Structure):
@@ -205,6 +221,9 @@ def load_library():
     dbl = ctypes.c_double
     L.pt_render_moments.argtypes = [p, p, wp, u32, u32, u32, i, i, p, p, p]
     L.pt_render_moments_async.argtypes = [p, p, wp, u32, u32, u32, i, i, p, p, sz, p, p]
+    L.pt_render_rects.argtypes = [p, p, wp, wp, sz, u32, u32, u32, i, i, p, p, p]
+    L.pt_render_rects_async.argtypes = [p, p, wp, wp, sz, u32, u32, u32, i, i, p, p, sz, p, p]
+    L.pt_selftest_rect_plan.argtypes = [wp, u32, u32, wp, sz, p, ctypes.POINTER(ctypes.c_uint64)]
     L.pt_noise_tiles_async.argtypes = [p, p, p, u32, u32, sz, u32, u32, p, dbl, dbl, p, p]
     L.pt_noise_tiles.argtypes = [p, p, p, u32, u32, u32, u32, p, dbl, dbl, p]
     L.pt_tile_mean_async.argtypes = [p, p, u32, u32, sz, u32, u32, p, p, p]
@@ -472,6 +491,46 @@ class Scene:
                                                  ctypes.c_void_p(d_counters_ptr or None),
                                                  ctypes.c_void_p(stream_ptr or None)))
 
+    def render_rects(self, meta, rects, frame0: int, nframes: int, stride: int = 1, max_depth: int = -1,
+                     mode: int = MODE_AUTO, accum: np.ndarray | None = None, m2: np.ndarray | None = None,
+                     counters: bool = False, frame=None):
+        """pt_render_rects: the pixels of the (x0, y0, w, h) rectangles of rects (image coordinates,
+        disjoint, inside frame) in ONE pass through the pipeline.  accum (and m2, when given: the second
+        moments too) are [h, w, 3] over frame=(x0, y0, w, h) (None: the whole image), in/out; only the
+        rectangles' pixels change, each to the bits Scene.render(window=...) gives it.  Returns accum,
+        then m2 if given, then the counters if requested (one value: accum alone)."""
+        meta = _f32(meta)
+        fr = _window(frame)
+        arr, n = _rects(rects)
+        W, H = _extent(meta, fr)
+        if accum is None:
+            accum = np.zeros((H, W, 3), np.float32)
+        for a, what in ((accum, "accum"), (m2, "m2")):
+            if a is not None and (not isinstance(a, np.ndarray) or a.dtype != np.float32 or not a.flags.c_contiguous or
+                                  a.size != W * H * 3):
+                raise ValueError(f"{what} must be a contiguous float32 array of H*W*3 elements (the frame's h*w*3)")
+        c = Counters()
+        _check(self._lib.pt_render_rects(self._h, _ptr(meta), ctypes.byref(fr) if fr is not None else None, arr, n, frame0,
+                                         nframes, stride, max_depth, mode, _ptr(accum), _ptr(m2) if m2 is not None else None,
+                                         ctypes.byref(c) if counters else None))
+        out = (accum,) + ((m2,) if m2 is not None else ()) + ((c.as_dict(),) if counters else ())
+        return out[0] if len(out) == 1 else out
+
+    def render_rects_async(self, meta, rects, frame0: int, nframes: int, stride: int, max_depth: int, mode: int,
+                           d_accum_ptr: int, d_m2_ptr: int = 0, row_pitch=None, stream_ptr: int = 0,
+                           d_counters_ptr: int = 0, frame=None):
+        """pt_render_rects_async: d_accum_ptr (and d_m2_ptr, 0: no moments) address the FIRST pixel of
+        frame (None: the image) in device buffers whose rows are row_pitch pixels apart (default: the
+        frame's width); nothing outside the rectangles is read or written."""
+        meta = _f32(meta)
+        fr = _window(frame)
+        arr, n = _rects(rects)
+        pitch = _extent(meta, fr)[0] if row_pitch is None else _uint(row_pitch, "row_pitch")
+        _check(self._lib.pt_render_rects_async(self._h, _ptr(meta), ctypes.byref(fr) if fr is not None else None, arr, n,
+                                               frame0, nframes, stride, max_depth, mode, ctypes.c_void_p(d_accum_ptr),
+                                               ctypes.c_void_p(d_m2_ptr or None), pitch,
+                                               ctypes.c_void_p(d_counters_ptr or None), ctypes.c_void_p(stream_ptr or None)))
+
     def noise_tiles(self, accum, m2, tile, frames, tol: float, floor: float) -> np.ndarray:
         """pt_noise_tiles: the noise verdict of every tile of tile=(tile_w, tile_h) pixels over the host
         accumulators accum and m2 [h, w, 3]; frames [TY, TX] are the tiles' sample counts.  Returns a
@@ -657,6 +716,19 @@ def tile_rects(active) -> np.ndarray:
     n = ctypes.c_size_t(0)
     _check(load_library().pt_selftest_tile_rects(_ptr(a), tx, ty, _ptr(out), out.shape[0], ctypes.byref(n)))
     return out[: n.value]
+
+
+def rect_plan(rects, W: int, H: int, frame=None):
+    """pt_selftest_rect_plan (host only): a rectangle list checked as pt_render_rects checks it, for a
+    W x H image and frame=(x0, y0, w, h) (None: the image).  Returns (first, npix): every rectangle's
+    first slot [n] u64 — the prefix sums of w * h in list order — and the list's pixels per frame."""
+    fr = _window(frame)
+    arr, n = _rects(rects)
+    first = np.zeros(max(1, n), np.uint64)
+    npix = ctypes.c_uint64(0)
+    _check(load_library().pt_selftest_rect_plan(ctypes.byref(fr) if fr is not None else None, _uint(W, "W"), _uint(H, "H"),
+                                                arr, n, _ptr(first), ctypes.byref(npix)))
+    return first[:n], int(npix.value)
 
 
 def tonemap(accum, sample_runs: int) -> np.ndarray:

@@ -163,6 +163,33 @@ int pt_render_moments_async(pt_scene* scene, const float meta[48], const pt_wind
                             uint32_t nframes, uint32_t frame_stride, int max_depth, int mode, float* d_accum,
                             float* d_m2, size_t row_pitch, pt_counters* d_counters, void* stream);
 
+/* Render frames frame0 + i*stride (i < nframes) of the pixels of n rectangles of the image, in ONE
+ * pass through the pipeline: the paths of all rectangles share the call's batches and launches.
+ * rects: image coordinates, each inside `frame` (NULL = the whole image), pairwise disjoint, w,h >= 1,
+ * 1 <= n <= 65536, in any order.  Destination: d_accum points at frame's first pixel, rows row_pitch
+ * pixels apart (>= frame->w); pixel (x, y) of a rectangle lives at
+ * d_accum + 3*((y - frame.y0)*row_pitch + (x - frame.x0)); in/out; nothing outside the rectangles is
+ * read or written.  d_m2: nullable, second moments at the same places (pt_render_moments' rule).
+ * Every pixel gets the bits of pt_render_window[_moments] of any window that holds it.
+ * A path's id is f * npix + q: npix the sum of the rectangles' areas ("paths per frame" for AUTO's
+ * choice of pipeline, the batches and the counters), q the pixel's position in the concatenation of
+ * the rectangles in list order, row-major inside each.  An empty list, n > 65536, a rectangle of no
+ * area or outside frame or the image, and any two rectangles that share a pixel (two slots on one
+ * pixel would race in the accumulation) fail with PT_ERR_INVALID before anything is launched or
+ * copied; pt_last_error() names the offending rectangle(s).  The rectangle table lives in device
+ * memory of the scene and is written on `stream` before the first launch. */
+int pt_render_rects_async(pt_scene* scene, const float meta[48], const pt_window* frame, const pt_window* rects,
+                          size_t n, uint32_t frame0, uint32_t nframes, uint32_t frame_stride, int max_depth, int mode,
+                          float* d_accum, float* d_m2, size_t row_pitch, pt_counters* d_counters, void* stream);
+/* Blocking, host buffers: accum (and nullable m2) dense [frame.h][frame.w][3], in/out. */
+int pt_render_rects(pt_scene* scene, const float meta[48], const pt_window* frame, const pt_window* rects, size_t n,
+                    uint32_t frame0, uint32_t nframes, uint32_t frame_stride, int max_depth, int mode, float* accum,
+                    float* m2, pt_counters* counters);
+/* Host only, for tests: validates a list and writes each rectangle's first slot (prefix sum of w*h in
+ * list order) and *npix_out = the pixels per frame.  W, H: the image's size; first_out, npix_out: nullable. */
+int pt_selftest_rect_plan(const pt_window* frame, uint32_t W, uint32_t H, const pt_window* rects, size_t n,
+                          uint64_t* first_out, uint64_t* npix_out);
+
 /* A tile's noise verdict: its pixels, how many of them are noisy, and the largest error estimate. */
 typedef struct { uint32_t noisy, pixels; double max_err; } pt_tile_noise; /* 16 B */
 
@@ -202,8 +229,8 @@ typedef struct {
  * with moments.  After each pass pt_noise_tiles_async judges every tile; a tile stays active iff
  * noisy > (uint32_t)(noisy_fraction * pixels) and its frames < max_frames, and every active tile gets
  * the next min(step_frames, max_frames - frames) frames (a tile that stops never restarts, so the
- * active tiles share one frame count) as in-place window renders of the active set's rectangles
- * (pt_selftest_tile_rects).  A tile with n frames holds the bits of that rectangle of a plain n-frame
+ * active tiles share one frame count) as ONE in-place list render (pt_render_rects_async) of the
+ * active set's rectangles (pt_selftest_tile_rects).  A tile with n frames holds the bits of that rectangle of a plain n-frame
  * render.  Outputs (host, written, not read): accum and m2 [h][w][3], tile_frames [TY][TX],
  * tile_noise [TY][TX] (the last verdicts), rgba [h][w][4] = the display transform of the per-tile
  * mean (pt_tile_mean_async, then sample_runs = 1), counters = the sum over all passes, passes = the
