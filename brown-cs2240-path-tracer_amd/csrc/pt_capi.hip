@@ -63,6 +63,7 @@ constexpr OptSpec kOptSpecs[] = {
     {"leaf_skip", OPT_BOOL, nullptr},
     {"mb_uid_order", OPT_ENUM, "forward|reverse"},
     {"reduce", OPT_ENUM, "rccl|ordered"},
+    {"denoise_lds", OPT_ENUM, "0|1|2|3|4"},
 };
 constexpr int kNumOpts = (int)(sizeof(kOptSpecs) / sizeof(kOptSpecs[0]));
 
@@ -192,6 +193,11 @@ struct pt_scene {
     // a rectangle-list render's table (pt_render_rects): the rows, then the megakernel's blocks; written
     // on the call's stream before its first launch, so calls in stream order may share it
     Scratch<char> d_rects;
+    // the denoiser's four w * h float4 planes (pt_denoise_async: two ping-pong (c, var), (N, Z), (A, 0);
+    // counted in info.device_bytes while held), and the scratch of its blocking calls: the guide buffers
+    // (geo, then alb) and the filtered variance
+    Scratch<float4> d_dn;
+    Scratch<float> d_feat, d_var;
     WfStreams ws;  // dual-stream wavefront: aux stream + fork/join events (created with d_wf)
     // pinned mirror of the wavefront control words, copied after every wavefront render on its
     // stream: a watchdog flag set by an asynchronous render surfaces once that copy has landed
@@ -454,6 +460,7 @@ void pt_scene_destroy(pt_scene* s) {
     if (s->d_rad) hipFree(s->d_rad);
     if (s->d_pres) hipFree(s->d_pres);
     s->d_accum.free(); s->d_m2.free(); s->d_mean.free(); s->d_peer.free(); s->d_rgba.free(); s->d_tiles.free(); s->d_rects.free();
+    s->d_dn.free(); s->d_feat.free(); s->d_var.free();
     if (s->h_ctl) hipHostFree(s->h_ctl);
     if (s->d_mem) hipFree(s->d_mem);
     s->prof.destroy();
@@ -567,6 +574,10 @@ LaunchOpts launch_opts(const Opts& o, int mode, uint64_t paths, const SceneView&
 // (probe of option wf_paths)
 constexpr uint64_t kWfTargetPaths = 64ull << 20;
 constexpr int kBigLeafDefault = 128;
+// option denoise_lds: how many of the denoiser's first passes stage their taps in LDS (0..4).  Measured at
+// 1024^2 (profiles/denoise_bench.jsonl): staged, the passes with steps 1 and 2 take 0.06 ms
+// against 0.10 and 0.09; the pass with step 4 is 4-13 % slower staged, the one with step 8 two thirds slower
+constexpr long kDenoiseLdsDefault = 2;
 constexpr long kPreRatioDefault = 50;  // shape_view: the leaf pass when >= 50 % of its work is visited
 
 int ensure_rad(pt_scene* s, uint64_t paths) {
@@ -1245,6 +1256,196 @@ int pt_render_adaptive(pt_scene* s, const float meta[48], const pt_window* win, 
     std::memcpy(tile_frames, frames.data(), T * sizeof(uint32_t));
     if (tile_noise) std::memcpy(tile_noise, noise.data(), T * sizeof(pt_tile_noise));
     if (passes) *passes = npass;
+    return take_watchdog(s);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Guide buffers and the denoiser (pt_features.hip, pt_denoise.hip)
+// ---------------------------------------------------------------------------------------------
+static int features_impl(pt_scene* s, const float* meta, const pt_window* win, const size_t* pitch, uint32_t frame0,
+                         uint32_t nframes, uint32_t stride, float* d_geo, float* d_alb, Counters* d_cnt, hipStream_t stream) {
+    FrameParams fp{};
+    int rc = make_params(meta, 0, fp, win, pitch);
+    if (rc != PT_OK) return rc;
+    if ((uint64_t)frame0 + (uint64_t)(nframes ? nframes - 1 : 0) * stride >= (1ull << 24))
+        return fail(PT_ERR_INVALID, "frame index >= 2^24 (t_k = u32(f32(k)) would round)");
+    if (((uintptr_t)d_geo | (uintptr_t)d_alb) & 15u) return fail(PT_ERR_INVALID, "geo and alb must be 16-byte aligned");
+    HIP_TRY(hipSetDevice(s->device));
+    if (nframes == 0) return PT_OK;
+    ProfScope prof_scope(s);
+    // the scene as the default megakernel instance sees it: no option chooses this kernel's flavour
+    SceneView view;
+    if ((rc = shape_view(s, Opts{}, fp, PT_MODE_MEGAKERNEL, (uint64_t)fp.win_w * fp.win_h * nframes, view)) != PT_OK) return rc;
+    if ((rc = take_watchdog(s)) != PT_OK) return rc;  // an earlier asynchronous render failed
+    HIP_TRY(launch_features(view, fp, frame0, nframes, stride, d_cnt != nullptr, d_geo, d_alb, d_cnt, stream));
+    return PT_OK;
+}
+
+int pt_render_features_async(pt_scene* s, const float meta[48], const pt_window* win, uint32_t frame0, uint32_t nframes,
+                             uint32_t frame_stride, float* d_geo, float* d_alb, size_t row_pitch, pt_counters* d_counters,
+                             void* stream) {
+    if (!s || !meta || !d_geo || !d_alb) return fail(PT_ERR_INVALID, "null argument");
+    return features_impl(s, meta, win, &row_pitch, frame0, nframes, frame_stride, d_geo, d_alb,
+                         reinterpret_cast<Counters*>(d_counters), static_cast<hipStream_t>(stream));
+}
+
+int pt_render_features(pt_scene* s, const float meta[48], const pt_window* win, uint32_t frame0, uint32_t nframes,
+                       uint32_t frame_stride, float* geo, float* alb, pt_counters* counters) {
+    if (!s || !meta || !geo || !alb) return fail(PT_ERR_INVALID, "null argument");
+    FrameParams fp{};
+    int rc = make_params(meta, 0, fp, win);
+    if (rc != PT_OK) return rc;
+    const size_t n = (size_t)4 * fp.win_w * fp.win_h;
+    HIP_TRY(hipSetDevice(s->device));
+    if ((rc = s->d_feat.ensure(2 * n, "guide buffers")) != PT_OK || (rc = blocking_stream(s)) != PT_OK) return rc;
+    float* const d_geo = s->d_feat.p;
+    float* const d_alb = s->d_feat.p + n;
+    Counters* d_cnt = counters ? s->d_counters : nullptr;
+    HIP_TRY(hipMemcpyAsync(d_geo, geo, n * sizeof(float), hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipMemcpyAsync(d_alb, alb, n * sizeof(float), hipMemcpyHostToDevice, s->stream));
+    if (d_cnt) HIP_TRY(hipMemsetAsync(d_cnt, 0, sizeof(Counters), s->stream));
+    if ((rc = features_impl(s, meta, win, nullptr, frame0, nframes, frame_stride, d_geo, d_alb, d_cnt, s->stream)) != PT_OK)
+        return rc;
+    HIP_TRY(hipMemcpyAsync(geo, d_geo, n * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipMemcpyAsync(alb, d_alb, n * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+    if (d_cnt) HIP_TRY(hipMemcpyAsync(counters, d_cnt, sizeof(Counters), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return take_watchdog(s);
+}
+
+void pt_denoise_defaults(pt_denoise_params* p) {
+    if (p) *p = pt_denoise_params{4u, 0.5f, 0.3f, 0.1f, 4.0f};
+}
+
+static int check_denoise(const pt_denoise_params& p, uint32_t feature_frames) {
+    if (p.iters < 1 || p.iters > 5) return fail(PT_ERR_INVALID, "pt_denoise_params: iters must lie in [1, 5]");
+    const float sg[4] = {p.sigma_n, p.sigma_a, p.sigma_z, p.sigma_l};
+    static const char* const names[4] = {"sigma_n", "sigma_a", "sigma_z", "sigma_l"};
+    for (int k = 0; k < 4; ++k)
+        if (!(std::isfinite(sg[k]) && sg[k] > 0.0f))
+            return fail(PT_ERR_INVALID, std::string("pt_denoise_params: ") + names[k] + " must be finite and > 0");
+    if (feature_frames < 1) return fail(PT_ERR_INVALID, "feature_frames must be at least 1");
+    return PT_OK;
+}
+
+int pt_denoise_async(pt_scene* s, const float* d_accum, const float* d_m2, uint32_t w, uint32_t h, size_t row_pitch,
+                     uint32_t tile_w, uint32_t tile_h, const uint32_t* d_frames, const float* d_geo, const float* d_alb,
+                     uint32_t feature_frames, const pt_denoise_params* p, float* d_out, float* d_var_out, void* stream) {
+    if (!s || !d_accum || !d_m2 || !d_frames || !d_geo || !d_alb || !d_out) return fail(PT_ERR_INVALID, "null argument");
+    pt_denoise_params prm;
+    pt_denoise_defaults(&prm);
+    if (p) prm = *p;
+    TileGrid g{};
+    int rc = check_denoise(prm, feature_frames);
+    if (rc != PT_OK || (rc = make_grid(w, h, row_pitch, tile_w, tile_h, g)) != PT_OK) return rc;
+    if (((uintptr_t)d_geo | (uintptr_t)d_alb) & 15u) return fail(PT_ERR_INVALID, "geo and alb must be 16-byte aligned");
+    const size_t npix = (size_t)w * h;
+    HIP_TRY(hipSetDevice(s->device));
+    {
+        const size_t before = s->d_dn.cap;
+        if ((rc = s->d_dn.ensure(4 * npix, "denoiser planes")) != PT_OK) {
+            s->info.device_bytes -= before * sizeof(float4);  // (ensure frees before it allocates)
+            return rc;
+        }
+        s->info.device_bytes += (s->d_dn.cap - before) * sizeof(float4);
+    }
+    float4* const cv[2] = {s->d_dn.p, s->d_dn.p + npix};
+    float4* const nz = s->d_dn.p + 2 * npix;
+    float4* const ab = s->d_dn.p + 3 * npix;
+    // host constants: double, rounded once
+    const float isn = (float)(1.0 / ((double)prm.sigma_n * (double)prm.sigma_n));
+    const float isa = (float)(1.0 / ((double)prm.sigma_a * (double)prm.sigma_a));
+    const float isz = (float)(1.0 / (double)prm.sigma_z);
+    // option denoise_lds = v: the first v passes (steps 1 .. 2^(v-1)) read their taps through LDS
+    const uint32_t staged = (uint32_t)opts_snapshot().num("denoise_lds", kDenoiseLdsDefault);
+    ProfScope prof_scope(s);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    HIP_TRY(launch_denoise_prepare(d_accum, d_m2, d_geo, d_alb, g, d_frames, feature_frames, cv[0], nz, ab, st));
+    for (uint32_t i = 0; i < prm.iters; ++i) {
+        const uint32_t step = 1u << i;
+        const bool last = i + 1 == prm.iters;
+        HIP_TRY(launch_atrous(cv[i & 1], nz, ab, w, h, step, isn, isa, isz, prm.sigma_l, i < staged && atrous_can_stage(step),
+                              last ? nullptr : cv[(i & 1) ^ 1], last ? d_out : nullptr, last ? d_var_out : nullptr,
+                              g.row_pitch, st));
+    }
+    return PT_OK;
+}
+
+int pt_denoise(pt_scene* s, const float* accum, const float* m2, uint32_t w, uint32_t h, uint32_t tile_w, uint32_t tile_h,
+               const uint32_t* frames, const float* geo, const float* alb, uint32_t feature_frames,
+               const pt_denoise_params* p, float* out, float* var_out) {
+    if (!s || !accum || !m2 || !frames || !geo || !alb || !out) return fail(PT_ERR_INVALID, "null argument");
+    pt_denoise_params prm;
+    pt_denoise_defaults(&prm);
+    if (p) prm = *p;
+    TileGrid g{};
+    int rc = check_denoise(prm, feature_frames);
+    if (rc != PT_OK || (rc = make_grid(w, h, w, tile_w, tile_h, g)) != PT_OK) return rc;
+    const size_t npix = (size_t)w * h, n = 3 * npix, T = (size_t)g.tx * g.ty;
+    HIP_TRY(hipSetDevice(s->device));
+    pt_tile_noise* d_noise = nullptr;
+    uint32_t* d_frames = nullptr;
+    if ((rc = s->d_accum.ensure(n, "accumulator")) != PT_OK || (rc = s->d_m2.ensure(n, "second moments")) != PT_OK ||
+        (rc = s->d_mean.ensure(n, "filtered image")) != PT_OK || (rc = s->d_feat.ensure(8 * npix, "guide buffers")) != PT_OK ||
+        (rc = s->d_var.ensure(npix, "filtered variance")) != PT_OK || (rc = ensure_tiles(s, T, d_noise, d_frames)) != PT_OK ||
+        (rc = blocking_stream(s)) != PT_OK)
+        return rc;
+    float* const d_geo = s->d_feat.p;
+    float* const d_alb = s->d_feat.p + 4 * npix;
+    HIP_TRY(hipMemcpyAsync(s->d_accum.p, accum, n * sizeof(float), hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipMemcpyAsync(s->d_m2.p, m2, n * sizeof(float), hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipMemcpyAsync(d_geo, geo, 4 * npix * sizeof(float), hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipMemcpyAsync(d_alb, alb, 4 * npix * sizeof(float), hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipMemcpyAsync(d_frames, frames, T * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
+    if ((rc = pt_denoise_async(s, s->d_accum.p, s->d_m2.p, w, h, w, tile_w, tile_h, d_frames, d_geo, d_alb, feature_frames,
+                               &prm, s->d_mean.p, var_out ? s->d_var.p : nullptr, s->stream)) != PT_OK)
+        return rc;
+    HIP_TRY(hipMemcpyAsync(out, s->d_mean.p, n * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+    if (var_out) HIP_TRY(hipMemcpyAsync(var_out, s->d_var.p, npix * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return PT_OK;
+}
+
+int pt_render_denoised_image(pt_scene* s, const float meta[48], uint32_t frame0, uint32_t nframes, uint32_t frame_stride,
+                             int max_depth, int mode, uint32_t feature_frames, const pt_denoise_params* params,
+                             uint8_t* rgba, pt_counters* counters) {
+    if (!s || !meta || !rgba) return fail(PT_ERR_INVALID, "null argument");
+    if (nframes < 2) return fail(PT_ERR_INVALID, "nframes must be at least 2 (the variance needs two samples)");
+    pt_denoise_params prm;
+    pt_denoise_defaults(&prm);
+    if (params) prm = *params;
+    int rc = check_denoise(prm, feature_frames);
+    if (rc != PT_OK) return rc;
+    FrameParams fp{};
+    if ((rc = make_params(meta, max_depth, fp)) != PT_OK) return rc;
+    const uint32_t W = fp.width, H = fp.height;
+    const size_t npix = (size_t)W * H, n = 3 * npix;
+    HIP_TRY(hipSetDevice(s->device));
+    pt_tile_noise* d_noise = nullptr;
+    uint32_t* d_frames = nullptr;
+    if ((rc = s->d_accum.ensure(n, "accumulator")) != PT_OK || (rc = s->d_m2.ensure(n, "second moments")) != PT_OK ||
+        (rc = s->d_mean.ensure(n, "filtered image")) != PT_OK || (rc = s->d_feat.ensure(8 * npix, "guide buffers")) != PT_OK ||
+        (rc = s->d_rgba.ensure(4 * npix, "image")) != PT_OK || (rc = ensure_tiles(s, 1, d_noise, d_frames)) != PT_OK ||
+        (rc = blocking_stream(s)) != PT_OK)
+        return rc;
+    float* const d_geo = s->d_feat.p;
+    float* const d_alb = s->d_feat.p + 4 * npix;
+    Counters* d_cnt = counters ? s->d_counters : nullptr;
+    HIP_TRY(hipMemsetAsync(s->d_accum.p, 0, n * sizeof(float), s->stream));
+    HIP_TRY(hipMemsetAsync(s->d_m2.p, 0, n * sizeof(float), s->stream));
+    HIP_TRY(hipMemsetAsync(s->d_feat.p, 0, 8 * npix * sizeof(float), s->stream));
+    HIP_TRY(hipMemcpyAsync(d_frames, &nframes, sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
+    if (d_cnt) HIP_TRY(hipMemsetAsync(d_cnt, 0, sizeof(Counters), s->stream));
+    if ((rc = render_impl(s, meta, frame0, nframes, frame_stride, max_depth, mode, true, s->d_accum.p, d_cnt, s->stream, nullptr,
+                          nullptr, s->d_m2.p)) != PT_OK ||
+        (rc = features_impl(s, meta, nullptr, nullptr, frame0, feature_frames, 1, d_geo, d_alb, d_cnt, s->stream)) != PT_OK ||
+        (rc = pt_denoise_async(s, s->d_accum.p, s->d_m2.p, W, H, W, W, H, d_frames, d_geo, d_alb, feature_frames, &prm,
+                               s->d_mean.p, nullptr, s->stream)) != PT_OK ||
+        (rc = pt_tonemap_async(s, s->d_mean.p, npix, 1, s->d_rgba.p, s->stream)) != PT_OK)
+        return rc;
+    HIP_TRY(hipMemcpyAsync(rgba, s->d_rgba.p, 4 * npix, hipMemcpyDeviceToHost, s->stream));
+    if (d_cnt) HIP_TRY(hipMemcpyAsync(counters, d_cnt, sizeof(Counters), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
     return take_watchdog(s);
 }
 

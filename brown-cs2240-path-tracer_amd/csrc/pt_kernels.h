@@ -20,12 +20,14 @@ namespace pt {
 // calling thread, every launch is bracketed by two HIP events on its stream.
 enum KernelId : int {
     KID_MEGA = 0, KID_REGEN, KID_WF_GENERATE, KID_WF_TRACE, KID_WF_SHADE_EXT, KID_WF_SHADE_SHADOW, KID_WF_ACCUM,
-    KID_TONEMAP, KID_WF_STEP, KID_WF_LEAF, KID_NOISE_TILES, KID_TILE_MEAN, KID_COUNT
+    KID_TONEMAP, KID_WF_STEP, KID_WF_LEAF, KID_NOISE_TILES, KID_TILE_MEAN, KID_FEATURES, KID_DENOISE_PREPARE, KID_ATROUS,
+    KID_COUNT
 };
 inline const char* kernel_name(int k) {
     static const char* const n[KID_COUNT] = {"k_mega",         "k_regen",           "k_wf_generate", "k_wf_trace",
                                              "k_wf_shade_ext", "k_wf_shade_shadow", "k_wf_accum",    "k_tonemap",
-                                             "k_wf_step",      "k_wf_leafpass",     "k_noise_tiles", "k_tile_mean"};
+                                             "k_wf_step",      "k_wf_leafpass",     "k_noise_tiles", "k_tile_mean",
+                                             "k_features",     "k_denoise_prepare", "k_atrous"};
     return (k >= 0 && k < KID_COUNT) ? n[k] : "?";
 }
 struct KernelProfiler {
@@ -156,6 +158,22 @@ struct TileNoise { uint32_t noisy, pixels; double max_err; };              // pt
 hipError_t launch_noise_tiles(const float* acc, const float* m2, const TileGrid& g, const uint32_t* frames, double tol,
                               double floor, TileNoise* out, hipStream_t stream);
 hipError_t launch_tile_mean(const float* acc, const TileGrid& g, const uint32_t* frames, float* mean, hipStream_t stream);
+// guide buffers of the first hit (pt_features.hip; pt_hip.h pt_render_features_async): geo += (n, t),
+// alb += (albedo, 1) per frame and hit, four floats per pixel, rows fp.row_pitch pixels apart
+hipError_t launch_features(const SceneView& sc, const FrameParams& fp, uint32_t frame0, uint32_t nframes, uint32_t stride,
+                           bool count, float* geo, float* alb, Counters* cnt, hipStream_t stream);
+// the a-trous denoiser (pt_denoise.hip; pt_hip.h pt_denoise_async).  prepare: the accumulators and the
+// guides (g: the tile grid of frames, g.row_pitch the pitch of all four inputs) -> three dense planes
+// of g.w * g.h float4: cv (c.rgb, var), nz (N.xyz, Z), ab (A.rgb, 0).  atrous: one pass with step s
+// from cv to cv_out (nullable) and, the last pass, to out [h][w][3] and var_out (nullable) [h][w],
+// rows row_pitch pixels apart; staged: the block's region through LDS (atrous_can_stage(s)), same bits.
+hipError_t launch_denoise_prepare(const float* acc, const float* m2, const float* geo, const float* alb, const TileGrid& g,
+                                  const uint32_t* frames, uint32_t feature_frames, float4* cv, float4* nz, float4* ab,
+                                  hipStream_t stream);
+bool atrous_can_stage(uint32_t s);
+hipError_t launch_atrous(const float4* cv, const float4* nz, const float4* ab, uint32_t w, uint32_t h, uint32_t s, float isn,
+                         float isa, float isz, float sigma_l, bool staged, float4* cv_out, float* out, float* var_out,
+                         uint32_t row_pitch, hipStream_t stream);
 // n floats from device memory to pinned host memory (h_dst_dev: its device address; pt_image.hip)
 hipError_t launch_readback(const float* d_src, float* h_dst_dev, size_t n, hipStream_t stream);
 // dst[i] += src[i] for i < n (f32; both on the stream's device; pt_image.hip)

@@ -609,6 +609,37 @@ static napi_value js_frame(napi_env env, napi_callback_info info) {
     return NULL;
 }
 
+/* renderDenoised(scene, meta, frame0, nframes, stride, maxDepth, mode, featureFrames, iters, Uint8Array rgba[W*H*4]):
+ * pt_render_denoised_image — a moments render, the guide buffers, the a-trous filter and the device tone
+ * map in one blocking call; iters 0 = pt_denoise_defaults, else the defaults with that many passes */
+static napi_value js_render_denoised(napi_env env, napi_callback_info info) {
+    size_t argc = 10;
+    napi_value argv[10];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    float* meta;
+    uint8_t* out;
+    size_t ml, ol;
+    uint32_t frame0, nframes, stride, ff, iters;
+    int32_t md, mode;
+    pt_scene* s = argc >= 10 ? get_scene(env, argv[0]) : NULL;
+    if (!s || !get_f32(env, argv[1], &meta, &ml) || ml < 48 || !get_u32(env, argv[2], &frame0) ||
+        !get_u32(env, argv[3], &nframes) || !get_u32(env, argv[4], &stride) || !get_i32(env, argv[5], &md) ||
+        !get_i32(env, argv[6], &mode) || !get_u32(env, argv[7], &ff) || !get_u32(env, argv[8], &iters) ||
+        !get_u8(env, argv[9], &out, &ol) || ol != (size_t)meta[0] * (size_t)meta[1] * 4) {
+        if (!pending_exception(env))
+            napi_throw_type_error(env, NULL,
+                                  "renderDenoised(scene, Float32Array meta[48], frame0, nframes, stride, maxDepth, mode, "
+                                  "featureFrames, iters, Uint8Array rgba[W*H*4])");
+        return NULL;
+    }
+    pt_denoise_params p;
+    pt_denoise_defaults(&p);
+    if (iters) p.iters = iters;
+    int rc = pt_render_denoised_image(s, meta, frame0, nframes, stride, md, mode, ff, &p, out, NULL);
+    if (rc) return throw_pt(env, rc);
+    return NULL;
+}
+
 /* tonemap(accum Float32Array, sampleRuns, out Uint8Array[npix*4]) */
 static napi_value js_tonemap(napi_env env, napi_callback_info info) {
     size_t argc = 3;
@@ -759,6 +790,7 @@ static napi_value init(napi_env env, napi_value exports) {
         {"renderSync", NULL, js_render_sync, NULL, NULL, NULL, napi_enumerable, NULL},
         {"renderMulti", NULL, js_render_multi, NULL, NULL, NULL, napi_enumerable, NULL},
         {"renderImage", NULL, js_render_image, NULL, NULL, NULL, napi_enumerable, NULL},
+        {"renderDenoised", NULL, js_render_denoised, NULL, NULL, NULL, napi_default, NULL},
         {"frame", NULL, js_frame, NULL, NULL, NULL, napi_enumerable, NULL},
         {"tonemap", NULL, js_tonemap, NULL, NULL, NULL, napi_enumerable, NULL},
         {"profileEnable", NULL, js_profile_enable, NULL, NULL, NULL, napi_enumerable, NULL},

@@ -9,6 +9,8 @@
 // [--window x0,y0,w,h] (render and write only that rectangle of the image: the crop of the full PNG)
 // [--window "x0,y0,w,h;x0,y0,w,h;..."] (several disjoint rectangles, rendered in one pass: the PNG keeps the
 //  image's size, the rectangles hold the full PNG's pixels and everything else is black)
+// [--denoise [iters]] (the variance-guided a-trous denoiser, pt_render_denoised_image: 1..5 passes, default the
+//  library's; the whole image only, without --counters, --spp at least 2) [--feature-frames N] (frames of its guide buffers, default 4)
 const fs = require('fs');
 const path = require('path');
 const host = require('..');
@@ -16,7 +18,8 @@ const host = require('..');
 async function main(argv) {
     const args = { _: [] };
     for (let i = 0; i < argv.length; i++) {
-        if (argv[i].startsWith('--')) args[argv[i].slice(2).replace(/-/g, '_')] = argv[++i];
+        if (argv[i] === '--denoise' && (i + 1 >= argv.length || argv[i + 1].startsWith('--'))) args.denoise = '';
+        else if (argv[i].startsWith('--')) args[argv[i].slice(2).replace(/-/g, '_')] = argv[++i];
         else args._.push(argv[i]);
     }
     if (!args._.length) { console.error('usage: pt-render.js <scene.ini> [options]'); process.exit(2); }
@@ -35,13 +38,25 @@ async function main(argv) {
             process.exit(2);
         }
     }
+    let denoise = null;
+    if (args.denoise !== undefined || args.feature_frames !== undefined) {
+        const it = args.denoise === undefined || args.denoise === '' ? '0' : String(args.denoise);
+        const ff = args.feature_frames === undefined ? '4' : String(args.feature_frames);
+        if (args.denoise === undefined || !/^\d+$/.test(it) || !/^\d+$/.test(ff) || (it !== '0' && !(+it >= 1 && +it <= 5)) ||
+            (args.denoise !== '' && it === '0') || !(+ff >= 1 && +ff <= 0xffffffff) || window || rects || args.counters === '1') {
+            console.error('usage: pt-render.js <scene.ini> --denoise [iters] [--feature-frames N] (iters 1..5, N at least 1; ' +
+                          `not with --window or --counters 1): --denoise ${args.denoise} --feature-frames ${args.feature_frames}`);
+            process.exit(2);
+        }
+        denoise = { iters: +it, featureFrames: +ff };
+    }
     const t0 = Date.now();
     const s = host.load_scene_from_ini(args._[0], { web_root: args.web_root, quiet: true });
     if (args.spp) s.scene_description.Settings.samplesPerPixel = parseInt(args.spp);
     const t1 = Date.now();
     const r = await host.programEntry(s.screenDimension, s.primitive_data, s.camera_data, s.scene_description, {
         device: parseInt(args.device || '0'), maxDepth: parseInt(args.max_depth || '16'), mode: args.mode || 'auto',
-        vertexNormals: args.vertex_normals === '1', counters: args.counters === '1', window, rects,
+        vertexNormals: args.vertex_normals === '1', counters: args.counters === '1', window, rects, denoise,
     });
     const t2 = Date.now();
     const [W, H] = window ? [window[2], window[3]] : s.screenDimension;
@@ -50,6 +65,6 @@ async function main(argv) {
     fs.writeFileSync(out, host.encode_png(r.rgba, W, H));
     const samples = (rects ? rects.reduce((a, w) => a + w[2] * w[3], 0) : W * H) * r.sample_runs;
     console.log(JSON.stringify({ output: out, width: W, height: H, window, rects, spp: r.sample_runs, scene_ms: t1 - t0,
-        render_ms: t2 - t1, msamples_per_s: samples / ((t2 - t1) / 1000) / 1e6, counters: r.counters }));
+        denoise, render_ms: t2 - t1, msamples_per_s: samples / ((t2 - t1) / 1000) / 1e6, counters: r.counters }));
 }
 main(process.argv.slice(2)).catch((e) => { console.error(e.stack || String(e)); process.exit(1); });

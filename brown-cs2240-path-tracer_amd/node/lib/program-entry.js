@@ -60,7 +60,11 @@ function check_rects(rects) {
  *           with imageOnly or several devices),
  *           rects=[[x0, y0, w, h], ...] (render those disjoint rectangles of the image only, all in one pass per
  *           chunk (pt_render_rects): accum and rgba stay the full image's size, the rectangles hold the windowless
- *           result's pixels and everything else is black; not with window, imageOnly or several devices)}
+ *           result's pixels and everything else is black; not with window, imageOnly or several devices),
+ *           denoise={iters=0 (the library's default), featureFrames=4} (the displayed image through the
+ *           variance-guided a-trous denoiser, pt_render_denoised_image: returns only {rgba, ...} like imageOnly;
+ *           samplesPerPixel >= 2; one device call, so not with window, rects, counters, imageOnly, chunk,
+ *           onFrames or several devices: each of those combinations is an Error)}
  * imageOnly: render and tone-map on the device in one call and return only {rgba, counters, ...}
  * (no accumulator crosses PCIe; pt_render_image).
  * As in the reference only primitive_data[0] is rendered (program-raymarch.wgsl:31,33).
@@ -76,6 +80,8 @@ async function programEntry(screenDimension, primitive_data, camera_data, scene_
     if (win && (o.imageOnly || (o.devices && o.devices.length > 1))) throw Error('window: not with imageOnly or several devices');
     const rects = check_rects(o.rects);
     if (rects && (win || o.imageOnly || (o.devices && o.devices.length > 1))) throw Error('rects: not with window, imageOnly or several devices');
+    if (o.denoise && (win || rects || o.counters || o.imageOnly || o.chunk || o.onFrames || (o.devices && o.devices.length > 1)))
+        throw Error('denoise: not with window, rects, counters, imageOnly, chunk, onFrames or several devices');
     if (o.devices && o.devices.length > 1) return programEntryMulti(pt, meta, W, H, primitive_data, scene_description, o, mode);
     const scene = pt.sceneCreate(primitive_data[0].triangle_data, primitive_data[0].bvh_data,
                                  o.devices && o.devices.length ? o.devices[0] : o.device);
@@ -86,6 +92,12 @@ async function programEntry(screenDimension, primitive_data, camera_data, scene_
         const spp = scene_description.Settings.samplesPerPixel;
         const chunk = Math.max(1, o.chunk || spp);
         const scene_info = pt.sceneInfo(scene);
+        if (o.denoise) {
+            const d = Object.assign({ iters: 0, featureFrames: 4 }, o.denoise === true ? {} : o.denoise);
+            const rgba = new Uint8ClampedArray(W * H * 4);
+            pt.renderDenoised(scene, meta, o.frame0, spp, 1, o.maxDepth, mode, d.featureFrames, d.iters, new Uint8Array(rgba.buffer));
+            return { accum: null, sample_runs: spp, rgba, counters: null, scene_info, denoise: d };
+        }
         if (o.imageOnly) {
             const rgba = new Uint8ClampedArray(W * H * 4);
             const c = await pt.renderImage(scene, meta, o.frame0, spp, 1, o.maxDepth, mode, new Uint8Array(rgba.buffer),

@@ -17,6 +17,7 @@ from ._lib import (  # noqa: F401
     MODE_MEGAKERNEL,
     MODE_WAVEFRONT,
     Counters,
+    DenoiseParams,
     PtError,
     Scene,
     SceneInfo,
@@ -26,6 +27,7 @@ from ._lib import (  # noqa: F401
     abi_version,
     build_id,
     bvh_build,
+    denoise_defaults,
     device_count,
     get_option,
     lib_path,

@@ -12,7 +12,7 @@ _LIB_FILE = os.path.join(_PKG_ROOT, "lib", "libpt_hip.so")
 ABI_VERSION = 3  # include/pt_hip.h PT_ABI_VERSION
 _CSRC = os.path.join(_PKG_ROOT, "csrc")
 # csrc/Makefile BUILD_SRCS: the sources whose SHA-256 the library carries as pt_build_id()
-_BUILD_SRCS = ["pt_kernels.hip", "pt_wavefront.hip", "pt_leafpass.hip", "pt_image.hip", "pt_capi.hip", "pt_math.h", "pt_flavour.h", "pt_layout.h",
+_BUILD_SRCS = ["pt_kernels.hip", "pt_wavefront.hip", "pt_leafpass.hip", "pt_image.hip", "pt_features.hip", "pt_denoise.hip", "pt_capi.hip", "pt_math.h", "pt_flavour.h", "pt_layout.h",
                "pt_device.h", "pt_path.h", "pt_kernels.h", "../../include/pt_hip.h", "pt_bvh.cpp", "pt_leafbvh.h",
                "pt_leafbvh.cpp", "pt_leafskip.cpp", "pt_scene_layout.h", "pt_scene_layout.cpp", "pt_rect_plan.h",
                "pt_rect_plan.cpp", "Makefile"]
@@ -143,6 +143,48 @@ def _adaptive(tile, min_frames, step_frames, max_frames, tol, floor, noisy_fract
     return Adaptive(tw, th, lo, step, hi, _real(tol, "tol"), _real(floor, "floor"), nf)
 
 
+class DenoiseParams(ctypes.Structure):
+    """pt_denoise_params: the a-trous passes (1..5, step 2^i) and the four sigmas (finite, > 0)."""
+    _fields_ = [("iters", ctypes.c_uint32), ("sigma_n", ctypes.c_float), ("sigma_a", ctypes.c_float),
+                ("sigma_z", ctypes.c_float), ("sigma_l", ctypes.c_float)]
+
+
+def denoise_defaults() -> DenoiseParams:
+    """pt_denoise_defaults: 4 passes, sigma_n 0.5, sigma_a 0.3, sigma_z 0.1, sigma_l 4.0."""
+    p = DenoiseParams()
+    load_library().pt_denoise_defaults(ctypes.byref(p))
+    return p
+
+
+def _denoise_params(params):
+    """None (the library's defaults), a DenoiseParams, or a mapping / keyword set over the defaults'
+    fields, checked on the host (the library checks again)."""
+    if params is None:
+        return None
+    if isinstance(params, DenoiseParams):
+        p = DenoiseParams(params.iters, params.sigma_n, params.sigma_a, params.sigma_z, params.sigma_l)
+        it = p.iters
+    else:
+        try:
+            kv = dict(params)
+        except (TypeError, ValueError):
+            raise PtError(-1, f"params must be a DenoiseParams or a mapping of its fields, not {params!r}") from None
+        unknown = set(kv) - {n for n, _ in DenoiseParams._fields_}
+        if unknown:
+            raise PtError(-1, f"params: unknown field(s) {sorted(unknown)}")
+        p = denoise_defaults()
+        it = _uint(kv.get("iters", p.iters), "iters")
+        p.iters = it
+        for n in ("sigma_n", "sigma_a", "sigma_z", "sigma_l"):
+            if n in kv:
+                setattr(p, n, _real(kv[n], n))
+    if not 1 <= it <= 5:
+        raise PtError(-1, f"iters must lie in [1, 5], not {it}")
+    for n in ("sigma_n", "sigma_a", "sigma_z", "sigma_l"):
+        _real(getattr(p, n), n)
+    return p
+
+
 def _extent(meta, win):
     """(w, h) of a call's result: the window's, or the image's of meta[0..1]."""
     return (int(win.w), int(win.h)) if win is not None else (int(meta[0]), int(meta[1]))
@@ -229,6 +271,16 @@ def load_library():
     L.pt_tile_mean_async.argtypes = [p, p, u32, u32, sz, u32, u32, p, p, p]
     L.pt_render_adaptive.argtypes = [p, p, wp, ctypes.POINTER(Adaptive), u32, i, i, p, p, p, p, p, p, ctypes.POINTER(u32)]
     L.pt_selftest_tile_rects.argtypes = [p, u32, u32, p, sz, ctypes.POINTER(sz)]
+    dpp = ctypes.POINTER(DenoiseParams)
+    L.pt_render_features.argtypes = [p, p, wp, u32, u32, u32, p, p, p]
+    L.pt_render_features_async.argtypes = [p, p, wp, u32, u32, u32, p, p, sz, p, p]
+    L.pt_denoise_defaults.argtypes = [dpp]
+    L.pt_denoise_defaults.restype = None
+    L.pt_denoise.argtypes = [p, p, p, u32, u32, u32, u32, p, p, p, u32, dpp, p, p]
+    L.pt_denoise_async.argtypes = [p, p, p, u32, u32, sz, u32, u32, p, p, p, u32, dpp, p, p, p]
+    L.pt_render_denoised_image.argtypes = [p, p, u32, u32, u32, i, i, u32, dpp, p, p]
+    for fn in ("pt_render_features", "pt_render_features_async", "pt_denoise", "pt_denoise_async", "pt_render_denoised_image"):
+        getattr(L, fn).restype = i
     L.pt_tonemap.argtypes = [p, sz, u32, p]
     L.pt_selftest_math.argtypes = [i, i, p, p, p, sz]
     L.pt_profile_enable.argtypes = [p, i]
@@ -598,6 +650,104 @@ class Scene:
         if counters:
             out["counters"] = c.as_dict()
         return out
+
+    def render_features(self, meta, frame0: int, nframes: int, stride: int = 1, geo: np.ndarray | None = None,
+                        alb: np.ndarray | None = None, counters: bool = False, window=None):
+        """pt_render_features: the guide buffers of the first hit, summed over the frames frame0 +
+        i * stride: geo [h, w, 4] += (normal, hit distance), alb [h, w, 4] += (albedo, 1) per hit (so
+        alb[..., 3] counts the hits), in/out like accum.  Returns (geo, alb) (and counters if requested).
+
+        With the adaptive driver (tile frame counts differ, the guides are uniform):
+
+            r = scene.render_adaptive(meta, tile=(64, 64), min_frames=16, max_frames=256)
+            geo, alb = scene.render_features(meta, 0, 4)
+            img, var = scene.denoise(r["accum"], r["m2"], geo, alb, feature_frames=4, tile=(64, 64),
+                                     frames=r["tile_frames"])
+        """
+        meta = _f32(meta)
+        win = _window(window)
+        W, H = _extent(meta, win)
+        bufs = []
+        for a, what in ((geo, "geo"), (alb, "alb")):
+            if a is None:
+                a = np.zeros((H, W, 4), np.float32)
+            if not isinstance(a, np.ndarray) or a.dtype != np.float32 or not a.flags.c_contiguous or a.size != W * H * 4:
+                raise ValueError(f"{what} must be a contiguous float32 array of H*W*4 elements (the window's h*w*4)")
+            bufs.append(a)
+        c = Counters()
+        _check(self._lib.pt_render_features(self._h, _ptr(meta), ctypes.byref(win) if win is not None else None, frame0,
+                                            nframes, stride, _ptr(bufs[0]), _ptr(bufs[1]),
+                                            ctypes.byref(c) if counters else None))
+        return (bufs[0], bufs[1], c.as_dict()) if counters else (bufs[0], bufs[1])
+
+    def render_features_async(self, meta, frame0: int, nframes: int, stride: int, d_geo_ptr: int, d_alb_ptr: int,
+                              stream_ptr: int = 0, d_counters_ptr: int = 0, window=None, row_pitch=None):
+        """pt_render_features_async: d_geo_ptr / d_alb_ptr address the window's FIRST pixel in device f32
+        buffers of four floats per pixel (16-byte aligned), rows row_pitch pixels apart (default: the
+        window's width)."""
+        meta = _f32(meta)
+        win = _window(window)
+        pitch = _extent(meta, win)[0] if row_pitch is None else _uint(row_pitch, "row_pitch")
+        _check(self._lib.pt_render_features_async(self._h, _ptr(meta), ctypes.byref(win) if win is not None else None,
+                                                  frame0, nframes, stride, ctypes.c_void_p(d_geo_ptr or None),
+                                                  ctypes.c_void_p(d_alb_ptr or None), pitch,
+                                                  ctypes.c_void_p(d_counters_ptr or None), ctypes.c_void_p(stream_ptr or None)))
+
+    def denoise(self, accum, m2, geo, alb, feature_frames: int, frames, tile=None, params=None):
+        """pt_denoise: the variance-guided a-trous filter over the host accumulators accum, m2 [h, w, 3]
+        and the guide buffers geo, alb [h, w, 4] (render_features over feature_frames frames).  frames:
+        the sample count of a uniform render, or with tile=(tile_w, tile_h) the [TY, TX] counts per tile
+        (render_adaptive's tile_frames).  params: None (denoise_defaults()), a DenoiseParams or a
+        mapping of its fields.  Returns (image [h, w, 3] f32: the filtered mean, variance [h, w])."""
+        acc, sq, ge, al = _f32(accum), _f32(m2), _f32(geo), _f32(alb)
+        if acc.ndim != 3 or acc.shape[2] != 3 or sq.shape != acc.shape:
+            raise PtError(-1, f"accum and m2 must both be [h, w, 3], not {acc.shape} and {sq.shape}")
+        h, w = acc.shape[:2]
+        if ge.shape != (h, w, 4) or al.shape != (h, w, 4):
+            raise PtError(-1, f"geo and alb must both be [{h}, {w}, 4], not {ge.shape} and {al.shape}")
+        tw, th = (w, h) if tile is None else _tile(tile)
+        tx, ty = -(-w // tw), -(-h // th)
+        fr = np.ascontiguousarray(frames, dtype=np.uint32).reshape(-1)
+        if fr.size != tx * ty:
+            raise PtError(-1, f"frames must hold one count per tile ({ty} x {tx}), not {fr.size} values")
+        prm = _denoise_params(params)
+        out, var = np.zeros((h, w, 3), np.float32), np.zeros((h, w), np.float32)
+        _check(self._lib.pt_denoise(self._h, _ptr(acc), _ptr(sq), w, h, tw, th, _ptr(fr), _ptr(ge), _ptr(al),
+                                    _uint(feature_frames, "feature_frames", 1), ctypes.byref(prm) if prm is not None else None,
+                                    _ptr(out), _ptr(var)))
+        return out, var
+
+    def denoise_async(self, d_accum_ptr: int, d_m2_ptr: int, w: int, h: int, tile, d_frames_ptr: int, d_geo_ptr: int,
+                      d_alb_ptr: int, feature_frames: int, d_out_ptr: int, d_var_out_ptr: int = 0, params=None,
+                      row_pitch=None, stream_ptr: int = 0):
+        """pt_denoise_async between caller-owned device buffers, all with rows row_pitch pixels apart
+        (default w): accumulators [h, w, 3], guides [h, w, 4], u32 frames per tile of tile=(tile_w,
+        tile_h), out [h, w, 3] and (0: none) var_out [h, w]."""
+        tw, th = _tile(tile)
+        w, h = _uint(w, "w", 1), _uint(h, "h", 1)
+        pitch = w if row_pitch is None else _uint(row_pitch, "row_pitch")
+        prm = _denoise_params(params)
+        v = ctypes.c_void_p
+        _check(self._lib.pt_denoise_async(self._h, v(d_accum_ptr or None), v(d_m2_ptr or None), w, h, pitch, tw, th,
+                                          v(d_frames_ptr or None), v(d_geo_ptr or None), v(d_alb_ptr or None),
+                                          _uint(feature_frames, "feature_frames", 1),
+                                          ctypes.byref(prm) if prm is not None else None, v(d_out_ptr or None),
+                                          v(d_var_out_ptr or None), v(stream_ptr or None)))
+
+    def render_denoised(self, meta, frame0: int, nframes: int, stride: int = 1, max_depth: int = -1, mode: int = MODE_AUTO,
+                        feature_frames: int = 4, params=None, counters: bool = False):
+        """pt_render_denoised_image: an nframes (>= 2) moments render, the guides of the first
+        feature_frames frames, the denoiser and the device tone map in one call: RGBA u8 [H, W, 4]."""
+        meta = _f32(meta)
+        W, H = int(meta[0]), int(meta[1])
+        prm = _denoise_params(params)
+        out = np.zeros((H, W, 4), np.uint8)
+        c = Counters()
+        _check(self._lib.pt_render_denoised_image(self._h, _ptr(meta), frame0, _uint(nframes, "nframes", 2), stride, max_depth,
+                                                  mode, _uint(feature_frames, "feature_frames", 1),
+                                                  ctypes.byref(prm) if prm is not None else None, _ptr(out),
+                                                  ctypes.byref(c) if counters else None))
+        return (out, c.as_dict()) if counters else out
 
     def render_image(self, meta, frame0: int, nframes: int, stride: int = 1, max_depth: int = -1,
                      mode: int = MODE_AUTO, counters: bool = False):

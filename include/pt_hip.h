@@ -248,6 +248,79 @@ int pt_render_adaptive(pt_scene* scene, const float meta[48], const pt_window* w
 int pt_selftest_tile_rects(const uint8_t* active, uint32_t tx, uint32_t ty, uint32_t* rects, size_t cap,
                            size_t* n_out);
 
+/* Guide buffers of the first hit, for the denoiser below.  For the frames k = frame0 + i*frame_stride,
+ * i < nframes (salt t_k = u32(f32(k)) as everywhere), and every pixel of the window (NULL = the whole
+ * image), the SAME jittered camera ray the render traces for that pixel and frame is traced to its
+ * closest hit, and the hit is added into two f32 buffers of FOUR floats per pixel, in/out, in frame
+ * order from the values already there, each component one f32 addition:
+ *   geo += (n.x, n.y, n.z, t)   n: the hit's shading normal (pt_scene_set_vertex_normals is honoured),
+ *                               t: the hit distance
+ *   alb += (a.r, a.g, a.b, 1)   a = Ke where (Ke.r + Ke.g) + Ke.b > 0, else Kd + Ks
+ * A miss adds nothing, so alb's fourth component counts the hits.  d_geo / d_alb address the window's
+ * first pixel in device memory, 16-byte aligned; rows are row_pitch pixels apart (>= the window's
+ * width; in pixels, as for the accumulator).  Window and pitch are checked as by
+ * pt_render_window_async; failures of earlier asynchronous renders surface here as there.
+ * Counters (nullable, added to): samples = ext_queries = w*h*nframes, shadow_queries = 0, nodes,
+ * tri_tests and box_tests the traversal's. */
+int pt_render_features_async(pt_scene* scene, const float meta[48], const pt_window* win, uint32_t frame0,
+                             uint32_t nframes, uint32_t frame_stride, float* d_geo, float* d_alb, size_t row_pitch,
+                             pt_counters* d_counters, void* stream);
+/* The same on dense host buffers geo, alb [h][w][4], in/out.  Blocking. */
+int pt_render_features(pt_scene* scene, const float meta[48], const pt_window* win, uint32_t frame0, uint32_t nframes,
+                       uint32_t frame_stride, float* geo, float* alb, pt_counters* counters);
+
+/* Denoiser: the edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) steered by the guide
+ * buffers and by the variance of the mean (the luminance weight of SVGF). */
+typedef struct {
+    uint32_t iters;                           /* 1..5 passes; the step of pass i is s = 2^i */
+    float sigma_n, sigma_a, sigma_z, sigma_l; /* normal, albedo, depth, luminance: finite, > 0 */
+} pt_denoise_params;
+void pt_denoise_defaults(pt_denoise_params* p); /* 4, 0.5, 0.3, 0.1, 4.0 */
+
+/* d_accum, d_m2: the accumulators of a w x h buffer ([h][w][3]); tile_w, tile_h, d_frames: the frame
+ * count n of every tile, as for pt_noise_tiles_async (a uniform n-frame render is tile_w = w,
+ * tile_h = h, frames = {n}); d_geo, d_alb: pt_render_features' buffers ([h][w][4], 16-byte aligned)
+ * summed over feature_frames >= 1 frames.  Outputs: d_out [h][w][3] the filtered mean, d_var_out
+ * (nullable) [h][w] the filtered variance of the mean.  Rows of ALL six buffers are row_pitch pixels
+ * apart (>= w).  p NULL = pt_denoise_defaults.  Asynchronous on `stream`; the scratch (four w*h
+ * float4 planes) belongs to the scene, so calls on one scene must be in stream order.
+ *
+ * Every operation is f32, rounded once, no FMA, in the order written, except where marked double.
+ * Prepare, per pixel (n = the frames of the pixel's tile, nf = (float)feature_frames):
+ *   c = acc / (float)n per channel (n = 0: 0)
+ *   in double, S_c, Q_c the pixel's accum and m2: d_c = Q_c - (S_c * S_c) / n; v_c = d_c > 0 ? d_c : 0;
+ *   V = (v_r + v_g) + v_b; var = (float)(V / (n * (n - 1)))  (n < 2: 0)
+ *   N = geo.xyz / nf (not renormalised); Z = geo.w / nf; A = alb.xyz / nf
+ *   isn = (float)(1.0 / ((double)sigma_n * (double)sigma_n)), isa likewise, isz = (float)(1.0 / (double)sigma_z)
+ * Pass i = 0 .. iters - 1, s = 2^i, for pixel p: the taps q = p + s * (dx, dy), dy = -2..2 outermost,
+ * dx = -2..2 inside; taps outside the w x h buffer are skipped; h = (1/16, 1/4, 3/8, 1/4, 1/16):
+ *   l_x = (c_x.r + c_x.g) + c_x.b;  den_p = sigma_l * sqrtf(var_p) + 1e-6f
+ *   tn = ((dN.x*dN.x + dN.y*dN.y) + dN.z*dN.z) * isn   with dN = N_p - N_q;  ta likewise with A and isa
+ *   zs = Z_p + Z_q;  tz = (|Z_p - Z_q| / (zs > 1e-6f ? zs : 1e-6f)) * isz;  tl = |l_p - l_q| / den_p
+ *   e = (tn + ta) + (tz + tl);  e = e < 126 ? e : 126;  wgt = (h[dy+2] * h[dx+2]) * exp2(-e)
+ *   sw += wgt;  sc += wgt * c_q (per channel);  sv += (wgt * wgt) * var_q
+ *   c'_p = sc / sw;  var'_p = sv / (sw * sw)
+ * with the pinned exp2 (the sigmas absorb the base).  A pass reads the previous pass's c and var of
+ * every pixel; N, Z, A stay.  The centre tap has e = 0, so sw >= 9/64.  Inputs are assumed finite;
+ * other inputs do not fault and give unspecified values.  Option "denoise_lds" chooses how the passes
+ * read their taps, never the bits. */
+int pt_denoise_async(pt_scene* scene, const float* d_accum, const float* d_m2, uint32_t w, uint32_t h, size_t row_pitch,
+                     uint32_t tile_w, uint32_t tile_h, const uint32_t* d_frames, const float* d_geo, const float* d_alb,
+                     uint32_t feature_frames, const pt_denoise_params* p, float* d_out, float* d_var_out, void* stream);
+/* The same on dense host buffers (frames [TY][TX]; var_out nullable).  Blocking. */
+int pt_denoise(pt_scene* scene, const float* accum, const float* m2, uint32_t w, uint32_t h, uint32_t tile_w,
+               uint32_t tile_h, const uint32_t* frames, const float* geo, const float* alb, uint32_t feature_frames,
+               const pt_denoise_params* p, float* out, float* var_out);
+
+/* A denoised image in one call: a moments render of frames frame0 + i*stride (i < nframes, nframes >= 2)
+ * of the whole image from zero, the guide buffers of frames frame0 .. frame0 + feature_frames - 1
+ * (stride 1, feature_frames >= 1), pt_denoise_async (params NULL = the defaults), the device tone map
+ * with sample_runs = 1, and the RGBA image [H][W][4] copied to the host.  counters: nullable, the
+ * render's plus the guide pass's.  Blocking. */
+int pt_render_denoised_image(pt_scene* scene, const float meta[48], uint32_t frame0, uint32_t nframes,
+                             uint32_t frame_stride, int max_depth, int mode, uint32_t feature_frames,
+                             const pt_denoise_params* params, uint8_t* rgba_out, pt_counters* counters);
+
 /* Completion check of the asynchronous calls: waits for every render of the scene to finish
  * (blocking) and reports a device-side failure of any of them — a wavefront traversal wave that
  * gave up after its watchdog limit leaves a flag instead of hanging, and the accumulators of
@@ -292,6 +365,9 @@ int pt_set_hw_queues(int n);
  *   "leaf_blocks" "leaf_pairs"          integers (the leaf pass's grid; its pair walk: 0 | 1 | 2)
  *   "leaf_refine"   0 | 1               (the pair walk's second check with the entries' normals)
  *   "reduce"        rccl | ordered      (pt_render_multi's reduction)
+ *   "denoise_lds"   0 | 1 | 2 | 3 | 4   (pt_denoise_async: the first that many passes — steps 1, 2, 4, 8 — stage
+ *                                        their block's (16 + 4 s)^2 region in LDS, the others load their taps
+ *                                        from global memory; default 2, the measured best)
  * DESIGN.md §6 describes each.  pt_get_option writes the current value ("" = default) into buf. */
 int pt_set_option(const char* name, const char* value);
 int pt_get_option(const char* name, char* buf, size_t cap);
