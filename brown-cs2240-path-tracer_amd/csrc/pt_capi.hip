@@ -64,6 +64,7 @@ constexpr OptSpec kOptSpecs[] = {
     {"mb_uid_order", OPT_ENUM, "forward|reverse"},
     {"reduce", OPT_ENUM, "rccl|ordered"},
     {"denoise_lds", OPT_ENUM, "0|1|2|3|4"},
+    {"query_refill", OPT_BOOL, nullptr}, {"query_blocks", OPT_INT, nullptr},
 };
 constexpr int kNumOpts = (int)(sizeof(kOptSpecs) / sizeof(kOptSpecs[0]));
 
@@ -198,6 +199,12 @@ struct pt_scene {
     // (geo, then alb) and the filtered variance
     Scratch<float4> d_dn;
     Scratch<float> d_feat, d_var;
+    // ray queries (pt_query_*): the blocking calls' rays and results (counted in info.device_bytes while
+    // held), the kernels' control words (kQueryCtlWords: a wave that gave up sets the first) and their
+    // pinned mirror, copied after every query launch on its stream like h_ctl below
+    Scratch<char> d_query;
+    uint32_t* d_qctl = nullptr;
+    uint32_t* h_qctl = nullptr;
     WfStreams ws;  // dual-stream wavefront: aux stream + fork/join events (created with d_wf)
     // pinned mirror of the wavefront control words, copied after every wavefront render on its
     // stream: a watchdog flag set by an asynchronous render surfaces once that copy has landed
@@ -460,7 +467,9 @@ void pt_scene_destroy(pt_scene* s) {
     if (s->d_rad) hipFree(s->d_rad);
     if (s->d_pres) hipFree(s->d_pres);
     s->d_accum.free(); s->d_m2.free(); s->d_mean.free(); s->d_peer.free(); s->d_rgba.free(); s->d_tiles.free(); s->d_rects.free();
-    s->d_dn.free(); s->d_feat.free(); s->d_var.free();
+    s->d_dn.free(); s->d_feat.free(); s->d_var.free(); s->d_query.free();
+    if (s->d_qctl) hipFree(s->d_qctl);
+    if (s->h_qctl) hipHostFree(s->h_qctl);
     if (s->h_ctl) hipHostFree(s->h_ctl);
     if (s->d_mem) hipFree(s->d_mem);
     s->prof.destroy();
@@ -674,7 +683,25 @@ int ensure_wavefront(pt_scene* s, uint64_t paths) {
 // the scene comes next, megakernel or wavefront — and cleared.  The failure path waits for the
 // device first, so no mirror copy still in flight can bring the flag back after the clear and
 // report the same failure twice.
+// The same for a query wave (pt_query.hip k_query): the flag is the first of the scene's query control
+// words, mirrored in h_qctl after every query launch.
+int take_query_watchdog(pt_scene* s) {
+    if (!s->h_qctl || !__atomic_load_n(&s->h_qctl[0], __ATOMIC_ACQUIRE)) return PT_OK;
+    HIP_TRY(hipDeviceSynchronize());  // every pending mirror copy of the scene has landed
+    uint32_t v[kQueryCtlWords];
+    std::memcpy(v, s->h_qctl, sizeof v);
+    HIP_TRY(hipMemset(s->d_qctl, 0, sizeof v));
+    std::memset(s->h_qctl, 0, sizeof v);
+    char msg[256];
+    std::snprintf(msg, sizeof(msg),
+                  "ray query gave up after its watchdog limit (results invalid); first wave: n=%u nwaves=%u w=%u "
+                  "fetched=%u base=%u wv=%u cur=%u in_flight=%u",
+                  v[2], v[3], v[4], v[5], v[6], v[7], v[8], v[9]);
+    return fail(PT_ERR_HIP, msg);
+}
+
 int take_watchdog(pt_scene* s) {
+    if (const int rc = take_query_watchdog(s); rc != PT_OK) return rc;
     if (!s->h_ctl) return PT_OK;
     int h = 0;
     while (h < kMaxParts && !__atomic_load_n(&s->h_ctl[h * WF_CTL_WORDS + WF_WATCHDOG], __ATOMIC_ACQUIRE)) ++h;
@@ -1311,6 +1338,167 @@ int pt_render_features(pt_scene* s, const float meta[48], const pt_window* win, 
     if (d_cnt) HIP_TRY(hipMemcpyAsync(counters, d_cnt, sizeof(Counters), hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
     return take_watchdog(s);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Ray queries (pt_query.hip)
+// ---------------------------------------------------------------------------------------------
+static_assert(sizeof(pt_ray) == 32 && sizeof(pt_hit) == 32 && offsetof(pt_ray, d) == 16 && offsetof(pt_hit, n) == 16,
+              "pt_ray and pt_hit are two 16-byte halves");
+
+// the checks that need no device, in the header's order: true when the call ends here with rc (an
+// error, or PT_OK for an empty batch), false to go on
+// align_rays, align_out: the _async forms' device pointers (the blocking forms copy host buffers of any
+// alignment the types allow into the scene's aligned scratch)
+static bool query_args(const void* s, const void* rays, size_t n, const void* out, bool align_rays, bool align_out, int& rc) {
+    if (n > kQueryMaxRays) { rc = fail(PT_ERR_INVALID, "query: n exceeds 2^30 rays"); return true; }
+    if (n > 0 && (!rays || !out)) { rc = fail(PT_ERR_INVALID, "query: null ray or result pointer"); return true; }
+    if (n > 0 && ((align_rays && ((uintptr_t)rays & 15u)) || (align_out && ((uintptr_t)out & 15u)))) {
+        rc = fail(PT_ERR_INVALID, "query: rays and hits must be 16-byte aligned");
+        return true;
+    }
+    if (!s) { rc = fail(PT_ERR_INVALID, "null scene"); return true; }
+    if (n == 0) { rc = PT_OK; return true; }
+    return false;
+}
+
+static int ensure_query_ctl(pt_scene* s) {
+    if (s->d_qctl && s->h_qctl) return PT_OK;
+    const size_t bytes = kQueryCtlWords * sizeof(uint32_t);
+    if (!s->d_qctl) {
+        if (hipMalloc(reinterpret_cast<void**>(&s->d_qctl), bytes) != hipSuccess) {
+            s->d_qctl = nullptr;
+            (void)hipGetLastError();
+            return fail(PT_ERR_NOMEM, "hipMalloc query control words");
+        }
+        HIP_TRY(hipMemset(s->d_qctl, 0, bytes));
+    }
+    if (!s->h_qctl) {
+        if (hipHostMalloc(reinterpret_cast<void**>(&s->h_qctl), bytes) != hipSuccess) {
+            s->h_qctl = nullptr;
+            return fail(PT_ERR_NOMEM, "hipHostMalloc query control mirror");
+        }
+        std::memset(s->h_qctl, 0, bytes);
+    }
+    return PT_OK;
+}
+
+// the blocking calls' scratch, counted in device_bytes while held (as the denoiser's planes)
+static int ensure_query_scratch(pt_scene* s, size_t bytes) {
+    const size_t before = s->d_query.cap;
+    const int rc = s->d_query.ensure(bytes, "query rays and results");
+    if (rc != PT_OK) {
+        s->info.device_bytes -= before;  // (ensure frees before it allocates)
+        return rc;
+    }
+    s->info.device_bytes += s->d_query.cap - before;
+    return PT_OK;
+}
+
+// d_hits or d_occ, the other NULL; the arguments are checked (query_args)
+static int query_impl(pt_scene* s, const pt_ray* d_rays, size_t n, pt_hit* d_hits, uint8_t* d_occ, Counters* d_cnt,
+                      hipStream_t stream) {
+    HIP_TRY(hipSetDevice(s->device));
+    int rc = ensure_query_ctl(s);
+    if (rc != PT_OK) return rc;
+    ProfScope prof_scope(s);
+    const Opts o = opts_snapshot();
+    // the scene as the default megakernel instance sees it (the big-leaf threshold, the leaf
+    // remainders), as the guide buffers; of the options only the query's own and trace_watchdog apply
+    SceneView view;
+    if ((rc = shape_view(s, Opts{}, FrameParams{}, PT_MODE_MEGAKERNEL, n, view)) != PT_OK) return rc;
+    if ((rc = take_watchdog(s)) != PT_OK) return rc;  // an earlier asynchronous call failed
+    HIP_TRY(launch_query(view, d_rays, (uint32_t)n, d_hits, d_occ, d_cnt != nullptr, d_cnt, s->d_qctl,
+                         (uint32_t)o.num("trace_watchdog", 0), o.flag("query_refill", 1), (int)o.num("query_blocks", 0), stream));
+    HIP_TRY(hipMemcpyAsync(s->h_qctl, s->d_qctl, kQueryCtlWords * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    return PT_OK;
+}
+
+static int query_blocking(pt_scene* s, const pt_ray* rays, size_t n, pt_hit* hits, uint8_t* occ, pt_counters* counters) {
+    HIP_TRY(hipSetDevice(s->device));
+    const size_t ray_bytes = n * sizeof(pt_ray), out_bytes = hits ? n * sizeof(pt_hit) : n;
+    int rc;
+    if ((rc = ensure_query_scratch(s, ray_bytes + align_up(out_bytes, 16))) != PT_OK || (rc = blocking_stream(s)) != PT_OK)
+        return rc;
+    pt_ray* const d_rays = reinterpret_cast<pt_ray*>(s->d_query.p);
+    char* const d_out = s->d_query.p + ray_bytes;
+    Counters* d_cnt = counters ? s->d_counters : nullptr;
+    HIP_TRY(hipMemcpyAsync(d_rays, rays, ray_bytes, hipMemcpyHostToDevice, s->stream));
+    if (d_cnt) HIP_TRY(hipMemsetAsync(d_cnt, 0, sizeof(Counters), s->stream));
+    if ((rc = query_impl(s, d_rays, n, hits ? reinterpret_cast<pt_hit*>(d_out) : nullptr,
+                         hits ? nullptr : reinterpret_cast<uint8_t*>(d_out), d_cnt, s->stream)) != PT_OK)
+        return rc;
+    pt_counters got{};
+    HIP_TRY(hipMemcpyAsync(hits ? static_cast<void*>(hits) : static_cast<void*>(occ), d_out, out_bytes, hipMemcpyDeviceToHost,
+                           s->stream));
+    if (d_cnt) HIP_TRY(hipMemcpyAsync(&got, d_cnt, sizeof(Counters), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    if ((rc = take_watchdog(s)) != PT_OK) return rc;
+    if (counters) {
+        counters->samples += got.samples; counters->ext_queries += got.ext_queries;
+        counters->shadow_queries += got.shadow_queries; counters->nodes += got.nodes;
+        counters->tri_tests += got.tri_tests; counters->box_tests += got.box_tests;
+    }
+    return PT_OK;
+}
+
+int pt_query_hits_async(pt_scene* s, const pt_ray* d_rays, size_t n, pt_hit* d_hits, pt_counters* d_counters, void* stream) {
+    int rc;
+    if (query_args(s, d_rays, n, d_hits, true, true, rc)) return rc;
+    return query_impl(s, d_rays, n, d_hits, nullptr, reinterpret_cast<Counters*>(d_counters), static_cast<hipStream_t>(stream));
+}
+
+int pt_query_occluded_async(pt_scene* s, const pt_ray* d_rays, size_t n, uint8_t* d_occluded, pt_counters* d_counters,
+                            void* stream) {
+    int rc;
+    if (query_args(s, d_rays, n, d_occluded, true, false, rc)) return rc;
+    return query_impl(s, d_rays, n, nullptr, d_occluded, reinterpret_cast<Counters*>(d_counters),
+                      static_cast<hipStream_t>(stream));
+}
+
+int pt_query_hits(pt_scene* s, const pt_ray* rays, size_t n, pt_hit* hits, pt_counters* counters) {
+    int rc;
+    if (query_args(s, rays, n, hits, false, false, rc)) return rc;
+    return query_blocking(s, rays, n, hits, nullptr, counters);
+}
+
+int pt_query_occluded(pt_scene* s, const pt_ray* rays, size_t n, uint8_t* occluded, pt_counters* counters) {
+    int rc;
+    if (query_args(s, rays, n, occluded, false, false, rc)) return rc;
+    return query_blocking(s, rays, n, nullptr, occluded, counters);
+}
+
+static int camera_rays_args(const pt_scene* s, const float* meta, const pt_window* win, uint32_t frame, const void* rays,
+                            bool aligned, FrameParams& fp) {
+    if (frame >= (1u << 24)) return fail(PT_ERR_INVALID, "frame index >= 2^24 (t_k = u32(f32(k)) would round)");
+    if (!meta || !rays) return fail(PT_ERR_INVALID, "null argument");
+    if (aligned && ((uintptr_t)rays & 15u)) return fail(PT_ERR_INVALID, "rays must be 16-byte aligned");
+    if (!s) return fail(PT_ERR_INVALID, "null scene");
+    return make_params(meta, 0, fp, win);
+}
+
+int pt_camera_rays_async(pt_scene* s, const float meta[48], const pt_window* win, uint32_t frame, pt_ray* d_rays,
+                         void* stream) {
+    FrameParams fp{};
+    const int rc = camera_rays_args(s, meta, win, frame, d_rays, true, fp);
+    if (rc != PT_OK) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    ProfScope prof_scope(s);
+    HIP_TRY(launch_camera_rays(fp, (uint32_t)(float)frame, d_rays, static_cast<hipStream_t>(stream)));
+    return PT_OK;
+}
+
+int pt_camera_rays(pt_scene* s, const float meta[48], const pt_window* win, uint32_t frame, pt_ray* rays) {
+    FrameParams fp{};
+    int rc = camera_rays_args(s, meta, win, frame, rays, false, fp);
+    if (rc != PT_OK) return rc;
+    const size_t bytes = (size_t)fp.win_w * fp.win_h * sizeof(pt_ray);
+    HIP_TRY(hipSetDevice(s->device));
+    if ((rc = ensure_query_scratch(s, bytes)) != PT_OK || (rc = blocking_stream(s)) != PT_OK) return rc;
+    if ((rc = pt_camera_rays_async(s, meta, win, frame, reinterpret_cast<pt_ray*>(s->d_query.p), s->stream)) != PT_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(rays, s->d_query.p, bytes, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return PT_OK;
 }
 
 void pt_denoise_defaults(pt_denoise_params* p) {

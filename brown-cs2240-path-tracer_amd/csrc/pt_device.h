@@ -328,6 +328,18 @@ __device__ __forceinline__ void trav_init(TravLean& s, bool active) {
 }
 __device__ __forceinline__ bool trav_finished(const TravLean& s) { return (s.fl & TF_DONE) != 0; }
 __device__ __forceinline__ bool trav_finished(const TravState& s) { return s.done; }
+// Abandon a traversal between two trav_advance calls (the any-hit queries' early exit, pt_query.hip).
+// Legal in every state a lane can be in when trav_advance returns, because all a later turn reads of a
+// lane is its flag word and, for lanes the flags select, the fields below it:
+//  - mid-leaf (TF_LEAF, k < nt): the rest of the pair is simply not tested; no other lane reads k, la, lb;
+//  - parked for a cooperative turn (TF_PARK): big_turn serves the FIRST lane of the ballot of TF_PARK
+//    flags and reads only that lane's ray and big_seg fields; a lane whose TF_PARK is cleared is not in
+//    the ballot, and the fields big_seg computes on the other lanes are never used;
+//  - between the node steps of one turn: trav_step_lean runs all steps of a turn and its lean_decide
+//    before it returns, so a returning lane's push or pop is complete — the stack holds no half-made entry;
+//  - the stack itself: per lane, and trav_init sets sp = 0 (and last = -1) for the lane's next ray.
+// A done lane takes no part in the wave's votes (want_leaf, want_node, parked) until trav_init.
+__device__ __forceinline__ void trav_stop(TravLean& s) { s.fl = (s.fl & ~(TF_LEAF | TF_PARK)) | TF_DONE; }
 
 // K = triangle tests per leaf turn: a lane with at least two triangles of its leaf pair left
 // runs two in sequence (same order, each against the closest t so far), which halves the

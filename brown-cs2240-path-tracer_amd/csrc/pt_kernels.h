@@ -2,10 +2,12 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <vector>
 
 #include "pt_device.h"
 #include "pt_flavour.h"
+#include "pt_query_plan.h"
 #include "pt_rect_plan.h"
 
 // ids for k_selftest_math (also used by pt_selftest_math in the C-ABI)
@@ -21,13 +23,14 @@ namespace pt {
 enum KernelId : int {
     KID_MEGA = 0, KID_REGEN, KID_WF_GENERATE, KID_WF_TRACE, KID_WF_SHADE_EXT, KID_WF_SHADE_SHADOW, KID_WF_ACCUM,
     KID_TONEMAP, KID_WF_STEP, KID_WF_LEAF, KID_NOISE_TILES, KID_TILE_MEAN, KID_FEATURES, KID_DENOISE_PREPARE, KID_ATROUS,
-    KID_COUNT
+    KID_QUERY_HITS, KID_QUERY_OCCLUDED, KID_CAMERA_RAYS, KID_COUNT
 };
 inline const char* kernel_name(int k) {
     static const char* const n[KID_COUNT] = {"k_mega",         "k_regen",           "k_wf_generate", "k_wf_trace",
                                              "k_wf_shade_ext", "k_wf_shade_shadow", "k_wf_accum",    "k_tonemap",
                                              "k_wf_step",      "k_wf_leafpass",     "k_noise_tiles", "k_tile_mean",
-                                             "k_features",     "k_denoise_prepare", "k_atrous"};
+                                             "k_features",     "k_denoise_prepare", "k_atrous",      "k_query_hits",
+                                             "k_query_occluded", "k_camera_rays"};
     return (k >= 0 && k < KID_COUNT) ? n[k] : "?";
 }
 struct KernelProfiler {
@@ -174,6 +177,17 @@ bool atrous_can_stage(uint32_t s);
 hipError_t launch_atrous(const float4* cv, const float4* nz, const float4* ab, uint32_t w, uint32_t h, uint32_t s, float isn,
                          float isa, float isz, float sigma_l, bool staged, float4* cv_out, float* out, float* var_out,
                          uint32_t row_pitch, hipStream_t stream);
+// ray queries (pt_query.hip; pt_hip.h pt_query_hits_async, pt_query_occluded_async): n <= 2^30 rays of 32 B
+// (pt_ray) traced to hits (n pt_hit records) or, hits == nullptr, to occluded (n bytes); exactly one of the
+// two is given.  ctl: the scene's ten query control words (a wave that gave up sets ctl[0] and launches
+// skip while it is set); watchdog: iterations before a wave gives up (0: kTraceWatchdog); refill: idle
+// lanes take the window's next rays (0: only when the whole wave is idle); blocks: the grid (0: by occupancy)
+// The batch goes out in launches of at most kQueryLaunchRays rays, in order on the stream.
+constexpr int kQueryCtlWords = 10;
+hipError_t launch_query(const SceneView& sc, const void* rays, uint32_t n, void* hits, uint8_t* occluded, bool count,
+                        Counters* cnt, uint32_t* ctl, uint32_t watchdog, int refill, int blocks, hipStream_t stream);
+// the window's camera rays of salt t, row-major, as pt_ray records (tmax = +inf, reserved = 0)
+hipError_t launch_camera_rays(const FrameParams& fp, uint32_t t, void* rays, hipStream_t stream);
 // n floats from device memory to pinned host memory (h_dst_dev: its device address; pt_image.hip)
 hipError_t launch_readback(const float* d_src, float* h_dst_dev, size_t n, hipStream_t stream);
 // dst[i] += src[i] for i < n (f32; both on the stream's device; pt_image.hip)

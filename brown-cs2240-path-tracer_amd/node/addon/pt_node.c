@@ -640,6 +640,87 @@ static napi_value js_render_denoised(napi_env env, napi_callback_info info) {
     return NULL;
 }
 
+/* a new typed array of n elements (Float32Array or Uint8Array) and its storage */
+static napi_value new_typedarray(napi_env env, napi_typedarray_type type, size_t n, void** data) {
+    napi_value ab, ta;
+    const size_t bytes = n * (type == napi_float32_array ? 4 : 1);
+    if (napi_create_arraybuffer(env, bytes, data, &ab) != napi_ok || napi_create_typedarray(env, type, n, ab, 0, &ta) != napi_ok) {
+        if (!pending_exception(env)) napi_throw_error(env, NULL, "could not allocate the result array");
+        return NULL;
+    }
+    return ta;
+}
+
+/* queryHits(scene, Float32Array rays[8n]) -> Float32Array[8n]: pt_query_hits — per ray (o.xyz, tmax, d.xyz,
+ * reserved) the closest hit's (p.xyz, t, n.xyz, material as int32 bits; a miss: t = -1, material = -1).
+ * queryOccluded(scene, rays) -> Uint8Array[n]: pt_query_occluded.  Blocking. */
+static napi_value query_call(napi_env env, napi_callback_info info, int occluded) {
+    size_t argc = 2;
+    napi_value argv[2];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    float* rays;
+    size_t rl;
+    pt_scene* s = argc >= 2 ? get_scene(env, argv[0]) : NULL;
+    if (!s || !get_f32(env, argv[1], &rays, &rl) || rl % 8 != 0) {
+        if (!pending_exception(env))
+            napi_throw_type_error(env, NULL, occluded ? "queryOccluded(scene, Float32Array rays[8n])"
+                                                      : "queryHits(scene, Float32Array rays[8n])");
+        return NULL;
+    }
+    const size_t n = rl / 8;
+    void* out = NULL;
+    napi_value res = new_typedarray(env, occluded ? napi_uint8_array : napi_float32_array, occluded ? n : 8 * n, &out);
+    if (!res) return NULL;
+    const int rc = occluded ? pt_query_occluded(s, (const pt_ray*)rays, n, (uint8_t*)out, NULL)
+                            : pt_query_hits(s, (const pt_ray*)rays, n, (pt_hit*)out, NULL);
+    if (rc) return throw_pt(env, rc);
+    return res;
+}
+static napi_value js_query_hits(napi_env env, napi_callback_info info) { return query_call(env, info, 0); }
+static napi_value js_query_occluded(napi_env env, napi_callback_info info) { return query_call(env, info, 1); }
+
+/* cameraRays(scene, meta, frame[, [x0, y0, w, h]]) -> Float32Array[8 w h]: pt_camera_rays, the rays the render
+ * traces for the window's pixels in that frame, row-major, tmax = +inf */
+static napi_value js_camera_rays(napi_env env, napi_callback_info info) {
+    size_t argc = 4;
+    napi_value argv[4];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    float* meta;
+    size_t ml;
+    uint32_t frame;
+    pt_window win;
+    int has_win = 0;
+    pt_scene* s = argc >= 3 ? get_scene(env, argv[0]) : NULL;
+    int ok = s && get_f32(env, argv[1], &meta, &ml) && ml >= 48 && get_u32(env, argv[2], &frame);
+    if (ok && argc >= 4) {
+        napi_valuetype vt;
+        if (napi_typeof(env, argv[3], &vt) != napi_ok) ok = 0;
+        else if (vt != napi_undefined && vt != napi_null) ok = has_win = parse_window(env, argv[3], &win);
+    }
+    if (!ok) {
+        if (!pending_exception(env)) napi_throw_type_error(env, NULL, "cameraRays(scene, Float32Array meta[48], frame[, [x0, y0, w, h]])");
+        return NULL;
+    }
+    /* the result's size is the window's, so the window is checked against the image (the library's own
+     * rule, pt_window) before anything is allocated for it */
+    const double W = (double)meta[0], H = (double)meta[1];
+    if (!(W >= 1.0 && H >= 1.0 && W <= 32768.0 && H <= 32768.0)) {
+        napi_throw_range_error(env, NULL, "cameraRays: meta[0..1] must be resolutions in [1, 32768]");
+        return NULL;
+    }
+    if (has_win && (win.w < 1 || win.h < 1 || (double)win.x0 + (double)win.w > W || (double)win.y0 + (double)win.h > H)) {
+        napi_throw_range_error(env, NULL, "cameraRays: the window must have w, h >= 1 and lie within the image (meta[0..1])");
+        return NULL;
+    }
+    const double npix = has_win ? (double)win.w * (double)win.h : W * H;
+    void* out = NULL;
+    napi_value res = new_typedarray(env, napi_float32_array, 8 * (size_t)npix, &out);
+    if (!res) return NULL;
+    const int rc = pt_camera_rays(s, meta, has_win ? &win : NULL, frame, (pt_ray*)out);
+    if (rc) return throw_pt(env, rc);
+    return res;
+}
+
 /* tonemap(accum Float32Array, sampleRuns, out Uint8Array[npix*4]) */
 static napi_value js_tonemap(napi_env env, napi_callback_info info) {
     size_t argc = 3;
@@ -791,6 +872,9 @@ static napi_value init(napi_env env, napi_value exports) {
         {"renderMulti", NULL, js_render_multi, NULL, NULL, NULL, napi_enumerable, NULL},
         {"renderImage", NULL, js_render_image, NULL, NULL, NULL, napi_enumerable, NULL},
         {"renderDenoised", NULL, js_render_denoised, NULL, NULL, NULL, napi_default, NULL},
+        {"queryHits", NULL, js_query_hits, NULL, NULL, NULL, napi_default, NULL},
+        {"queryOccluded", NULL, js_query_occluded, NULL, NULL, NULL, napi_default, NULL},
+        {"cameraRays", NULL, js_camera_rays, NULL, NULL, NULL, napi_default, NULL},
         {"frame", NULL, js_frame, NULL, NULL, NULL, napi_enumerable, NULL},
         {"tonemap", NULL, js_tonemap, NULL, NULL, NULL, napi_enumerable, NULL},
         {"profileEnable", NULL, js_profile_enable, NULL, NULL, NULL, napi_enumerable, NULL},

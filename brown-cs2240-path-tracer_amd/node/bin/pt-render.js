@@ -11,6 +11,8 @@
 //  image's size, the rectangles hold the full PNG's pixels and everything else is black)
 // [--denoise [iters]] (the variance-guided a-trous denoiser, pt_render_denoised_image: 1..5 passes, default the
 //  library's; the whole image only, without --counters, --spp at least 2) [--feature-frames N] (frames of its guide buffers, default 4)
+// [--pick x,y] (print what the frame-0 camera ray of pixel (x, y) hits — point, distance, normal, material —
+//  as one JSON line and render nothing: pt_camera_rays + pt_query_hits)
 const fs = require('fs');
 const path = require('path');
 const host = require('..');
@@ -50,6 +52,7 @@ async function main(argv) {
         }
         denoise = { iters: +it, featureFrames: +ff };
     }
+    if (args.pick !== undefined) return pick(args);
     const t0 = Date.now();
     const s = host.load_scene_from_ini(args._[0], { web_root: args.web_root, quiet: true });
     if (args.spp) s.scene_description.Settings.samplesPerPixel = parseInt(args.spp);
@@ -67,4 +70,33 @@ async function main(argv) {
     console.log(JSON.stringify({ output: out, width: W, height: H, window, rects, spp: r.sample_runs, scene_ms: t1 - t0,
         denoise, render_ms: t2 - t1, msamples_per_s: samples / ((t2 - t1) / 1000) / 1e6, counters: r.counters }));
 }
+// --pick x,y: what the camera ray of pixel (x, y), frame 0, hits (pt_camera_rays + pt_query_hits), as one
+// JSON line; nothing is rendered or written.  `bits`: the eight 32-bit words of the hit record.
+function pick(args) {
+    const parts = String(args.pick).split(',');
+    if (parts.length !== 2 || !parts.every((v) => /^\d+$/.test(v))) {
+        console.error(`usage: pt-render.js <scene.ini> --pick x,y (two non-negative integers): --pick ${args.pick}`);
+        process.exit(2);
+    }
+    const [x, y] = parts.map(Number);
+    const s = host.load_scene_from_ini(args._[0], { web_root: args.web_root, quiet: true });
+    const [W, H] = s.screenDimension;
+    if (x >= W || y >= H) { console.error(`--pick ${x},${y}: outside the ${W}x${H} image`); process.exit(2); }
+    const pt = host.native();
+    const meta = host.make_meta(s.screenDimension, s.camera_data, s.scene_description, 0);
+    const scene = pt.sceneCreate(s.primitive_data[0].triangle_data, s.primitive_data[0].bvh_data, parseInt(args.device || '0'));
+    try {
+        if (args.vertex_normals === '1') pt.sceneSetVertexNormals(scene, true);
+        const ray = host.cameraRays(scene, meta, 0, [x, y, 1, 1]);
+        const h = host.queryHits(scene, ray);
+        const material = new Int32Array(h.buffer, h.byteOffset, 8)[7];
+        console.log(JSON.stringify({ pick: [x, y], width: W, height: H, hit: material >= 0,
+            ray: { o: Array.from(ray.subarray(0, 3)), d: Array.from(ray.subarray(4, 7)) },
+            p: Array.from(h.subarray(0, 3)), t: h[3], n: Array.from(h.subarray(4, 7)), material,
+            bits: Array.from(new Uint32Array(h.buffer, h.byteOffset, 8)) }));
+    } finally {
+        pt.sceneDestroy(scene);
+    }
+}
+
 main(process.argv.slice(2)).catch((e) => { console.error(e.stack || String(e)); process.exit(1); });

@@ -18,7 +18,11 @@ from ._lib import (  # noqa: F401
     MODE_WAVEFRONT,
     Counters,
     DenoiseParams,
+    HIT_DTYPE,
+    Hit,
     PtError,
+    RAY_DTYPE,
+    Ray,
     Scene,
     SceneInfo,
     TILE_NOISE_DTYPE,

@@ -12,10 +12,10 @@ _LIB_FILE = os.path.join(_PKG_ROOT, "lib", "libpt_hip.so")
 ABI_VERSION = 3  # include/pt_hip.h PT_ABI_VERSION
 _CSRC = os.path.join(_PKG_ROOT, "csrc")
 # csrc/Makefile BUILD_SRCS: the sources whose SHA-256 the library carries as pt_build_id()
-_BUILD_SRCS = ["pt_kernels.hip", "pt_wavefront.hip", "pt_leafpass.hip", "pt_image.hip", "pt_features.hip", "pt_denoise.hip", "pt_capi.hip", "pt_math.h", "pt_flavour.h", "pt_layout.h",
+_BUILD_SRCS = ["pt_kernels.hip", "pt_wavefront.hip", "pt_leafpass.hip", "pt_image.hip", "pt_features.hip", "pt_denoise.hip", "pt_query.hip", "pt_capi.hip", "pt_math.h", "pt_flavour.h", "pt_layout.h",
                "pt_device.h", "pt_path.h", "pt_kernels.h", "../../include/pt_hip.h", "pt_bvh.cpp", "pt_leafbvh.h",
                "pt_leafbvh.cpp", "pt_leafskip.cpp", "pt_scene_layout.h", "pt_scene_layout.cpp", "pt_rect_plan.h",
-               "pt_rect_plan.cpp", "Makefile"]
+               "pt_rect_plan.cpp", "pt_query_plan.h", "Makefile"]
 MODE_AUTO, MODE_MEGAKERNEL, MODE_WAVEFRONT = 0, 1, 2
 MATH_FNS = ["sin", "cos", "tan", "acos", "log2", "exp2", "pow", "sqrt", "div", "hash1u", "hash1", "hash2x",
             "hash2y", "min", "max"]
@@ -185,6 +185,35 @@ def _denoise_params(params):
     return p
 
 
+class Ray(ctypes.Structure):
+    """pt_ray (32 B): origin, tmax, direction (not normalised; t is in its units), reserved (ignored)."""
+    _fields_ = [("o", ctypes.c_float * 3), ("tmax", ctypes.c_float), ("d", ctypes.c_float * 3),
+                ("reserved", ctypes.c_uint32)]
+
+
+class Hit(ctypes.Structure):
+    """pt_hit (32 B): point, t, shading normal, material; a miss is t = -1, material = -1, p = n = 0."""
+    _fields_ = [("p", ctypes.c_float * 3), ("t", ctypes.c_float), ("n", ctypes.c_float * 3),
+                ("material", ctypes.c_int32)]
+
+
+RAY_DTYPE = np.dtype([("o", "<f4", 3), ("tmax", "<f4"), ("d", "<f4", 3), ("reserved", "<u4")])
+HIT_DTYPE = np.dtype([("p", "<f4", 3), ("t", "<f4"), ("n", "<f4", 3), ("material", "<i4")])
+
+
+def _rays(rays) -> np.ndarray:
+    """A batch of rays as one contiguous [n, 8] f32 array (ox, oy, oz, tmax, dx, dy, dz, reserved bits):
+    an array of RAY_DTYPE records, or anything of n * 8 f32 values."""
+    a = np.asarray(rays)
+    if a.dtype == RAY_DTYPE:
+        a = np.ascontiguousarray(a).view(np.float32)
+    else:
+        a = np.ascontiguousarray(a, dtype=np.float32)
+    if a.size % 8:
+        raise PtError(-1, f"rays must hold 8 floats per ray (o, tmax, d, reserved), not {a.size} values")
+    return a.reshape(-1, 8)
+
+
 def _extent(meta, win):
     """(w, h) of a call's result: the window's, or the image's of meta[0..1]."""
     return (int(win.w), int(win.h)) if win is not None else (int(meta[0]), int(meta[1]))
@@ -274,6 +303,12 @@ def load_library():
     dpp = ctypes.POINTER(DenoiseParams)
     L.pt_render_features.argtypes = [p, p, wp, u32, u32, u32, p, p, p]
     L.pt_render_features_async.argtypes = [p, p, wp, u32, u32, u32, p, p, sz, p, p]
+    L.pt_query_hits.argtypes = [p, p, sz, p, p]
+    L.pt_query_hits_async.argtypes = [p, p, sz, p, p, p]
+    L.pt_query_occluded.argtypes = [p, p, sz, p, p]
+    L.pt_query_occluded_async.argtypes = [p, p, sz, p, p, p]
+    L.pt_camera_rays.argtypes = [p, p, wp, u32, p]
+    L.pt_camera_rays_async.argtypes = [p, p, wp, u32, p, p]
     L.pt_denoise_defaults.argtypes = [dpp]
     L.pt_denoise_defaults.restype = None
     L.pt_denoise.argtypes = [p, p, p, u32, u32, u32, u32, p, p, p, u32, dpp, p, p]
@@ -692,6 +727,59 @@ class Scene:
                                                   frame0, nframes, stride, ctypes.c_void_p(d_geo_ptr or None),
                                                   ctypes.c_void_p(d_alb_ptr or None), pitch,
                                                   ctypes.c_void_p(d_counters_ptr or None), ctypes.c_void_p(stream_ptr or None)))
+
+    def query_hits(self, rays, counters: bool = False):
+        """pt_query_hits: the closest hit of every ray (rays: [n, 8] f32 — o, tmax, d, reserved — or
+        RAY_DTYPE records; d is not normalised and t is in its units).  Returns [n, 8] f32 (p, t, n,
+        material as int32 bits: `.view(pt_amd.HIT_DTYPE)` names the fields; a miss is t = -1,
+        material = -1), and the counters if requested."""
+        r = _rays(rays)
+        out = np.zeros((r.shape[0], 8), np.float32)
+        c = Counters()
+        _check(self._lib.pt_query_hits(self._h, _ptr(r), r.shape[0], _ptr(out), ctypes.byref(c) if counters else None))
+        return (out, c.as_dict()) if counters else out
+
+    def query_occluded(self, rays, counters: bool = False):
+        """pt_query_occluded: uint8 [n], 1 where the ray's closest hit lies below its tmax (the segment
+        is blocked), computed with early exit; and the counters if requested."""
+        r = _rays(rays)
+        out = np.zeros(r.shape[0], np.uint8)
+        c = Counters()
+        _check(self._lib.pt_query_occluded(self._h, _ptr(r), r.shape[0], _ptr(out), ctypes.byref(c) if counters else None))
+        return (out, c.as_dict()) if counters else out
+
+    def camera_rays(self, meta, frame: int, window=None) -> np.ndarray:
+        """pt_camera_rays: [h, w, 8] f32, the rays the render traces for the window's pixels in `frame`
+        (tmax = +inf), ready for query_hits."""
+        meta = _f32(meta)
+        win = _window(window)
+        W, H = _extent(meta, win)
+        out = np.zeros((H, W, 8), np.float32)
+        _check(self._lib.pt_camera_rays(self._h, _ptr(meta), ctypes.byref(win) if win is not None else None,
+                                        _uint(frame, "frame"), _ptr(out)))
+        return out
+
+    def query_hits_async(self, d_rays_ptr: int, n: int, d_hits_ptr: int, stream_ptr: int = 0, d_counters_ptr: int = 0):
+        """pt_query_hits_async: n pt_ray records at d_rays_ptr -> n pt_hit records at d_hits_ptr (device
+        memory, both 16-byte aligned), asynchronous on the stream."""
+        _check(self._lib.pt_query_hits_async(self._h, ctypes.c_void_p(d_rays_ptr or None), n,
+                                             ctypes.c_void_p(d_hits_ptr or None), ctypes.c_void_p(d_counters_ptr or None),
+                                             ctypes.c_void_p(stream_ptr or None)))
+
+    def query_occluded_async(self, d_rays_ptr: int, n: int, d_occluded_ptr: int, stream_ptr: int = 0,
+                             d_counters_ptr: int = 0):
+        """pt_query_occluded_async: n pt_ray records -> n bytes at d_occluded_ptr."""
+        _check(self._lib.pt_query_occluded_async(self._h, ctypes.c_void_p(d_rays_ptr or None), n,
+                                                 ctypes.c_void_p(d_occluded_ptr or None),
+                                                 ctypes.c_void_p(d_counters_ptr or None), ctypes.c_void_p(stream_ptr or None)))
+
+    def camera_rays_async(self, meta, frame: int, d_rays_ptr: int, stream_ptr: int = 0, window=None):
+        """pt_camera_rays_async: the window's w * h pt_ray records to d_rays_ptr (16-byte aligned)."""
+        meta = _f32(meta)
+        win = _window(window)
+        _check(self._lib.pt_camera_rays_async(self._h, _ptr(meta), ctypes.byref(win) if win is not None else None,
+                                              _uint(frame, "frame"), ctypes.c_void_p(d_rays_ptr or None),
+                                              ctypes.c_void_p(stream_ptr or None)))
 
     def denoise(self, accum, m2, geo, alb, feature_frames: int, frames, tile=None, params=None):
         """pt_denoise: the variance-guided a-trous filter over the host accumulators accum, m2 [h, w, 3]

@@ -321,6 +321,68 @@ int pt_render_denoised_image(pt_scene* scene, const float meta[48], uint32_t fra
                              uint32_t frame_stride, int max_depth, int mode, uint32_t feature_frames,
                              const pt_denoise_params* params, uint8_t* rgba_out, pt_counters* counters);
 
+/* Ray queries: the traversal itself, for rays the caller supplies — what does this ray hit, is this
+ * segment blocked.  The answers are the reference's intersect() (src/wgsl-util/intersection-logic.wgsl),
+ * bit for bit, whatever kernel, grid or option computes them.
+ *
+ * The ray is (o, d) exactly as given: d is NOT normalised, and every t is in units of d — a ray with
+ * d = target - o and tmax = 1 asks the visibility question between two points.  The traversal takes
+ * inv = 1 / d per component by IEEE division (a zero component gives +-inf, as in the reference), and
+ * the triangle test takes 1 / det by IEEE division too.  `reserved` is ignored (it need not be 0). */
+typedef struct { float o[3]; float tmax; float d[3]; uint32_t reserved; } pt_ray;   /* 32 B */
+typedef struct { float p[3]; float t;    float n[3]; int32_t  material; } pt_hit;   /* 32 B */
+
+/* Closest hits.  For ray i, h = the reference's intersect(ray): its marker-stack order, its pruning of
+ * a child whose box distance exceeds the closest t so far (the exit distance for an origin inside the
+ * box: the reference's quirk, kept), a triangle taken on strict t < closest, so the first of equal t.
+ *   h.intersected and h.t < tmax:  hits[i] = { p = o + t*d (one fma per component, as the reference's
+ *       hit point), t, n = the shading normal (pt_scene_set_vertex_normals is honoured), material }
+ *   otherwise (no hit, t >= tmax, or tmax NaN — the comparison is false):
+ *       hits[i] = { p = 0, t = -1, n = 0, material = -1 }
+ * tmax = +inf asks for the closest hit without a limit.  tmax only filters the REPORT; the traversal
+ * and its counters are those of the unlimited query.
+ * Counters (nullable, added to): ext_queries += n; nodes, tri_tests and box_tests the traversal's;
+ * samples and shadow_queries untouched.
+ * n = 0: PT_OK, nothing is touched.  n > 2^30, a null pointer with n > 0, or (the _async forms) d_rays
+ * or d_hits not 16-byte aligned: PT_ERR_INVALID.  The _async forms take device pointers and run on
+ * `stream`; a device-side failure of an earlier asynchronous call on the scene surfaces here as in
+ * pt_render_async.  The blocking forms copy the rays in, run on the scene's own stream and copy the
+ * results out (host buffers of any alignment the types allow); their device scratch belongs to the scene
+ * (grown on demand, counted in device_bytes while held, freed by pt_scene_destroy).
+ * A batch is traced in launches of at most 2^22 rays, in order on the stream.  Every wave of a launch
+ * reaches an exit: one that is still tracing after option trace_watchdog iterations (default 2^24) or
+ * 5 s of wall clock gives up, the call's results are invalid, later query launches of the scene skip,
+ * and pt_scene_check or the next call on the scene reports PT_ERR_HIP (as for a traversal wave of a
+ * render).  The limit is per launch, so it does not bound the batch: 2^22 rays in 5 s is 0.8 Mrays/s,
+ * two orders of magnitude below the slowest rate measured. */
+int pt_query_hits(pt_scene* scene, const pt_ray* rays, size_t n, pt_hit* hits, pt_counters* counters);
+int pt_query_hits_async(pt_scene* scene, const pt_ray* d_rays, size_t n, pt_hit* d_hits, pt_counters* d_counters,
+                        void* stream);
+
+/* Occlusion.  occluded[i] = 1 iff the reference's intersect(ray i) reports a hit with t < tmax, else 0:
+ * DEFINED by the closest-hit result above, COMPUTED with early exit.  During the reference's traversal
+ * the closest t so far only decreases (a triangle replaces it on strict <).  So
+ *   - if any triangle test of the traversal succeeds with t < tmax, the final closest t is < tmax: 1;
+ *   - if none does, the traversal ends without a hit or with every accepted t >= tmax: 0.
+ * A ray may therefore stop at its first successful test with t < tmax: up to that test its traversal is
+ * the reference's (same order, same pruning), and the value is decided — whichever traversal flavour
+ * runs.  With tmax = +inf the query stops at the first hit of any kind; tmax <= 0 or NaN never stops
+ * early and gives 0.
+ * Counters (nullable, added to): shadow_queries += n; nodes, tri_tests and box_tests what the shortened
+ * traversals did (<= pt_query_hits' on the same rays); samples and ext_queries untouched.
+ * Arguments and errors as pt_query_hits (occluded: n bytes, any alignment). */
+int pt_query_occluded(pt_scene* scene, const pt_ray* rays, size_t n, uint8_t* occluded, pt_counters* counters);
+int pt_query_occluded_async(pt_scene* scene, const pt_ray* d_rays, size_t n, uint8_t* d_occluded,
+                            pt_counters* d_counters, void* stream);
+
+/* The camera rays of a window (NULL = the whole image), w * h records, row-major: ray (y - y0) * w +
+ * (x - x0) is the ray the render and pt_render_features trace for pixel (x, y) in frame `frame` — the
+ * jittered pinhole ray of salt t = u32(f32(frame)), a unit direction — with tmax = +inf and
+ * reserved = 0.  frame >= 2^24 is rejected, as everywhere.  d_rays: device memory, 16-byte aligned. */
+int pt_camera_rays(pt_scene* scene, const float meta[48], const pt_window* win, uint32_t frame, pt_ray* rays);
+int pt_camera_rays_async(pt_scene* scene, const float meta[48], const pt_window* win, uint32_t frame, pt_ray* d_rays,
+                         void* stream);
+
 /* Completion check of the asynchronous calls: waits for every render of the scene to finish
  * (blocking) and reports a device-side failure of any of them — a wavefront traversal wave that
  * gave up after its watchdog limit leaves a flag instead of hanging, and the accumulators of
@@ -368,6 +430,11 @@ int pt_set_hw_queues(int n);
  *   "denoise_lds"   0 | 1 | 2 | 3 | 4   (pt_denoise_async: the first that many passes — steps 1, 2, 4, 8 — stage
  *                                        their block's (16 + 4 s)^2 region in LDS, the others load their taps
  *                                        from global memory; default 2, the measured best)
+ *   "query_refill"  0 | 1               (pt_query_*: 1 = default, a lane that finishes its ray takes the next ray of
+ *                                        its wave's window at once; 0: a wave takes new rays only when all its 64
+ *                                        lanes are idle — the one-lane-per-pixel kernels' scheme, kept for A/B runs)
+ *   "query_blocks"  integer             (pt_query_*: the grid in blocks of 4 waves; 0 = default, by occupancy and
+ *                                        batch size; tests use 1 to make a small batch run many windows per wave)
  * DESIGN.md §6 describes each.  pt_get_option writes the current value ("" = default) into buf. */
 int pt_set_option(const char* name, const char* value);
 int pt_get_option(const char* name, char* buf, size_t cap);
