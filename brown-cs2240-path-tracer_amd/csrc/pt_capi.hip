@@ -1788,6 +1788,24 @@ int pt_selftest_leaf(pt_scene* s, int leaf, int mode, uint32_t seed, uint32_t nr
     return PT_OK;
 }
 
+int pt_selftest_lights(pt_scene* s, const uint32_t* seeds, const float* points, size_t n, float* out) {
+    if (!s || !seeds || !points || !out) return fail(PT_ERR_INVALID, "null argument");
+    if (n == 0 || n > (1u << 24)) return fail(PT_ERR_INVALID, "bad sample count");
+    HIP_TRY(hipSetDevice(s->device));
+    uint32_t* dseeds = nullptr;
+    float *dpts = nullptr, *dout = nullptr;
+    hipError_t e = hipMalloc(&dseeds, n * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMalloc(&dpts, n * 3 * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc(&dout, n * 4 * sizeof(float));
+    if (e == hipSuccess) e = hipMemcpy(dseeds, seeds, n * sizeof(uint32_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dpts, points, n * 3 * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = launch_selftest_lights(s->view, dseeds, dpts, (uint32_t)n, dout, nullptr);
+    if (e == hipSuccess) e = hipMemcpy(out, dout, n * 4 * sizeof(float), hipMemcpyDeviceToHost);
+    hipFree(dseeds); hipFree(dpts); hipFree(dout);
+    if (e != hipSuccess) return fail(PT_ERR_HIP, hipGetErrorString(e));
+    return PT_OK;
+}
+
 int pt_selftest_rcp(int device, int steps, uint32_t lo_bits, uint32_t hi_bits, uint64_t* mismatches,
                     uint32_t* failing_bits) {
     if (!mismatches || steps < -1 || steps > 2 || lo_bits > hi_bits || hi_bits >= 0x80000000u)

@@ -206,5 +206,8 @@ hipError_t launch_selftest_leafpass(const SceneView& sc, int b, int mode, uint32
                                     hipStream_t stream);
 hipError_t launch_selftest_leaf(const SceneView& sc, int rec0, int n, int mode, uint32_t seed, uint32_t nrays, int32_t* out,
                                 hipStream_t stream);
+// sample_area_lights for n caller-supplied (seed, point): out n x 4 (direction, bits of the slot k)
+hipError_t launch_selftest_lights(const SceneView& sc, const uint32_t* seeds, const float* points, uint32_t n, float* out,
+                                  hipStream_t stream);
 
 }  // namespace pt

@@ -408,6 +408,28 @@ hipError_t launch_selftest_leaf(const SceneView& sc, int rec0, int n, int mode, 
     return hipGetLastError();
 }
 
+// Light sampling slot by slot (pt_selftest_lights): sample_area_lights as the shade code calls it, for
+// the caller's (seed, x).  Row i of out: the direction and the bits of the slot k it drew (k == n_lights,
+// the table's last entry, when hash1 is exactly 1).
+__global__ __launch_bounds__(256) void k_selftest_lights(SceneView sc, const uint32_t* __restrict__ seeds,
+                                                         const float* __restrict__ points, uint32_t n,
+                                                         float* __restrict__ out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t seed = seeds[i];
+    const f3 d = sample_area_lights(sc, mk(points[3 * (size_t)i], points[3 * (size_t)i + 1], points[3 * (size_t)i + 2]), seed);
+    const int k = (int)(hash1(seed * 7u + 11u) * sc.f_ntri);
+    float* o = out + 4 * (size_t)i;
+    o[0] = d.x; o[1] = d.y; o[2] = d.z;
+    o[3] = __builtin_bit_cast(float, k);
+}
+
+hipError_t launch_selftest_lights(const SceneView& sc, const uint32_t* seeds, const float* points, uint32_t n, float* out,
+                                  hipStream_t stream) {
+    hipLaunchKernelGGL(k_selftest_lights, dim3((n + 255) / 256), dim3(256), 0, stream, sc, seeds, points, n, out);
+    return hipGetLastError();
+}
+
 __global__ void k_selftest_math(int fn, const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ o,
                                 int n) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;

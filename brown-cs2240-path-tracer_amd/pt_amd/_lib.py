@@ -340,7 +340,8 @@ def load_library():
     i32p = ctypes.POINTER(ctypes.c_int32)
     L.pt_scene_leaf_bvh.argtypes = [p, i, i32p, i32p, i32p]
     L.pt_selftest_leaf.argtypes = [p, i, i, u32, u32, p]
-    for fn in ("pt_render_moments", "pt_render_moments_async", "pt_noise_tiles_async", "pt_noise_tiles", "pt_tile_mean_async",
+    L.pt_selftest_lights.argtypes = [p, p, p, sz, p]
+    for fn in ("pt_selftest_lights","pt_render_moments", "pt_render_moments_async", "pt_noise_tiles_async", "pt_noise_tiles", "pt_tile_mean_async",
                "pt_render_adaptive", "pt_selftest_tile_rects", "pt_render_window", "pt_render_window_async", "pt_frame_window", "pt_scene_leaf_bvh", "pt_selftest_leaf", "pt_selftest_valu", "pt_set_option", "pt_get_option", "pt_release_communicators", "pt_scene_check", "pt_set_hw_queues", "pt_render_multi", "pt_bvh_build_sah", "pt_bvh_build_sah2", "pt_device_count", "pt_scene_create", "pt_scene_get_info", "pt_render", "pt_render_async", "pt_frame",
                "pt_frame_async", "pt_tonemap", "pt_selftest_math", "pt_profile_enable", "pt_profile_select", "pt_profile_read", "pt_selftest_rcp", "pt_bvh_build", "pt_tonemap_async", "pt_readback_async", "pt_render_image",
                "pt_scene_set_vertex_normals"):
@@ -494,6 +495,17 @@ class Scene:
         out = np.zeros((nrays, 6), np.int32)
         _check(self._lib.pt_selftest_leaf(self._h, leaf, mode, seed, nrays, _ptr(out)))
         return out
+
+    def selftest_lights(self, seeds, points):
+        """pt_selftest_lights: the device's sample_area_lights for seeds [n] (uint32) and points [n, 3]:
+        (directions [n, 3] float32, slots k [n] int32; k == Ntri is the table's clamped last entry)."""
+        seeds = np.ascontiguousarray(seeds, np.uint32)
+        points = _f32(points)
+        if seeds.ndim != 1 or points.shape != (seeds.size, 3):
+            raise ValueError("seeds must be [n] and points [n, 3]")
+        out = np.zeros((seeds.size, 4), np.float32)
+        _check(self._lib.pt_selftest_lights(self._h, _ptr(seeds), _ptr(points), seeds.size, _ptr(out)))
+        return out[:, :3].copy(), out[:, 3].copy().view(np.int32)
 
     def render(self, meta, frame0: int, nframes: int, stride: int = 1, max_depth: int = -1, mode: int = MODE_AUTO,
                accum: np.ndarray | None = None, counters: bool = False, window=None):

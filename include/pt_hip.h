@@ -584,6 +584,13 @@ int pt_scene_leaf_bvh(const pt_scene* scene, int leaf, int32_t* first_record, in
  * bits), 4-5 zero.  Blocking. */
 int pt_selftest_leaf(pt_scene* scene, int leaf, int mode, uint32_t seed, uint32_t nrays, int32_t* out);
 
+/* Light sampling self-test: the shade code's sample_area_lights ON THE DEVICE for n caller-supplied
+ * (seeds[i], points[3i..3i+2]): the direction from the point to the sampled point of the emissive
+ * triangle the seed draws.  out (host, n x 4 f32): the direction, then the bit pattern of the int32
+ * slot k = i32(hash1(seed * 7 + 11) * Ntri) it read, 0 <= k <= Ntri (k == Ntri, when hash1 is exactly
+ * 1, is the reference's out-of-range branch resolved with clamped reads).  Blocking. */
+int pt_selftest_lights(pt_scene* scene, const uint32_t* seeds, const float* points, size_t n, float* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -72,6 +72,7 @@ def lib():
         L.po_render.argtypes = [p, u32, p, u32, p, u32, u32, u32, u32, u32, i32, p, p, i32]
         L.po_ray_bbox.restype = f; L.po_ray_bbox.argtypes = [p, p, p, p]
         L.po_intersect.restype = i32; L.po_intersect.argtypes = [p, u32, p, u32, p, p, p, p]
+        L.po_sample_area_lights.restype = i32; L.po_sample_area_lights.argtypes = [p, u32, p, u32, p]
         L.po_tonemap.restype = None; L.po_tonemap.argtypes = [p, ctypes.c_uint64, u32, p]
         L.po_set_vertex_normals.restype = None; L.po_set_vertex_normals.argtypes = [i32]
         _lib = L
@@ -134,6 +135,21 @@ def intersect(tri, bvh, p, d):
     c = Counters()
     hit = lib().po_intersect(_ptr(tri), tri.size, _ptr(bvh), bvh.size, _ptr(p4), _ptr(d4), _ptr(out), ctypes.byref(c))
     return bool(hit), out, c.as_dict()
+
+
+def sample_area_lights(tri, points, seeds):
+    """The reference's sample_area_lights for points [n, 3] and seeds [n]: (directions [n, 3] float32,
+    slots k [n] int32, the MC weight 1 / Ntri).  k == Ntri (hash1 exactly 1) takes the reference's
+    else-branch past range 4 with clamped reads."""
+    tri, points = _f32(tri), _f32(points)
+    seeds = np.ascontiguousarray(seeds, np.uint32)
+    dirs, ks = np.zeros((seeds.size, 3), np.float32), np.zeros(seeds.size, np.int32)
+    out = np.zeros(4, np.float32)
+    f = lib().po_sample_area_lights
+    for j in range(seeds.size):
+        ks[j] = f(_ptr(tri), tri.size, _ptr(points[j]), int(seeds[j]), _ptr(out))
+        dirs[j] = out[:3]
+    return dirs, ks, float(out[3])
 
 
 def ray_bbox(p, d, mn, mx) -> float:

@@ -400,7 +400,7 @@ static v3 sample_triangle_3D(v3 p0, v3 p1, v3 p2, uint32_t seed) {
 }
 
 /* intersection-logic.wgsl:217-285 */
-static v4 sample_area_lights(const scene_t *s, v3 x, int32_t seed) {
+static v4 sample_area_lights(const scene_t *s, v3 x, int32_t seed, int32_t *k_out) {
     int32_t e1s = (int32_t)P(s, 8), e1e = (int32_t)P(s, 9), e2s = (int32_t)P(s, 10), e2e = (int32_t)P(s, 11);
     int32_t e3s = (int32_t)P(s, 12), e3e = (int32_t)P(s, 13), e4s = (int32_t)P(s, 14), e4e = (int32_t)P(s, 15);
     int32_t n1 = 0, n2 = 0, n3 = 0, n4 = 0;
@@ -410,6 +410,7 @@ static v4 sample_area_lights(const scene_t *s, v3 x, int32_t seed) {
     if (e4s != -1) n4 += (e4e - e4s) / 4;
     int32_t ntri = n1 + n2 + n3 + n4;
     int32_t k = (int32_t)(po_hash1((uint32_t)seed * 7u + 11u) * (float)ntri);
+    if (k_out) *k_out = k;
     int32_t idx;
     if (k < n1) idx = k * 4 + e1s;
     else if (k < n1 + n2) idx = (k - n1) * 4 + e2s;
@@ -468,7 +469,7 @@ static v3 radiance(const scene_t *s, ray_t ray, int32_t seed_in, float rr_prob, 
         }
         /* direct lighting (NEE) */
         v4 off = V4(fmaf(n4.x, 1.0e-4f, p4.x), fmaf(n4.y, 1.0e-4f, p4.y), fmaf(n4.z, 1.0e-4f, p4.z), fmaf(n4.w, 1.0e-4f, p4.w));
-        v4 sal = sample_area_lights(s, xyz(off), (int32_t)seed);
+        v4 sal = sample_area_lights(s, xyz(off), (int32_t)seed, NULL);
         v4 ldir = V4(sal.x, sal.y, sal.z, 0.0f);
         float mc = sal.w;
         seed = po_hash1u(seed + 7u);
@@ -694,6 +695,15 @@ EXPORT void po_render(const float *tri, uint32_t tri_len, const float *bvh, uint
 EXPORT float po_ray_bbox(const float *p, const float *d, const float *mn, const float *mx) {
     ray_t r; r.p = V4(p[0], p[1], p[2], p[3]); r.d = V4(d[0], d[1], d[2], d[3]); r.d_inv = inv4(r.d);
     return ray_bbox(&r, V3(mn[0], mn[1], mn[2]), V3(mx[0], mx[1], mx[2]));
+}
+/* sample_area_lights for one (x, seed).  out: direction xyz, the MC weight 1 / Ntri; returns the slot k
+ * (k == Ntri when hash1 is exactly 1: the else-branch's index past range 4, read with clamped indexing) */
+EXPORT int32_t po_sample_area_lights(const float *tri, uint32_t tri_len, const float *x, uint32_t seed, float *out) {
+    scene_t s = {tri, tri_len, NULL, 0};
+    int32_t k = 0;
+    v4 r = sample_area_lights(&s, V3(x[0], x[1], x[2]), (int32_t)seed, &k);
+    out[0] = r.x; out[1] = r.y; out[2] = r.z; out[3] = r.w;
+    return k;
 }
 /* out: point xyz, normal xyz, t, material_id; returns intersected */
 EXPORT int po_intersect(const float *tri, uint32_t tri_len, const float *bvh, uint32_t bvh_len, const float *p,

@@ -237,6 +237,28 @@ def test_math_pow_bitexact():
     assert same_bits(gpu, ref), mismatch_report(gpu, ref)
 
 
+def test_math_pow_bitexact_on_the_materials_domain():
+    """pow(q, Ns) as the shade code calls it: q a dot product of two unit vectors (it can pass 1 by a few
+    ulps, and be +-0 or tiny), Ns whatever the material record holds (tests/shade_scenes.py's tables:
+    0, the neighbours of 40 and 500, huge, negative, non-finite).  Every x with every y."""
+    one = np.float32(1.0)
+    near_one = [one]
+    for _ in range(8):
+        near_one = [np.nextafter(near_one[0], np.float32(0))] + near_one + [np.nextafter(near_one[-1], np.float32(2))]
+    x = np.concatenate([[0.0, -0.0, 1.4e-45, 1.17549435e-38], np.random.default_rng(40).uniform(0, 1, 4096), near_one,
+                        [1.0000005]]).astype(np.float32)
+    assert x[2] > 0 and len(set(near_one)) == 17
+    f40, inf = np.float32(40), np.float32(np.inf)
+    y = np.array([0, 1, 10, 17.5, np.nextafter(f40, -inf), 40, np.nextafter(f40, inf), 200, 500, 1000, 1e6, -1, -40, 3e38,
+                  np.inf, np.nan], np.float32)
+    xx, yy = np.repeat(x, len(y)), np.tile(y, len(x))
+    gpu = pt_amd.selftest_math("pow", xx, yy)
+    powf = oracle.lib().po_powf
+    ref = np.array([powf(float(a), float(b)) for a, b in zip(xx, yy)], np.float32)
+    bad = ~((bits(gpu) == bits(ref)) | (np.isnan(gpu) & np.isnan(ref)))
+    assert same_bits(gpu, ref), mismatch_report(gpu, ref) + f" at x {xx[bad][:5]} y {yy[bad][:5]}"
+
+
 def test_math_div_sqrt_correctly_rounded():
     a = (RNG.standard_normal(8192) * 10 ** RNG.uniform(-30, 30, 8192)).astype(np.float32)
     b = (RNG.standard_normal(8192) * 10 ** RNG.uniform(-30, 30, 8192)).astype(np.float32)
