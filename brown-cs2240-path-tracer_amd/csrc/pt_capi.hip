@@ -1806,6 +1806,16 @@ int pt_selftest_lights(pt_scene* s, const uint32_t* seeds, const float* points, 
     return PT_OK;
 }
 
+int pt_selftest_view_half_h(const float* metas, size_t n, float* out) {
+    if (!metas || !out) return fail(PT_ERR_INVALID, "null argument");
+    for (size_t i = 0; i < n; ++i) {
+        FrameParams fp;
+        if (int rc = make_params(metas + 48 * i, 0, fp); rc != PT_OK) return rc;
+        out[i] = fp.view_half_h;
+    }
+    return PT_OK;
+}
+
 int pt_selftest_rcp(int device, int steps, uint32_t lo_bits, uint32_t hi_bits, uint64_t* mismatches,
                     uint32_t* failing_bits) {
     if (!mismatches || steps < -1 || steps > 2 || lo_bits > hi_bits || hi_bits >= 0x80000000u)

@@ -45,6 +45,7 @@ from ._lib import (  # noqa: F401
     selftest_math,
     selftest_rcp,
     selftest_valu,
+    selftest_view_half_h,
     set_hw_queues,
     set_option,
     source_hash,

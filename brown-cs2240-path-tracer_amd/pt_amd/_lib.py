@@ -341,7 +341,8 @@ def load_library():
     L.pt_scene_leaf_bvh.argtypes = [p, i, i32p, i32p, i32p]
     L.pt_selftest_leaf.argtypes = [p, i, i, u32, u32, p]
     L.pt_selftest_lights.argtypes = [p, p, p, sz, p]
-    for fn in ("pt_selftest_lights","pt_render_moments", "pt_render_moments_async", "pt_noise_tiles_async", "pt_noise_tiles", "pt_tile_mean_async",
+    L.pt_selftest_view_half_h.argtypes = [p, sz, p]
+    for fn in ("pt_selftest_lights", "pt_selftest_view_half_h", "pt_render_moments", "pt_render_moments_async", "pt_noise_tiles_async", "pt_noise_tiles", "pt_tile_mean_async",
                "pt_render_adaptive", "pt_selftest_tile_rects", "pt_render_window", "pt_render_window_async", "pt_frame_window", "pt_scene_leaf_bvh", "pt_selftest_leaf", "pt_selftest_valu", "pt_set_option", "pt_get_option", "pt_release_communicators", "pt_scene_check", "pt_set_hw_queues", "pt_render_multi", "pt_bvh_build_sah", "pt_bvh_build_sah2", "pt_device_count", "pt_scene_create", "pt_scene_get_info", "pt_render", "pt_render_async", "pt_frame",
                "pt_frame_async", "pt_tonemap", "pt_selftest_math", "pt_profile_enable", "pt_profile_select", "pt_profile_read", "pt_selftest_rcp", "pt_bvh_build", "pt_tonemap_async", "pt_readback_async", "pt_render_image",
                "pt_scene_set_vertex_normals"):
@@ -1006,6 +1007,14 @@ def selftest_rcp(steps: int = -1, lo_bits: int = 0x00800000, hi_bits: int = 0x7E
     b = ctypes.c_uint32(0)
     _check(L.pt_selftest_rcp(device, steps, lo_bits, hi_bits, ctypes.byref(m), ctypes.byref(b)))
     return int(m.value), int(b.value)
+
+
+def selftest_view_half_h(metas) -> np.ndarray:
+    """pt_selftest_view_half_h: the host's view_half_h for meta blocks [n, 48] (needs no GPU)."""
+    metas = _f32(metas).reshape(-1, 48)
+    out = np.zeros(len(metas), np.float32)
+    _check(load_library().pt_selftest_view_half_h(_ptr(metas), len(metas), _ptr(out)))
+    return out
 
 
 def selftest_valu(iters: int = 20000, reps: int = 5, packed: int = 0, device: int = 0):

@@ -591,6 +591,12 @@ int pt_selftest_leaf(pt_scene* scene, int leaf, int mode, uint32_t seed, uint32_
  * 1, is the reference's out-of-range branch resolved with clamped reads).  Blocking. */
 int pt_selftest_lights(pt_scene* scene, const uint32_t* seeds, const float* points, size_t n, float* out);
 
+/* Camera self-test, host only (needs no device): out[i] = the view_half_h = 2 * focal * tan(vfov / 2)
+ * that every render, frame, feature and camera-ray call derives ON THE HOST from metas[48 i ..
+ * 48 i + 47] (meta[2] and meta[3]; the kernels take it as a uniform), for n meta blocks.  The blocks
+ * pass the same checks as a render's (meta[0..1] integral resolutions). */
+int pt_selftest_view_half_h(const float* metas, size_t n, float* out);
+
 #ifdef __cplusplus
 }
 #endif
