@@ -52,7 +52,7 @@ constexpr OptSpec kOptSpecs[] = {
     {"lds", OPT_BOOL, nullptr},          {"fastrcp", OPT_BOOL, nullptr},     {"dual", OPT_BOOL, nullptr},
     {"fuse", OPT_BOOL, nullptr},         {"fuse_gen", OPT_BOOL, nullptr},    {"bf", OPT_BOOL, nullptr},
     {"mailbox", OPT_BOOL, nullptr},      {"bf_stackless", OPT_BOOL, nullptr}, {"trace_sparse", OPT_INT, nullptr},
-    {"bf_narrow", OPT_BOOL, nullptr},
+    {"bf_narrow", OPT_BOOL, nullptr},    {"step_addr64", OPT_BOOL, nullptr},
     {"region_perm", OPT_BOOL, nullptr},  {"regen", OPT_INT, nullptr},  {"trace_ring", OPT_INT, nullptr},
     {"parts", OPT_INT, nullptr},         {"sort", OPT_INT, nullptr},
     {"node_bias", OPT_INT, nullptr},     {"node_steps", OPT_INT, nullptr},     {"big_leaf", OPT_INT, nullptr},     {"bf_slots", OPT_INT, nullptr},
@@ -284,6 +284,7 @@ extern "C" {
 int pt_abi_version(void) { return PT_ABI_VERSION; }
 
 int pt_last_bf_width(void) { return pt::last_bf_width(); }
+int pt_last_step_addr(void) { return pt::last_step_addr(); }
 
 int pt_profile_enable(pt_scene* s, int enable) {
     if (!s) return fail(PT_ERR_INVALID, "null scene");
@@ -564,6 +565,7 @@ LaunchOpts launch_opts(const Opts& o, int mode, uint64_t paths, const SceneView&
     lo.trace_blocks = (int)o.num("wf_trace_blocks", lo.trace_blocks);
     lo.watchdog = (uint32_t)o.num("trace_watchdog", lo.watchdog);
     lo.bf_slots = (int)o.num("bf_slots", lo.bf_slots);
+    lo.step_addr64 = flag("step_addr64", lo.step_addr64);
     lo.leaf_blocks = (int)o.num("leaf_blocks", lo.leaf_blocks);
     // | 4: the pair walk's second check of the open chunks with the entries' own normals (option
     // leaf_refine, default on; pt_leafpass.hip)

@@ -106,6 +106,7 @@ struct LaunchOpts {
     // 512, MedievalBoat unchanged, in-process A/B)
     int sort = 512;
     int bf_slots = kBfSlots; // brute-force kernels: hit slots per lane (fewer: tests of the recompute path)
+    bool step_addr64 = false;  // fused kernel: the 64-bit addressing instance whatever the part's size (tests)
     int trace_blocks = 0;    // traversal / step kernels: cap on the grid (tests): 0 = occupancy-derived
     // k_wf_trace narrows its windows when 32-entry ones would keep < 1/n of the waves busy (0 off;
     // 4 in-process A/B: MedievalBoat +16 %, Glossy and the synthetic scenes +-0.5 %)

@@ -9,11 +9,12 @@
 #include "pt_flavour.h"
 #include "pt_query_plan.h"
 #include "pt_rect_plan.h"
+#include "pt_step_addr.h"
 
 // ids for k_selftest_math (also used by pt_selftest_math in the C-ABI)
 enum {
     PT_MATH_SIN = 0, PT_MATH_COS, PT_MATH_TAN, PT_MATH_ACOS, PT_MATH_LOG2, PT_MATH_EXP2, PT_MATH_POW, PT_MATH_SQRT,
-    PT_MATH_DIV, PT_MATH_HASH1U, PT_MATH_HASH1, PT_MATH_HASH2X, PT_MATH_HASH2Y, PT_MATH_MIN, PT_MATH_MAX, PT_MATH_COUNT_
+    PT_MATH_DIV, PT_MATH_HASH1U, PT_MATH_HASH1, PT_MATH_HASH2X, PT_MATH_HASH2Y, PT_MATH_MIN, PT_MATH_MAX, PT_MATH_RAY_INV, PT_MATH_COUNT_
 };
 
 namespace pt {
@@ -143,6 +144,9 @@ hipError_t launch_wavefront(const LaunchOpts& lo, const SceneView& sc, const Fra
 // set width (32 / 64 bits) of the stackless replay in the fused kernel launched last in this process
 // (0: none yet, or the stack walk) — pt_last_bf_width, for the tests of the narrow instance
 int last_bf_width();
+// offset width (32 / 64 bits) of the queue addressing in the fused kernel launched last in this process
+// (0: none yet) — pt_last_step_addr, for the tests of the 64-bit instance
+int last_step_addr();
 
 // Megakernel render (accum=true: frames frame0 + i*stride, i < nframes, added to out) or one
 // dispatch (accum=false: raw radiance of salt frame0 written to out).  m2 (accum only, as in

@@ -452,6 +452,12 @@ __global__ void k_selftest_math(int fn, const float* __restrict__ a, const float
         case PT_MATH_HASH2Y: hash2(u, s, r); break;
         case PT_MATH_MIN: r = fminf(x, y); break;
         case PT_MATH_MAX: r = fmaxf(x, y); break;
+        case PT_MATH_RAY_INV: {  // a: n / 3 triples; thread i takes triple i, so a wave votes on 64 consecutive ones
+            if (3 * i + 2 >= n) return;
+            const f3 v = ray_inv(mk(a[3 * i], a[3 * i + 1], a[3 * i + 2]));
+            o[3 * i] = v.x; o[3 * i + 1] = v.y; o[3 * i + 2] = v.z;
+            return;
+        }
         default: r = __builtin_nanf(""); break;
     }
     o[i] = r;

@@ -25,6 +25,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cstddef>
 #include <cstdlib>
 #include <map>
 #include <mutex>
@@ -81,20 +82,39 @@ __device__ __forceinline__ void unpack_dspec(uint32_t dw, PathState& ps) {
     ps.depth = (int)(dw & 0xffffu);
     ps.spec = (dw & 0x10000u) != 0;
 }
+// FAST_INV (the fused kernel's FAST_RCP instances only): 1 / d from ray_inv (pt_math.h), the same bits
+template <bool FAST_INV = false>
 __device__ __forceinline__ Ray unpack_ray(float4 a, float4 b, uint32_t& p) {
     Ray r;
     r.o = mk(a.x, a.y, a.z);
     r.d = mk(a.w, b.x, b.y);
-    r.inv = rcp3(r.d);
+    r.inv = FAST_INV ? ray_inv(r.d) : rcp3(r.d);
     p = __builtin_bit_cast(uint32_t, b.z);
     return r;
 }
+// Element i of a queue array.  A32 (the fused kernel's 32-bit instances; pt_step_addr.h says when the
+// host may launch them): the wave-uniform base stays in SGPRs and the lane adds a 32-bit BYTE offset
+// (global_load/store v_off, s[base:base+1]), so no access costs 64-bit VALU; a neighbour element
+// (q_at(..)[1]) rides in the instruction's immediate offset.  Otherwise base + (size_t)i as ever.
+template <bool A32, class T>
+__device__ __forceinline__ T* q_at(T* base, uint32_t i) {
+    if constexpr (A32) return reinterpret_cast<T*>(reinterpret_cast<char*>(base) + (uint32_t)(i * (uint32_t)sizeof(T)));
+    else return base + (size_t)i;
+}
+// the two float4 of entry i of WfQueue::ray (the index doubles in 64 bits in the wide form)
+template <bool A32>
+__device__ __forceinline__ float4* ray_at(float4* ray, uint32_t i) {
+    if constexpr (A32) return reinterpret_cast<float4*>(reinterpret_cast<char*>(ray) + (uint32_t)(i * 32u));
+    else return ray + 2 * (size_t)i;
+}
 // queue entry i <- (ray, path index, path state)
+template <bool A32 = false>
 __device__ __forceinline__ void store_entry(const WfQueue& Q, uint32_t i, const Ray& r, uint32_t p, const PathState& ps) {
-    Q.ray[2 * (size_t)i] = make_float4(r.o.x, r.o.y, r.o.z, r.d.x);
-    Q.ray[2 * (size_t)i + 1] = make_float4(r.d.y, r.d.z, __builtin_bit_cast(float, p), __builtin_bit_cast(float, pack_dspec(ps)));
-    Q.q2[i] = make_float4(ps.L.x, ps.L.y, ps.L.z, __builtin_bit_cast(float, ps.seed));
-    Q.q3[i] = make_float4(ps.beta.x, ps.beta.y, ps.beta.z, 0.0f);
+    float4* ray = ray_at<A32>(Q.ray, i);
+    ray[0] = make_float4(r.o.x, r.o.y, r.o.z, r.d.x);
+    ray[1] = make_float4(r.d.y, r.d.z, __builtin_bit_cast(float, p), __builtin_bit_cast(float, pack_dspec(ps)));
+    *q_at<A32>(Q.q2, i) = make_float4(ps.L.x, ps.L.y, ps.L.z, __builtin_bit_cast(float, ps.seed));
+    *q_at<A32>(Q.q3, i) = make_float4(ps.beta.x, ps.beta.y, ps.beta.z, 0.0f);
 }
 __device__ __forceinline__ Ray load_entry(const WfQueue& Q, uint32_t i, uint32_t& p, PathState& ps) {
     const float4 a = Q.ray[2 * (size_t)i], b = Q.ray[2 * (size_t)i + 1], c = Q.q2[i], d = Q.q3[i];
@@ -126,22 +146,25 @@ __device__ __forceinline__ void load_shading_point(const WfBuffers& wb, uint32_t
 //   ray[2i]   = (d.xyz, path)      ray[2i+1] = (depth | spec, L.xyz)   q2 = (seed, beta.xyz)
 //   q3        = (hp.xyz, material) sp0      = (hn.xyz, wi.x)          sp2 = (wi.y, wi.z)
 // (sp1 unused).  The traversal pipeline (k_wf_trace + k_wf_shade) keeps the full layout above.
+template <bool A32 = false>
 __device__ __forceinline__ void store_shadow_packed(const WfBuffers& wb, uint32_t i, const Ray& r, uint32_t p,
                                                     const PathState& ps) {
     const WfQueue& Q = wb.shd;
-    Q.ray[2 * (size_t)i] = make_float4(r.d.x, r.d.y, r.d.z, __builtin_bit_cast(float, p));
-    Q.ray[2 * (size_t)i + 1] = make_float4(__builtin_bit_cast(float, pack_dspec(ps)), ps.L.x, ps.L.y, ps.L.z);
-    Q.q2[i] = make_float4(__builtin_bit_cast(float, ps.seed), ps.beta.x, ps.beta.y, ps.beta.z);
-    Q.q3[i] = make_float4(ps.hp.x, ps.hp.y, ps.hp.z, __builtin_bit_cast(float, ps.mat_id));
-    wb.sp0[i] = make_float4(ps.hn.x, ps.hn.y, ps.hn.z, ps.wi.x);
-    wb.sp2[i] = make_float2(ps.wi.y, ps.wi.z);
+    float4* ray = ray_at<A32>(Q.ray, i);
+    ray[0] = make_float4(r.d.x, r.d.y, r.d.z, __builtin_bit_cast(float, p));
+    ray[1] = make_float4(__builtin_bit_cast(float, pack_dspec(ps)), ps.L.x, ps.L.y, ps.L.z);
+    *q_at<A32>(Q.q2, i) = make_float4(__builtin_bit_cast(float, ps.seed), ps.beta.x, ps.beta.y, ps.beta.z);
+    *q_at<A32>(Q.q3, i) = make_float4(ps.hp.x, ps.hp.y, ps.hp.z, __builtin_bit_cast(float, ps.mat_id));
+    *q_at<A32>(wb.sp0, i) = make_float4(ps.hn.x, ps.hn.y, ps.hn.z, ps.wi.x);
+    *q_at<A32>(wb.sp2, i) = make_float2(ps.wi.y, ps.wi.z);
 }
 // the ray of a packed shadow entry from its words (a = ray[2i], h = q3, n = sp0)
+template <bool FAST_INV = false>
 __device__ __forceinline__ Ray unpack_shadow_ray(float4 a, float4 h, float4 n, uint32_t& p) {
     Ray r;
     r.o = madd(mk(h.x, h.y, h.z), mk(n.x, n.y, n.z), 1.0e-4f);  // = path_after_ext's offset, bit for bit
     r.d = mk(a.x, a.y, a.z);
-    r.inv = rcp3(r.d);
+    r.inv = FAST_INV ? ray_inv(r.d) : rcp3(r.d);
     p = __builtin_bit_cast(uint32_t, a.w);
     return r;
 }
@@ -798,10 +821,38 @@ struct GenArgs {
     uint32_t frame0, stride, fbase, R, rg, P;
     bool raw_salt;
 };
+// k_wf_step_bf's arguments as they lie in its kernarg segment (each at its natural alignment, in order)
+struct StepKernArgs {
+    SceneView sc;
+    FrameParams fp;
+    WfBuffers wb;
+    int it;
+    Counters* cnt_out;
+    int nslots;
+    uint32_t frame0, stride, fbase, P;
+    bool raw_salt;
+    uint32_t q;
+};
+// The queue pointers the batch needs after the trace, read again from the kernarg segment (scalar
+// loads at the use) instead of held in SGPRs across phase 1, where they were spilled to VGPR lanes.
+// The asm keeps the loads behind the trace and inside the batch loop.
+__device__ __forceinline__ void step_reload_queues(WfBuffers& w) {
+    const __attribute__((address_space(4))) char* ka =
+        (const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(ka));
+    const __attribute__((address_space(4))) WfBuffers* k =
+        (const __attribute__((address_space(4))) WfBuffers*)(ka + offsetof(StepKernArgs, wb));
+    w.ext.ray = k->ext.ray; w.ext.q2 = k->ext.q2; w.ext.q3 = k->ext.q3;
+    w.shd.ray = k->shd.ray; w.shd.q2 = k->shd.q2; w.shd.q3 = k->shd.q3;
+    w.sp0 = k->sp0; w.sp2 = k->sp2; w.rad = k->rad;
+}
 // genk (GEN instances; wave-uniform): >= 0 makes this batch camera batch genk of the region
 // instead of queue batch b (the first launch); -1 reads the queue.
 // CAM: the batch's rays are camera rays (a fresh batch of the first launch: bf_closest's table)
-template <bool EXT, bool FAST_RCP, bool COUNT, bool GEN = false, bool CAM = GEN, bool NARROW = false, class Append>
+// A32: the queue arrays and `rad` by 32-bit byte offsets (q_at; the host launches these instances
+// when step_addr32_ok holds for the part, pt_step_addr.h)
+template <bool EXT, bool FAST_RCP, bool COUNT, bool GEN = false, bool CAM = GEN, bool NARROW = false, bool A32 = false,
+          class Append>
 __device__ __forceinline__ void bf_step_batch(const SceneView& sc, const Tri* gtris, const FrameParams& fp,
                                               const WfBuffers& wb, size_t rbase, uint32_t b, uint32_t count,
                                               const BfLds& l, int nslots, Counters& c, Append append,
@@ -810,12 +861,15 @@ __device__ __forceinline__ void bf_step_batch(const SceneView& sc, const Tri* gt
     const uint64_t t0 = ph_now();
 #endif
     const WfQueue& in = EXT ? wb.ext : wb.shd;
-    const WfQueue& out = EXT ? wb.shd : wb.ext;
     const uint32_t lane = lane_id();
     const bool fresh = GEN && genk >= 0;
     const uint32_t pg = fresh ? ((uint32_t)genk * gen.R + gen.rg) * 64 + lane : 0u;
     const bool valid = fresh ? pg < gen.P : b * 64 + lane < count;
-    const size_t e = rbase + ((valid && !fresh) ? b * 64 + lane : 0);
+    // the lane's entry (< qcap, a uint32_t) and its words' places in the input queue's arrays
+    const uint32_t e = (uint32_t)rbase + ((valid && !fresh) ? b * 64 + lane : 0);
+    const float4* const in_ray = ray_at<A32>(in.ray, e);
+    const float4* const in_q2 = q_at<A32>(in.q2, e);
+    const float4* const in_q3 = q_at<A32>(in.q3, e);
     float4 a0 = make_float4(0, 0, 0, 1), a1 = make_float4(0, 0, 0, 0);
     float4 c2 = make_float4(0, 0, 0, 0), d3 = c2;
     if (fresh) {
@@ -832,25 +886,27 @@ __device__ __forceinline__ void bf_step_batch(const SceneView& sc, const Tri* gt
             if (COUNT) { c.samples++; c.ext_queries++; }
         }
     } else if (EXT) {
-        a0 = in.ray[2 * e];
-        a1 = in.ray[2 * e + 1];
+        a0 = in_ray[0];
+        a1 = in_ray[1];
         if (!valid) { a0 = make_float4(0, 0, 0, 1); a1 = make_float4(0, 0, 0, 0); }
     }
     uint32_t p;
     Ray r;
     if (EXT || fresh) {
-        r = unpack_ray(a0, a1, p);
+        r = unpack_ray<FAST_RCP>(a0, a1, p);
     } else {  // packed shadow entry (store_shadow_packed): the origin from the shading point (its
               // words are read again after the trace, from cache, rather than held across it)
-        a0 = valid ? in.ray[2 * e] : make_float4(0, 0, 1, 0);
-        r = unpack_shadow_ray(a0, valid ? in.q3[e] : make_float4(0, 0, 0, 0),
-                              valid ? wb.sp0[e] : make_float4(0, 0, 0, 0), p);
+        // (loaded by every lane — an invalid lane's e is the region's first entry, inside the arrays — and
+        // then replaced: loads under `valid` cost a branch each and their addresses 64-bit VALU)
+        a0 = in_ray[0];
+        float4 h3 = *in_q3, n4 = *q_at<A32>(wb.sp0, e);
+        a1 = in_ray[1];  // the path state: below
+        c2 = *in_q2;
+        if (!valid) { a0 = make_float4(0, 0, 1, 0); h3 = make_float4(0, 0, 0, 0); n4 = h3; }
+        r = unpack_shadow_ray<FAST_RCP>(a0, h3, n4, p);
     }
     // the path state is loaded before the trace and arrives while it runs (+1.3 %)
-    if (!fresh) {
-        if (EXT) { c2 = in.q2[e]; d3 = in.q3[e]; }
-        else { a1 = in.ray[2 * e + 1]; c2 = in.q2[e]; }
-    }
+    if (!fresh && EXT) { c2 = *in_q2; d3 = *in_q3; }
     float t;
 #if PT_PHASE_STATS
     {
@@ -868,6 +924,8 @@ __device__ __forceinline__ void bf_step_batch(const SceneView& sc, const Tri* gt
 #endif
     bool more = false;
     PathState ps;
+    WfBuffers wk = wb;  // the buffers as used from here on
+    step_reload_queues(wk);
     if (valid) {
         if (EXT) {
             unpack_dspec(__builtin_bit_cast(uint32_t, a1.w), ps);
@@ -881,17 +939,19 @@ __device__ __forceinline__ void bf_step_batch(const SceneView& sc, const Tri* gt
             ps.L = mk(a1.y, a1.z, a1.w);
             ps.seed = __builtin_bit_cast(uint32_t, c2.x);
             ps.beta = mk(c2.y, c2.z, c2.w);
-            const float4 h3 = in.q3[e], n4 = wb.sp0[e];
+            // the shading point again (through the re-read pointers, which the compiler cannot match
+            // with the loads before the trace: read from cache here, not held across the trace)
+            const float4 h3 = *q_at<A32>(wk.shd.q3, e), n4 = *q_at<A32>(wk.sp0, e);
             ps.hp = mk(h3.x, h3.y, h3.z);
             ps.mat_id = __builtin_bit_cast(int, h3.w);
-            const float2 w2 = wb.sp2[e];
+            const float2 w2 = *q_at<A32>(wk.sp2, e);
             ps.hn = mk(n4.x, n4.y, n4.z);
             ps.wi = mk(n4.w, w2.x, w2.y);
             more = path_after_shadow(sc, fp, rec, t, r, ps);
             if (more && COUNT) c.ext_queries++;
         }
         if (!more) {
-            float* o = wb.rad + 3 * (size_t)p;
+            float* o = A32 ? q_at<true>(wk.rad, 3 * p) : wk.rad + 3 * (size_t)p;
             o[0] = ps.L.x; o[1] = ps.L.y; o[2] = ps.L.z;
         }
     }
@@ -910,8 +970,8 @@ __device__ __forceinline__ void bf_step_batch(const SceneView& sc, const Tri* gt
         if (more) {
             PH_ITER(PH_APPEND);
             const uint32_t j = (uint32_t)rbase + base + rank_below(keep);
-            if (EXT) store_shadow_packed(wb, j, r, p, ps);
-            else store_entry(out, j, r, p, ps);
+            if (EXT) store_shadow_packed<A32>(wk, j, r, p, ps);
+            else store_entry<A32>(wk.ext, j, r, p, ps);
         }
     }
 #if PT_PHASE_STATS
@@ -940,7 +1000,11 @@ __device__ __forceinline__ void bf_step_batch(const SceneView& sc, const Tri* gt
 // (bf_replay_stackless NARROW), launched by the host for scenes with SceneView::bfnarrow.  The width
 // rides in GEN so that the kernel keeps its five template arguments (profile tools read them by
 // position).
+// GEN | 8 (kStepAddr64): the instance that addresses the queues with 64-bit indices, launched for a
+// part whose arrays pass 4 GiB (step_addr32_ok false; option step_addr64 forces it: tests); the
+// instances without it use 32-bit byte offsets (q_at).  The same body, the same bits.
 constexpr int kStepNarrow = 4;
+constexpr int kStepAddr64 = 8;
 template <bool EXT, bool LDS, bool FAST_RCP, bool COUNT, int GENW = 0>
 __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_wf_step_bf(SceneView sc, FrameParams fp, WfBuffers wb, int it,
                                                            Counters* cnt_out, int nslots, uint32_t frame0,
@@ -948,6 +1012,7 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(8, 
                                                            uint32_t q) {
     constexpr int GEN = GENW & 3;
     constexpr bool NARROW = (GENW & kStepNarrow) != 0;
+    constexpr bool A32 = (GENW & kStepAddr64) == 0;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const BfLds l = bf_lds(smem, sc);
     const uint32_t nwaves = gridDim.x * (blockDim.x / 64);
@@ -985,7 +1050,7 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(8, 
     PhaseAcc pa{};
 #endif
     for (uint32_t b = g; b < nb; b += G)  // this region's batches, interleaved over its waves
-        bf_step_batch<EXT, FAST_RCP, COUNT, GEN != 0, GEN == 1, NARROW>(sc, gtris, fp, wb, (size_t)rg * wb.rstride, b, count, l,
+        bf_step_batch<EXT, FAST_RCP, COUNT, GEN != 0, GEN == 1, NARROW, A32>(sc, gtris, fp, wb, (size_t)rg * wb.rstride, b, count, l,
                                                                 nslots, c, [&](uint32_t n) { return atomicAdd(out_count, n); },
                                                                 ga, b < nqb ? (int64_t)-1 : (int64_t)(k0 + b - nqb) PH_PASS);
     if (COUNT) flush_counters(c, cnt_out);
@@ -1246,6 +1311,8 @@ static WfBuffers wb_part(const WfBuffers& wb, int h, int nparts, size_t rad_off)
 
 static std::atomic<int> g_bf_width{0};
 int last_bf_width() { return g_bf_width.load(); }
+static std::atomic<int> g_step_addr{0};
+int last_step_addr() { return g_step_addr.load(); }
 
 // The brute-force kernels without counters replay without a stack when the scene has the BfNode
 // tree (bf_replay_stackless): no per-lane stack in their LDS (CornellBox: 14 KB of a 512-thread
@@ -1393,21 +1460,31 @@ static hipError_t wf_render_t(const SceneView& sc_in, const FrameParams& fp, con
             if constexpr (flv_fused(TRAV)) {  // trace + shade in one launch
 #define PT_STEP_(E, G) PT_LAUNCH(KID_WF_STEP, st, (k_wf_step_bf<E, LDS, flv_fast(TRAV), COUNT, G>), dim3(tblocks), dim3(kTraceBlock), \
                                  lds, st, sc, fp, w, it, cnt, bf_slots, frame0, stride, pv[h].fbase, pv[h].P, !accum, regen_q)
+#define PT_STEP_A(E, G)                                   \
+    do {                                                  \
+        if (addr32) PT_STEP_(E, G);                       \
+        else PT_STEP_(E, (G) | kStepAddr64);              \
+    } while (0)
 #define PT_STEP(E, G)                                                    \
     do {                                                                 \
         bool narrow_ = false;                                            \
         if constexpr (kNarrowOk && (G) != 2) narrow_ = narrow;           \
         if constexpr (kNarrowOk && (G) != 2) {                           \
-            if (narrow_) PT_STEP_(E, (G) | kStepNarrow);                 \
+            if (narrow_) PT_STEP_A(E, (G) | kStepNarrow);                \
         }                                                                \
-        if (!narrow_) PT_STEP_(E, G);                                    \
+        if (!narrow_) PT_STEP_A(E, G);                                   \
         g_bf_width = narrow_ ? 32 : (!COUNT && sc.bfnode) ? 64 : 0;      \
+        g_step_addr = addr32 ? 32 : 64;                                  \
     } while (0)
+                // 32-bit queue offsets while the part's arrays allow them (pt_step_addr.h), else the
+                // 64-bit instance; option step_addr64 forces that one (tests)
+                const bool addr32 = !lo.step_addr64 && step_addr32_ok(w.qcap, pv[h].P);
                 if (regen_q > 0 && (it & 1) == 0 && (uint32_t)(it / 2) * regen_q < regen_cam) PT_STEP(true, 2);
                 else if (fgen && it == 0) PT_STEP(true, 1);
                 else if ((it & 1) == 0) PT_STEP(true, 0);
                 else PT_STEP(false, 0);
 #undef PT_STEP
+#undef PT_STEP_A
 #undef PT_STEP_
                 return hipSuccess;
             } else if constexpr (flv_brute_force(TRAV)) {

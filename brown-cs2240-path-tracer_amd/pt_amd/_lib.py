@@ -15,10 +15,10 @@ _CSRC = os.path.join(_PKG_ROOT, "csrc")
 _BUILD_SRCS = ["pt_kernels.hip", "pt_wavefront.hip", "pt_leafpass.hip", "pt_image.hip", "pt_features.hip", "pt_denoise.hip", "pt_query.hip", "pt_capi.hip", "pt_math.h", "pt_flavour.h", "pt_layout.h",
                "pt_device.h", "pt_path.h", "pt_kernels.h", "../../include/pt_hip.h", "pt_bvh.cpp", "pt_leafbvh.h",
                "pt_leafbvh.cpp", "pt_leafskip.cpp", "pt_scene_layout.h", "pt_scene_layout.cpp", "pt_rect_plan.h",
-               "pt_rect_plan.cpp", "pt_query_plan.h", "Makefile"]
+               "pt_rect_plan.cpp", "pt_query_plan.h", "pt_step_addr.h", "Makefile"]
 MODE_AUTO, MODE_MEGAKERNEL, MODE_WAVEFRONT = 0, 1, 2
 MATH_FNS = ["sin", "cos", "tan", "acos", "log2", "exp2", "pow", "sqrt", "div", "hash1u", "hash1", "hash2x",
-            "hash2y", "min", "max"]
+            "hash2y", "min", "max", "ray_inv"]
 
 _STATUS = {0: "PT_OK", -1: "PT_ERR_INVALID", -2: "PT_ERR_SCENE", -3: "PT_ERR_NOMEM", -4: "PT_ERR_HIP",
            -5: "PT_ERR_NODEVICE"}
@@ -391,6 +391,15 @@ def last_bf_width() -> int:
     this process — 32 (the narrow instance: scenes of <= 32 entries and nodes, option bf_narrow), 64,
     or 0 (none yet, the counting instances, the stack walk)."""
     f = load_library().pt_last_bf_width
+    f.restype = ctypes.c_int
+    return int(f())
+
+
+def last_step_addr() -> int:
+    """pt_last_step_addr: offset width of the queue addressing in the fused step kernel launched last in
+    this process — 32 (the default while a part's queue arrays stay below 4 GiB), 64 (larger parts,
+    option step_addr64), or 0 (none yet)."""
+    f = load_library().pt_last_step_addr
     f.restype = ctypes.c_int
     return int(f())
 

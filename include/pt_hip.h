@@ -418,6 +418,8 @@ int pt_set_hw_queues(int n);
  *   "bf_narrow"     0 | 1               (default 1: scenes of <= 32 distinct entries and <= 32 internal
  *                                        nodes run the fused kernel's 32-bit instance — narrow sets and
  *                                        the replay's subtree pruning; 0 keeps the 64-bit one: tests)
+ *   "step_addr64"   0 | 1               (default 0; 1: the fused kernel addresses its queues with 64-bit
+ *                                        indices whatever the part's size, as parts beyond 4 GiB do: tests)
  *   "mb_uid_order"  forward | reverse   (read by pt_scene_create: uid numbering of mailbox scenes)
  *   "leaf_bvh"      integer             (read by pt_scene_create: leaves with a leaf BVH, >= this many entries)
  *   "pool_run"      2 | 4               (entries per run of the pooled leaf turns; default per scene)
@@ -443,6 +445,9 @@ void pt_reset_options(void);
 /* Which instance of the fused step kernel this process launched last: 32 (option bf_narrow), 64, or
  * 0 (none yet, a counting instance, or the stack walk of bf_stackless=0).  For tests. */
 int pt_last_bf_width(void);
+/* How that launch addressed its queues: 32 (byte offsets of 32 bits: the default while a part's queue
+ * arrays stay below 4 GiB), 64 (larger parts, or option step_addr64), or 0 (none yet).  For tests. */
+int pt_last_step_addr(void);
 
 /* Destroys the RCCL communicators pt_render_multi made (they are cached per device list; the
  * library also destroys them when the process exits).  Not concurrent with pt_render_multi. */
@@ -545,7 +550,8 @@ int pt_profile_read(pt_scene* scene, pt_kernel_time* out, int max_entries, int* 
 /* Numerics self-test: out[i] = f(a[i], b[i]) evaluated ON THE DEVICE with the core's
  * pinned f32 math (fn ids: 0 sin, 1 cos, 2 tan, 3 acos, 4 log2, 5 exp2, 6 pow, 7 sqrt,
  * 8 div, 9 hash1u, 10 hash1, 11 hash2.x, 12 hash2.y, 13 min, 14 max; hash inputs are the
- * bit patterns of a[i]). */
+ * bit patterns of a[i]).  15 ray_inv: a holds n / 3 triples (x, y, z) and out their 1 / x, 1 / y, 1 / z from
+ * the fused kernel's ray_inv, triple i on thread i — a wave votes on 64 consecutive triples (b unused). */
 int pt_selftest_math(int device, int fn, const float* a, const float* b, float* out, size_t n);
 
 /* Exhaustive self-test of the core's division-free reciprocal (pt_math.h rcp_rn, used by the
