@@ -6,7 +6,11 @@
 //   C=brown-cs2240-path-tracer_amd/csrc
 //   hipcc -x hip --offload-arch=gfx950 -O2 -std=c++17 -ffp-contract=off -I $C scripts/scene_layout_harness.cpp \
 //       $C/pt_scene_layout.cpp $C/pt_leafbvh.cpp $C/pt_leafskip.cpp -o harness
-//   ./harness triangle_data.f32 bvh_data.f32 [uid_reverse] [leaf_bvh=N] [leaf_skip=0]
+//   ./harness triangle_data.f32 bvh_data.f32 [uid_reverse] [leaf_bvh=N] [leaf_skip=0] [dump_bf]
+// dump_bf: after the lines above, the stackless replay tree word by word ("bf i node lm rm" per BfNode in
+// visiting order, "bn i lm rm" per narrow one), then the tables those words are made from: "nd i lref rref
+// lcnt rcnt" per HostLayout node (a child's node or first record, its entry count or -1 for a node) and
+// "uid r u" per record, for tests/test_tree_cpu.py.
 // Sanitizer run of every case of the test (host code, on a machine without a GPU): the same line with
 //   -g -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined
 #include <cinttypes>
@@ -38,12 +42,14 @@ static void row(const char* name, const std::vector<T>& v) {
 }
 
 int main(int argc, char** argv) {
-    if (argc < 3) { std::fprintf(stderr, "usage: %s triangle_data.f32 bvh_data.f32 [uid_reverse] [leaf_bvh=N] [leaf_skip=0]\n", argv[0]); return 2; }
+    if (argc < 3) { std::fprintf(stderr, "usage: %s triangle_data.f32 bvh_data.f32 [uid_reverse] [leaf_bvh=N] [leaf_skip=0] [dump_bf]\n", argv[0]); return 2; }
     pt::LayoutOptions opt;
+    bool dump_bf = false;
     for (int a = 3; a < argc; ++a) {
         if (!std::strcmp(argv[a], "uid_reverse")) opt.uid_reverse = true;
         else if (!std::strncmp(argv[a], "leaf_bvh=", 9)) opt.leaf_bvh = std::atol(argv[a] + 9);
         else if (!std::strcmp(argv[a], "leaf_skip=0")) opt.leaf_skip = false;
+        else if (!std::strcmp(argv[a], "dump_bf")) dump_bf = true;
         else { std::fprintf(stderr, "unknown argument %s\n", argv[a]); return 2; }
     }
     const std::vector<float> tri = read_f32(argv[1]), bvh = read_f32(argv[2]);
@@ -68,5 +74,14 @@ int main(int argc, char** argv) {
     std::printf("plan");
     for (int s = 0; s < pt::SEC_COUNT; ++s) std::printf(" %zu+%zu", p.sec[s].off, p.sec[s].bytes);
     std::printf("\nspan_end %zu off_counters %zu total %zu\n", p.span_end, p.off_counters, p.total);
+    if (dump_bf) {
+        for (size_t k = 0; k < L.bfnode.size(); ++k)
+            std::printf("bf %zu %d %016" PRIx64 " %016" PRIx64 "\n", k, L.bfmap[k], (uint64_t)L.bfnode[k].lm, (uint64_t)L.bfnode[k].rm);
+        for (size_t k = 0; k < L.bfnarrow.size(); ++k)
+            std::printf("bn %zu %016" PRIx64 " %016" PRIx64 "\n", k, (uint64_t)L.bfnarrow[k].lm, (uint64_t)L.bfnarrow[k].rm);
+        for (size_t k = 0; k < L.nodes.size(); ++k)
+            std::printf("nd %zu %d %d %d %d\n", k, L.nodes[k].lref, L.nodes[k].rref, L.nodes[k].lcnt, L.nodes[k].rcnt);
+        for (size_t k = 0; k < L.tris.size(); ++k) std::printf("uid %zu %d\n", k, L.tris[k].uid);
+    }
     return 0;
 }
