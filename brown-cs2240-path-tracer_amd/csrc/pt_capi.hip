@@ -1,40 +1,16 @@
-// pt_capi.hip — C ABI (include/pt_hip.h): options, scene upload, render entry points.
+// pt_capi.hip — C ABI (include/pt_hip.h): errors, options, the build id, kernel timing, devices and the
+// scene's life.  The other entry points: pt_capi_render.hip, _adaptive, _denoise, _query, _selftest, _multi.
 // Host code only; kernels live in pt_kernels.hip, the scene's re-encoding in pt_scene_layout.cpp.
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
 #include <algorithm>
-#include <array>
-#include <cstring>
-#include <map>
-#include <mutex>
-#include <string>
-#include <thread>
-#include <vector>
+#include <cstdio>
 
-#include <dlfcn.h>
-#include <rccl/rccl.h>  // types only: librccl is opened on first multi-device use (pt_render_multi)
-
-#include "../../include/pt_hip.h"
-#include "pt_kernels.h"
-#include "pt_scene_layout.h"
+#include "pt_capi_internal.h"
 
 using namespace pt;
 
 namespace {
 
 thread_local std::string g_err;
-
-int fail(int code, const std::string& msg) {
-    g_err = msg;
-    return code;
-}
-
-#define HIP_TRY(expr)                                                                                \
-    do {                                                                                            \
-        hipError_t e_ = (expr);                                                                      \
-        if (e_ != hipSuccess) return fail(PT_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
 
 // ---------------------------------------------------------------------------------------------
 // Options (pt_set_option): the process-wide table of kernel-selection switches.  Nothing is read
@@ -66,14 +42,27 @@ constexpr OptSpec kOptSpecs[] = {
     {"denoise_lds", OPT_ENUM, "0|1|2|3|4"},
     {"query_refill", OPT_BOOL, nullptr}, {"query_blocks", OPT_INT, nullptr},
 };
-constexpr int kNumOpts = (int)(sizeof(kOptSpecs) / sizeof(kOptSpecs[0]));
+static_assert(sizeof(kOptSpecs) / sizeof(kOptSpecs[0]) == kNumOpts, "pt_capi_internal.h kNumOpts");
+constexpr int count_choices(const char* c) {
+    int n = 1;
+    for (; *c; ++c) n += *c == '|';
+    return n;
+}
+// launch_opts takes a trav choice's position for its TravBase
+static_assert(kOptSpecs[1].name[0] == 't' && count_choices(kOptSpecs[1].choices) == TRAV_BASE_COUNT, "option trav");
 
 std::mutex g_opt_mu;
 std::string g_opt_val[kNumOpts];  // "" = default
 
-int opt_index(const char* name) {
-    for (int i = 0; i < kNumOpts; ++i)
-        if (!std::strcmp(name, kOptSpecs[i].name)) return i;
+int choice_index(const char* choices, const char* v) {
+    const size_t n = std::strlen(v);
+    int k = 0;
+    for (const char* c = choices; *c; ++k) {
+        const char* bar = std::strchr(c, '|');
+        const size_t len = bar ? (size_t)(bar - c) : std::strlen(c);
+        if (len == n && !std::strncmp(c, v, n)) return k;
+        c += len + (bar ? 1 : 0);
+    }
     return -1;
 }
 
@@ -85,29 +74,30 @@ bool opt_valid(const OptSpec& s, const char* v) {
         const long long x = std::strtoll(v, &end, 10);
         return *end == 0 && x >= 0 && x <= 0x7fffffffLL;
     }
-    const size_t n = std::strlen(v);
-    for (const char* c = s.choices; *c;) {
-        const char* bar = std::strchr(c, '|');
-        const size_t len = bar ? (size_t)(bar - c) : std::strlen(c);
-        if (len == n && !std::strncmp(c, v, n)) return true;
-        c += len + (bar ? 1 : 0);
-    }
-    return false;
+    return choice_index(s.choices, v) >= 0;
 }
 
-// Snapshot of the table, taken once per call (a concurrent pt_set_option affects later calls only).
-struct Opts {
-    std::string v[kNumOpts];
-    const std::string& get(const char* name) const {
-        static const std::string empty;
-        const int i = opt_index(name);
-        return i >= 0 ? v[i] : empty;
-    }
-    bool has(const char* name) const { return !get(name).empty(); }
-    long num(const char* name, long def) const { return has(name) ? std::atol(get(name).c_str()) : def; }
-    int flag(const char* name, int def) const { return has(name) ? (get(name) == "1" ? 1 : 0) : def; }
-    bool is(const char* name, const char* val) const { return get(name) == val; }
-};
+// Set once any call of this library has touched the HIP runtime (pt_set_hw_queues is then too late).
+bool g_hip_touched = false;
+
+}  // namespace
+
+namespace pt {
+
+int fail(int code, const std::string& msg) {
+    g_err = msg;
+    return code;
+}
+
+int opt_index(const char* name) {
+    for (int i = 0; i < kNumOpts; ++i)
+        if (!std::strcmp(name, kOptSpecs[i].name)) return i;
+    return -1;
+}
+int opt_choice(const char* name, const char* value) {
+    const int i = opt_index(name);
+    return i >= 0 && kOptSpecs[i].kind == OPT_ENUM ? choice_index(kOptSpecs[i].choices, value) : -1;
+}
 Opts opts_snapshot() {
     std::lock_guard<std::mutex> lk(g_opt_mu);
     Opts o;
@@ -115,14 +105,7 @@ Opts opts_snapshot() {
     return o;
 }
 
-// the probe of the pre-resolvable leaves (probe_pre_leaves): a 32 x 32 raster (<= 4 Ki queries), at
-// most 2^23 triangle tests (MedievalBoat: ~4 k per query, ~30 ms)
-constexpr int kPreProbeGrid = 32;
-constexpr uint64_t kPreProbeTests = 1ull << 23;
-
-size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-}  // namespace
+}  // namespace pt
 
 extern "C" {
 
@@ -159,84 +142,6 @@ const char* pt_build_id(void) { return PT_SOURCE_HASH; }
 
 }  // extern "C"
 
-// A device scratch buffer kept with the scene and grown on demand (cap: T's)
-template <class T>
-struct Scratch {
-    T* p = nullptr;
-    size_t cap = 0;
-    int ensure(size_t n, const char* what) {
-        if (cap >= n) return PT_OK;
-        free();
-        if (hipMalloc(reinterpret_cast<void**>(&p), n * sizeof(T)) != hipSuccess) return fail(PT_ERR_NOMEM, std::string("hipMalloc ") + what);
-        cap = n;
-        return PT_OK;
-    }
-    void free() { if (p) hipFree(p); p = nullptr; cap = 0; }
-};
-
-struct pt_scene {
-    int device = 0;
-    void* d_mem = nullptr;
-    SceneView view{};
-    pt_scene_info info{};
-    hipStream_t stream = nullptr;
-    Scratch<float> d_accum;  // scratch for the blocking host-buffer calls
-    Counters* d_counters = nullptr;
-    void* d_wf = nullptr;  // wavefront path state, allocated on first use
-    WfBuffers wf{};
-    bool prof_on = false;  // pt_profile_enable
-    KernelProfiler prof;
-    Scratch<uint8_t> d_rgba;  // pt_render_image scratch
-    // scratch of the blocking moments, noise and adaptive calls: second moments, per-tile mean (floats),
-    // tile verdicts followed by tile frame counts (bytes)
-    Scratch<float> d_m2, d_mean;
-    Scratch<char> d_tiles;
-    // a rectangle-list render's table (pt_render_rects): the rows, then the megakernel's blocks; written
-    // on the call's stream before its first launch, so calls in stream order may share it
-    Scratch<char> d_rects;
-    // the denoiser's four w * h float4 planes (pt_denoise_async: two ping-pong (c, var), (N, Z), (A, 0);
-    // counted in info.device_bytes while held), and the scratch of its blocking calls: the guide buffers
-    // (geo, then alb) and the filtered variance
-    Scratch<float4> d_dn;
-    Scratch<float> d_feat, d_var;
-    // ray queries (pt_query_*): the blocking calls' rays and results (counted in info.device_bytes while
-    // held), the kernels' control words (kQueryCtlWords: a wave that gave up sets the first) and their
-    // pinned mirror, copied after every query launch on its stream like h_ctl below
-    Scratch<char> d_query;
-    uint32_t* d_qctl = nullptr;
-    uint32_t* h_qctl = nullptr;
-    WfStreams ws;  // dual-stream wavefront: aux stream + fork/join events (created with d_wf)
-    // pinned mirror of the wavefront control words, copied after every wavefront render on its
-    // stream: a watchdog flag set by an asynchronous render surfaces once that copy has landed
-    // (next call, pt_scene_check) without a synchronisation of its own
-    uint32_t* h_ctl = nullptr;
-    float* d_rad = nullptr;  // radiance of finished wavefront paths (ensure_rad)
-    uint64_t rad_cap = 0;
-    Scratch<float> d_peer;  // pt_render_multi (ordered reduction): another device's partial accumulator
-    int32_t leaf_min = 0;  // leaf BVHs: leaves of at least this many entries have one (0: none)
-    std::vector<std::array<int32_t, 3>> lleaves;  // (first record, entries, nodes) per leaf BVH
-    // big leaves resolved before the traversal (k_wf_leafpass): the table (device copy in d_mem at
-    // d_pre), every leaf's size (largest first), and the result keys (ensure_pres)
-    std::vector<PreLeaf> pre;
-    // shape_view's choice of the leaf pass: per leaf of pre, probe queries passing its box filter and
-    // visiting it (probe_pre_leaves, once, with the camera of the scene's first render that could
-    // use the pass), from host copies of the tree, records and lights kept for it
-    std::vector<std::array<uint32_t, 2>> pre_probe;
-    bool pre_probed = false;
-    ProbeCamera pre_cam{};  // the camera pre_probe was taken with (a render with another probes again)
-    std::mutex pre_mu;
-    std::vector<Node> h_nodes;
-    std::vector<Tri> h_tris;
-    std::vector<Light> h_lights;
-    std::vector<int32_t> leaf_sizes;
-    const PreLeaf* d_pre = nullptr;
-    uint64_t* d_pres = nullptr;
-    size_t pres_cap = 0;  // keys
-};
-
-// Set once any call of this library has touched the HIP runtime (pt_set_hw_queues is then too late).
-static bool g_hip_touched = false;
-
 namespace pt {
 thread_local KernelProfiler* t_prof = nullptr;
 
@@ -272,19 +177,9 @@ void KernelProfiler::destroy() {
 }
 }  // namespace pt
 
-namespace {
-struct ProfScope {  // attach the scene's profiler to this thread for the launches of its scope
-    explicit ProfScope(pt_scene* s) { t_prof = s->prof_on ? &s->prof : nullptr; }
-    ~ProfScope() { t_prof = nullptr; }
-};
-}  // namespace
-
 extern "C" {
 
 int pt_abi_version(void) { return PT_ABI_VERSION; }
-
-int pt_last_bf_width(void) { return pt::last_bf_width(); }
-int pt_last_step_addr(void) { return pt::last_step_addr(); }
 
 int pt_profile_enable(pt_scene* s, int enable) {
     if (!s) return fail(PT_ERR_INVALID, "null scene");
@@ -392,8 +287,8 @@ int pt_scene_create(const float* triangle_data, size_t triangle_len, const float
     const ScenePlan plan = plan_sections(L, sizeof(Counters));
     pt_scene* s = new pt_scene();
     s->device = device;
-    if (hipMalloc(&s->d_mem, plan.total) != hipSuccess) { delete s; return fail(PT_ERR_NOMEM, "hipMalloc scene"); }
-    char* base = static_cast<char*>(s->d_mem);
+    if (const int rc2 = s->d_mem.ensure(plan.total, "scene"); rc2 != PT_OK) { delete s; return rc2; }
+    char* base = s->d_mem.p;
     for (const auto& sec : plan.sec)
         if (sec.bytes && hipMemcpy(base + sec.off, sec.src, sec.bytes, hipMemcpyHostToDevice) != hipSuccess) {
             pt_scene_destroy(s);
@@ -459,22 +354,13 @@ void pt_scene_destroy(pt_scene* s) {
     if (!s) return;
     hipSetDevice(s->device);
     if (s->stream) { hipStreamSynchronize(s->stream); hipStreamDestroy(s->stream); }
-    if (s->d_wf) hipFree(s->d_wf);
     for (int h = 0; h < kMaxParts; ++h) {
         if (s->ws.aux[h]) { hipStreamSynchronize(s->ws.aux[h]); hipStreamDestroy(s->ws.aux[h]); }
         if (s->ws.join[h]) hipEventDestroy(s->ws.join[h]);
     }
     if (s->ws.fork) hipEventDestroy(s->ws.fork);
-    if (s->d_rad) hipFree(s->d_rad);
-    if (s->d_pres) hipFree(s->d_pres);
-    s->d_accum.free(); s->d_m2.free(); s->d_mean.free(); s->d_peer.free(); s->d_rgba.free(); s->d_tiles.free(); s->d_rects.free();
-    s->d_dn.free(); s->d_feat.free(); s->d_var.free(); s->d_query.free();
-    if (s->d_qctl) hipFree(s->d_qctl);
-    if (s->h_qctl) hipHostFree(s->h_qctl);
-    if (s->h_ctl) hipHostFree(s->h_ctl);
-    if (s->d_mem) hipFree(s->d_mem);
     s->prof.destroy();
-    delete s;
+    delete s;  // the buffers free themselves, on the device set above
 }
 
 int pt_scene_set_vertex_normals(pt_scene* s, int enable) {
@@ -489,530 +375,6 @@ int pt_scene_get_info(const pt_scene* s, pt_scene_info* out) {
     return PT_OK;
 }
 
-}  // extern "C"
-
-namespace {
-
-// meta (program-raymarch.ts:79-92) -> FrameParams.  view_half_h uses the pinned tan
-// (program-raymarch.wgsl:62); it is uniform, so it is evaluated once here.
-// win: the window of the image the call renders (NULL: the whole image); row_pitch: pixels between
-// rows of its destination (NULL: the window's width, a dense [h][w][3] buffer).
-int make_params(const float* meta, int max_depth, FrameParams& fp, const pt_window* win = nullptr,
-                const size_t* pitch = nullptr) {
-    if (!meta) return fail(PT_ERR_INVALID, "meta is NULL");
-    const float W = meta[0], H = meta[1];
-    if (!(W >= 1.0f && H >= 1.0f && W <= 32768.0f && H <= 32768.0f) || W != std::floor(W) || H != std::floor(H))
-        return fail(PT_ERR_INVALID, "meta[0..1] must be integral resolutions in [1, 32768]");
-    if (max_depth < -1 || max_depth > 1024) return fail(PT_ERR_INVALID, "max_depth out of range");
-    std::memset(&fp, 0, sizeof fp);
-    fp.W = W; fp.H = H;
-    fp.inv_w = meta[8]; fp.inv_h = meta[9];
-    fp.aspect = meta[10];
-    fp.focal = meta[2];
-    fp.view_half_h = (2.0f * meta[2]) * tan_p(meta[3] * 0.5f);
-    fp.rr_prob = meta[45];
-    for (int i = 0; i < 4; ++i) fp.cam[i] = meta[4 + i];
-    for (int i = 0; i < 16; ++i) fp.M[i] = meta[28 + i];
-    fp.width = (uint32_t)W; fp.height = (uint32_t)H;
-    fp.direct_only = meta[46] > 0.0f ? 1 : 0;
-    fp.max_depth = max_depth < 0 ? 16 : max_depth;
-    const pt_window whole = {0, 0, fp.width, fp.height};
-    const pt_window& w = win ? *win : whole;
-    if (w.w < 1 || w.h < 1) return fail(PT_ERR_INVALID, "window: w and h must be at least 1");
-    if ((uint64_t)w.x0 + w.w > fp.width || (uint64_t)w.y0 + w.h > fp.height)
-        return fail(PT_ERR_INVALID, "window: x0 + w and y0 + h must lie within the image (meta[0..1])");
-    const size_t row_pitch = pitch ? *pitch : w.w;
-    if (row_pitch < w.w) return fail(PT_ERR_INVALID, "row_pitch is smaller than the window's width");
-    if (row_pitch > 0xffffffffull) return fail(PT_ERR_INVALID, "row_pitch out of range");
-    fp.win_x0 = w.x0; fp.win_y0 = w.y0; fp.win_w = w.w; fp.win_h = w.h;
-    fp.row_pitch = (uint32_t)row_pitch;
-    return PT_OK;
-}
-
-// PT_MODE_* -> pipeline.  A/B overrides (pt_set_option): kernel=literal|mega|wavefront, lds=0|1,
-// trav=nested|flat1|pred|lean|lean2|lean4|lean8|lean16|lean32, fastrcp=0|1, ...
-// AUTO picks the wavefront pipeline once a call has this many paths: below it the fixed
-// cost of its ~2(D+1) launches per batch outweighs its better SIMD utilisation.  Measured per
-// scene type (round 2, depth 16, ms megakernel / wavefront): mailbox scenes (the fused kernel)
-// gain at every size (CornellBox 128^2 x 1: 1.43 / 0.66), so do scenes with cooperative big
-// leaves (MedievalBoat 256^2 x 1: 62 / 35); other scenes from about 2^19 paths (Glossy 512^2 x 1:
-// 7.1 / 9.1, 512^2 x 2: 13.1 / 9.6).
-constexpr uint64_t kWfAutoMinPaths = 1ull << 19;
-// The call's pipeline: option kernel, else the mode, AUTO by the call's paths and the scene (view's
-// mailbox and big_leaf > 0)
-bool wants_wavefront(const Opts& o, int mode, uint64_t paths, const SceneView& view) {
-    if (o.is("kernel", "wavefront")) return true;
-    if (o.is("kernel", "mega") || o.is("kernel", "literal")) return false;
-    const uint64_t auto_min = (view.mailbox || view.big_leaf > 0) ? 1 : kWfAutoMinPaths;
-    return mode == PT_MODE_WAVEFRONT || (mode == PT_MODE_AUTO && paths >= auto_min);
-}
-
-// The call's LaunchOpts: pt_flavour.h's defaults, the pipeline, and whatever pt_set_option overrides
-LaunchOpts launch_opts(const Opts& o, int mode, uint64_t paths, const SceneView& view) {
-    LaunchOpts lo;
-    lo.wavefront = wants_wavefront(o, mode, paths, view);
-    lo.literal = o.is("kernel", "literal");
-    auto flag = [&](const char* name, bool def) { return o.flag(name, def ? 1 : 0) != 0; };
-    lo.lds = flag("lds", lo.lds);
-    lo.fuse_gen = flag("fuse_gen", lo.fuse_gen);
-    lo.dual = flag("dual", lo.dual);
-    lo.region_perm = flag("region_perm", lo.region_perm);
-    if (const long p = o.num("parts", 0); p > 0) lo.parts = (int)p;  // 0: the default
-    lo.sort = (int)o.num("sort", lo.sort);  // 1 / 8: direction octant; 64: + origin octant; 512: + 4^3 origin cells
-    lo.trace_sparse = (int)o.num("trace_sparse", lo.trace_sparse);
-    lo.regen = (int)std::max(0L, std::min(1L << 20, o.num("regen", lo.regen)));
-    lo.trace_ring = (int)o.num("trace_ring", lo.trace_ring);
-    lo.trace_blocks = (int)o.num("wf_trace_blocks", lo.trace_blocks);
-    lo.watchdog = (uint32_t)o.num("trace_watchdog", lo.watchdog);
-    lo.bf_slots = (int)o.num("bf_slots", lo.bf_slots);
-    lo.step_addr64 = flag("step_addr64", lo.step_addr64);
-    lo.leaf_blocks = (int)o.num("leaf_blocks", lo.leaf_blocks);
-    // | 4: the pair walk's second check of the open chunks with the entries' own normals (option
-    // leaf_refine, default on; pt_leafpass.hip)
-    lo.leaf_pairs = (int)std::max(0L, std::min(2L, o.num("leaf_pairs", 1))) | (flag("leaf_refine", true) ? 4 : 0);
-    int trav = -1;
-    static const char* const names[TRAV_BASE_COUNT] = {"nested", "flat1", "pred", "lean", "lean2", "lean4", "lean8", "lean16", "lean32"};
-    for (int k = 0; k < TRAV_BASE_COUNT; ++k)
-        if (o.is("trav", names[k])) trav = k;
-    lo.set_flavour_opts(trav, o.flag("fastrcp", -1), o.flag("mailbox", -1), o.flag("bf", -1), o.flag("fuse", -1));
-    return lo;
-}
-
-// paths in flight per wavefront batch (kWfBytesPerPath = 188 B of queue state per path: 64 M
-// paths ~ 12 GB of the 288 GB, plus the queue slack of the region layout).  Every batch ends in
-// launch tails that carry few paths at low occupancy (the last depths); a larger batch pays them
-// for more samples: CornellBox 1024^2 x 256 +6 % at 64 M over 8 M, CornellBox-Glossy +28 %
-// (probe of option wf_paths)
-constexpr uint64_t kWfTargetPaths = 64ull << 20;
-constexpr int kBigLeafDefault = 128;
-// option denoise_lds: how many of the denoiser's first passes stage their taps in LDS (0..4).  Measured at
-// 1024^2 (profiles/denoise_bench.jsonl): staged, the passes with steps 1 and 2 take 0.06 ms
-// against 0.10 and 0.09; the pass with step 4 is 4-13 % slower staged, the one with step 8 two thirds slower
-constexpr long kDenoiseLdsDefault = 2;
-constexpr long kPreRatioDefault = 50;  // shape_view: the leaf pass when >= 50 % of its work is visited
-
-int ensure_rad(pt_scene* s, uint64_t paths) {
-    if (s->d_rad && s->rad_cap >= paths) { s->wf.rad = s->d_rad; s->wf.rad_cap = s->rad_cap; return PT_OK; }
-    if (s->d_rad) { hipDeviceSynchronize(); hipFree(s->d_rad); s->d_rad = nullptr; s->rad_cap = 0; }
-    if (hipMalloc(&s->d_rad, 12 * paths) != hipSuccess) {
-        s->d_rad = nullptr;
-        (void)hipGetLastError();
-        return fail(PT_ERR_NOMEM, "hipMalloc wavefront radiance");
-    }
-    s->rad_cap = paths;
-    s->wf.rad = s->d_rad;
-    s->wf.rad_cap = paths;
-    return PT_OK;
-}
-
-// keys of the pre-resolved big leaves: npre per queue entry of the wavefront buffers
-int ensure_pres(pt_scene* s, int npre) {
-    const size_t need = (size_t)npre * s->wf.qcap;
-    if (s->d_pres && s->pres_cap >= need) { s->wf.pres = s->d_pres; s->wf.pres_stride = s->wf.qcap; return PT_OK; }
-    if (s->d_pres) { hipDeviceSynchronize(); hipFree(s->d_pres); s->d_pres = nullptr; s->pres_cap = 0; }
-    if (hipMalloc(&s->d_pres, need * sizeof(uint64_t)) != hipSuccess) {
-        s->d_pres = nullptr;
-        (void)hipGetLastError();
-        return fail(PT_ERR_NOMEM, "hipMalloc pre-resolved leaf keys");
-    }
-    s->pres_cap = need;
-    s->wf.pres = s->d_pres;
-    s->wf.pres_stride = s->wf.qcap;
-    return PT_OK;
-}
-
-int ensure_wavefront(pt_scene* s, uint64_t paths) {
-    if (s->d_wf && s->wf.capacity >= paths) return PT_OK;
-    if (paths > 0x7fffffffull) return fail(PT_ERR_INVALID, "image too large for one wavefront batch");
-    if (s->d_wf) { hipDeviceSynchronize(); hipFree(s->d_wf); s->d_wf = nullptr; s->wf.capacity = 0; }
-    const size_t n = paths;
-    // queue arrays carry slack so that each part can be cut into up to kRegions regions of a whole
-    // number of 64-entry batches holding all its paths (k_wf_step_bf)
-    const size_t qn = n + 2 * (size_t)kQueueSlackRegions * 64;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
-    size_t oq[6];
-    for (int k = 0; k < 6; ++k) oq[k] = take((k % 3 == 0 ? 32 : 16) * qn);
-    const size_t o_p0 = take(16 * qn), o_p1 = take(16 * qn), o_p2 = take(8 * qn), o_hit = take(8 * qn),
-                 o_ctl = take(4 * kMaxParts * WF_CTL_WORDS), o_rcnt = take(4 * kMaxParts * 3 * kRegions),
-                 o_cam = take(2 * 64 * sizeof(float4));
-    if (hipMalloc(&s->d_wf, off) != hipSuccess) {
-        s->d_wf = nullptr;
-        (void)hipGetLastError();  // the failed allocation is reported here, not by a later call
-        return fail(PT_ERR_NOMEM, "hipMalloc wavefront state");
-    }
-    char* b = static_cast<char*>(s->d_wf);
-    auto f4 = [&](size_t o) { return reinterpret_cast<float4*>(b + o); };
-    WfBuffers& w = s->wf;
-    w.ext = WfQueue{f4(oq[0]), f4(oq[1]), f4(oq[2])};
-    w.shd = WfQueue{f4(oq[3]), f4(oq[4]), f4(oq[5])};
-    w.sp0 = f4(o_p0); w.sp1 = f4(o_p1);
-    w.sp2 = reinterpret_cast<float2*>(b + o_p2);
-    w.hitq = reinterpret_cast<int2*>(b + o_hit);
-    w.ctl = reinterpret_cast<uint32_t*>(b + o_ctl);
-    w.rcnt = reinterpret_cast<uint32_t*>(b + o_rcnt);
-    w.camtab = f4(o_cam);
-    if (hipMemset(w.ctl, 0, 4 * kMaxParts * WF_CTL_WORDS) != hipSuccess ||
-        hipMemset(w.rcnt, 0, 4 * kMaxParts * 3 * kRegions) != hipSuccess)
-        return fail(PT_ERR_HIP, "hipMemset wavefront control words");
-    if (!s->ws.aux[0]) {
-        bool ok = hipEventCreateWithFlags(&s->ws.fork, hipEventDisableTiming) == hipSuccess;
-        for (int h = 0; h < kMaxParts && ok; ++h)
-            ok = hipStreamCreateWithFlags(&s->ws.aux[h], hipStreamNonBlocking) == hipSuccess &&
-                 hipEventCreateWithFlags(&s->ws.join[h], hipEventDisableTiming) == hipSuccess;
-        if (!ok) return fail(PT_ERR_HIP, "creating the wavefront's streams");
-    }
-    if (!s->h_ctl) {
-        if (hipHostMalloc(reinterpret_cast<void**>(&s->h_ctl), 4 * kMaxParts * WF_CTL_WORDS) != hipSuccess) {
-            s->h_ctl = nullptr;
-            return fail(PT_ERR_NOMEM, "hipHostMalloc wavefront control mirror");
-        }
-        std::memset(s->h_ctl, 0, 4 * kMaxParts * WF_CTL_WORDS);
-    }
-    w.capacity = (uint32_t)n;
-    w.qcap = (uint32_t)qn;
-    w.rq = w.rqi = 1;
-    w.rad = s->d_rad;
-    w.rad_cap = s->rad_cap;
-    return PT_OK;
-}
-
-// A trace wave that hit its watchdog (k_wf_trace: kTraceWatchdog iterations or
-// kTraceWatchdogTicks) sets ctl[WF_WATCHDOG] and leaves its state in ctl[WF_SNAP..]; later
-// launches of the scene skip their work.  The pinned mirror h_ctl receives the control words
-// after every wavefront render on its stream; once that copy has landed (the caller synchronised,
-// or the blocking calls' own synchronisation) the flag is reported here — by whichever call of
-// the scene comes next, megakernel or wavefront — and cleared.  The failure path waits for the
-// device first, so no mirror copy still in flight can bring the flag back after the clear and
-// report the same failure twice.
-// The same for a query wave (pt_query.hip k_query): the flag is the first of the scene's query control
-// words, mirrored in h_qctl after every query launch.
-int take_query_watchdog(pt_scene* s) {
-    if (!s->h_qctl || !__atomic_load_n(&s->h_qctl[0], __ATOMIC_ACQUIRE)) return PT_OK;
-    HIP_TRY(hipDeviceSynchronize());  // every pending mirror copy of the scene has landed
-    uint32_t v[kQueryCtlWords];
-    std::memcpy(v, s->h_qctl, sizeof v);
-    HIP_TRY(hipMemset(s->d_qctl, 0, sizeof v));
-    std::memset(s->h_qctl, 0, sizeof v);
-    char msg[256];
-    std::snprintf(msg, sizeof(msg),
-                  "ray query gave up after its watchdog limit (results invalid); first wave: n=%u nwaves=%u w=%u "
-                  "fetched=%u base=%u wv=%u cur=%u in_flight=%u",
-                  v[2], v[3], v[4], v[5], v[6], v[7], v[8], v[9]);
-    return fail(PT_ERR_HIP, msg);
-}
-
-int take_watchdog(pt_scene* s) {
-    if (const int rc = take_query_watchdog(s); rc != PT_OK) return rc;
-    if (!s->h_ctl) return PT_OK;
-    int h = 0;
-    while (h < kMaxParts && !__atomic_load_n(&s->h_ctl[h * WF_CTL_WORDS + WF_WATCHDOG], __ATOMIC_ACQUIRE)) ++h;
-    if (h == kMaxParts) return PT_OK;
-    HIP_TRY(hipDeviceSynchronize());  // every pending mirror copy of the scene has landed
-    uint32_t v[WF_SNAP_WORDS];
-    std::memcpy(v, s->h_ctl + h * WF_CTL_WORDS + WF_SNAP, sizeof v);
-    for (int k = 0; k < kMaxParts; ++k)
-        HIP_TRY(hipMemset(s->wf.ctl + k * WF_CTL_WORDS + WF_WATCHDOG, 0,
-                          (WF_SNAP + WF_SNAP_WORDS - WF_WATCHDOG) * sizeof(uint32_t)));
-    std::memset(s->h_ctl, 0, 4 * kMaxParts * WF_CTL_WORDS);
-    char msg[360];
-    std::snprintf(msg, sizeof(msg),
-                  "wavefront trace gave up after its watchdog limit (result invalid); first wave: count=%u "
-                  "nwaves=%u w=%u jl=%u wv=%u nv=%u cur=%u flushed=%u in_flight=%u mask=%08x%08x queue=%u",
-                  v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], v[8], v[10], v[9], v[11]);
-    return fail(PT_ERR_HIP, msg);
-}
-
-// The scene as this call's kernels see it: the scene's view with the per-call choices applied — the
-// big-leaf threshold, leaf chunks, the pooled runs' length, leaf remainders, and whether the big
-// leaves are resolved before the traversal (for the camera of fp).  paths: the call's, for AUTO's
-// choice of pipeline.
-int shape_view(pt_scene* s, const Opts& o, const FrameParams& fp, int mode, uint64_t paths, SceneView& view) {
-    view = s->view;
-    if (o.has("node_bias")) view.node_bias = std::max(1L, o.num("node_bias", 1));  // A/B runs
-    if (o.has("node_steps")) view.node_steps = (int32_t)std::max(1L, std::min(8L, o.num("node_steps", 1)));
-    // big leaves (lean traversal): a ray reaching a leaf of >= big_leaf entries has it tested by the
-    // whole wave (pt_device.h big_turn); default 128 (MedievalBoat 2.3x, in-process A/B; 64 is 1.5 %
-    // faster there but 12 % slower on the 1M-triangle synthetic scene, whose many 64..127-entry
-    // leaves waste half a cooperative step each); option big_leaf=n sets it, 0 turns big-leaf
-    // turns and leaf chunks off
-    {
-        const long big = o.num("big_leaf", kBigLeafDefault);
-        view.big_leaf = (big > 0 && s->info.max_leaf >= (uint32_t)big) ? (int32_t)big : 0;
-        // leaf BVHs (built at pt_scene_create, option leaf_bvh): lanes park at every leaf that has
-        // chunks and test them chunk by chunk (chunk_turn_multi); option leaf_walk=0 keeps them out (A/B)
-        if (big > 0 && s->leaf_min > 0 && o.flag("leaf_walk", 1) != 0)
-            view.big_leaf = view.big_leaf > 0 ? std::min<int32_t>(view.big_leaf, s->leaf_min) : s->leaf_min;
-        else
-            view.lnodes = nullptr;
-    }
-    // pooled leaf turns (pt_device.h lean_leaf_pool) on every tree (option leaf_pool=0: each lane
-    // walks its own pairs).  The run length: 2 on trees of short leaves (< 16 entries: the SAH
-    // builder's; Glossy +2.9 %, the boat +16.5 %, 100k +26 %, 1M +29 % over unpooled:
-    // profiles/r04am_sah_pool.log — runs of 4 there cost Glossy 3.6 %, r04t_configs.jsonl) and
-    // where the leaves reference >= 32 Ki triangles and no leaf is big (100k +12 %, 1M +26 % against
-    // runs of 4: r04aa_ab_run.log; 12.5k +3.7 % with node bias 1-2: r04ak_run2_bias.log), else 4
-    // (Glossy 5 Ki references, 1k, and the boat — 52 Ki references, but big leaves walked in
-    // chunks — are 1-2 % faster with 4); option pool_run=2|4.  Round 6, with four node steps per node
-    // turn: runs of 2 on every tree without big leaves (Glossy +5 %, 1k +2.2 %, 12.5k +0.8 % over 4;
-    // the boat, whose big leaves go to the leaf pass, -0.7 %: profiles/r06ac_ab_*.log)
-    {
-        const bool pool = o.flag("leaf_pool", 1) != 0;
-        const bool run2 = s->info.max_leaf < 16 || view.big_leaf == 0;
-        const long run = o.num("pool_run", run2 ? 2 : 4);
-        view.leaf_pool = pool ? (int32_t)run : 0;
-    }
-    // leaf remainders (pt_device.h lean_node_unit): option leaf_skip=0 keeps them out (A/B); a big-leaf
-    // threshold below kLeafSkipMaxLeaf too (a leaf the cooperative turns or the leaf pass take by its
-    // first record must keep it)
-    if (o.flag("leaf_skip", 1) == 0 || (view.big_leaf > 0 && view.big_leaf < kLeafSkipMaxLeaf)) view.nalt = nullptr;
-    // the brute-force replay walks the BfNode tree without a stack (bf_stackless=0: the stack walk; A/B)
-    if (o.flag("bf_stackless", 1) == 0) view.bfnode = nullptr;
-    // ... and its 32-bit instance where the scene has the narrow payload (bf_narrow=0: the 64-bit one; tests)
-    if (o.flag("bf_narrow", 1) == 0 || !view.bfnode) view.bfnarrow = nullptr;
-    // big leaves resolved before the traversal (k_wf_leafpass, pt_leafpass.hip; option leaf_pre=0:
-    // the cooperative turns and chunk walks inside k_wf_trace): the leaves of >= big_leaf entries, at
-    // most kMaxPre of them — with more, the threshold rises above the (kMaxPre + 1)-th largest and
-    // the rest are ordinary leaves of the pooled turns
-    // The leaf pass resolves a leaf for every ray that passes its box filter; the traversal tests it
-    // only for the rays that reach it, and a ray whose closest hit so far is nearer than a box on the
-    // leaf's path never does.  Where the filter over-predicts — the boat of CornellBox2's all-meshes
-    // scene sits inside the box's walls: 0.33 of the filtered leaf work is visited, 65 against 91.6
-    // Msamples/s without the pass (profiles/r05d_auto_ab.log) — the pass costs more than it saves;
-    // the boat alone visits 0.99 of it (+30 %).  The choice (option leaf_pre absent or 2) follows the
-    // scene's probe (pt_scene::pre_probe, pt_leafbvh.h probe_pre_leaves; CornellBox2 all meshes 0.38,
-    // the boat 1.00): the pass when the visited entries are at least pre_ratio % (default
-    // kPreRatioDefault) of the filtered ones, each leaf weighted by its entries.  leaf_pre=1 always,
-    // 0 never.  (The choice changes the kernels, not the image: both paths are exact.)
-    view.npre = 0;
-    view.pre = nullptr;
-    const long pre_opt = o.num("leaf_pre", 2);
-    if (wants_wavefront(o, mode, paths, view) && view.big_leaf > 0 && pre_opt != 0 && !s->pre.empty()) {
-        int32_t T = view.big_leaf;
-        if (s->leaf_sizes.size() > (size_t)kMaxPre && s->leaf_sizes[kMaxPre] >= T) T = s->leaf_sizes[kMaxPre] + 1;
-        int np = 0;
-        while (np < (int)s->pre.size() && s->pre[(size_t)np].n >= T) ++np;
-        // more big leaves than the table holds: the pass would raise the threshold to T and the big
-        // leaves left out (big_leaf <= n < T) would lose their chunk walks and cooperative turns, a
-        // cost the probe below does not weigh — AUTO keeps the traversal's own big-leaf machinery then
-        // (advisor r05; leaf_pre=1 still forces the pass)
-        if (pre_opt != 1 && T > view.big_leaf) np = 0;
-        if (np > 0 && pre_opt != 1) {
-            std::lock_guard<std::mutex> lk(s->pre_mu);  // held for the probe and for the reading of its result
-            ProbeCamera pc{};
-            for (int c = 0; c < 3; ++c) pc.cam[c] = fp.cam[c];
-            for (int c = 0; c < 16; ++c) pc.M[c] = fp.M[c];
-            pc.focal = fp.focal;
-            pc.half_h = fp.view_half_h;
-            pc.half_w = fp.view_half_h * fp.aspect;
-            // probed once per camera: a render whose camera differs from the probe's probes again
-            // (advisor r05: the choice is the camera's; both paths give the same bits)
-            if (!s->pre_probed || std::memcmp(&pc, &s->pre_cam, sizeof pc) != 0) {
-                probe_pre_leaves(s->h_nodes, s->h_tris, s->h_lights, s->pre, pc, kPreProbeGrid, kPreProbeTests,
-                                 s->pre_probe);
-                s->pre_cam = pc;
-                s->pre_probed = true;
-            }
-            if (s->pre_probe.size() >= (size_t)np) {
-                double filt = 0.0, vis = 0.0;
-                for (int b = 0; b < np; ++b) {
-                    filt += (double)s->pre_probe[(size_t)b][0] * s->pre[(size_t)b].n;
-                    vis += (double)s->pre_probe[(size_t)b][1] * s->pre[(size_t)b].n;
-                }
-                if (filt > 0.0 && vis * 100.0 < filt * (double)o.num("pre_ratio", kPreRatioDefault)) np = 0;
-            }
-        }
-        if (np > 0) {
-            // pt_device.h pre_slot finds a leaf's key slot by its first record among the first np table
-            // entries, and answers slot 0 for any other: every leaf of >= T entries must be among them
-            // (the table is the kMaxPre largest, and T was raised above the (kMaxPre + 1)-th; advisor r05)
-            for (size_t k = (size_t)np; k < s->pre.size(); ++k)
-                if (s->pre[k].n >= T) return fail(PT_ERR_SCENE, "internal: a leaf of >= big_leaf entries outside the pre-resolved table");
-            if (s->leaf_sizes.size() > (size_t)np && s->leaf_sizes[(size_t)np] >= T)
-                return fail(PT_ERR_SCENE, "internal: more leaves of >= big_leaf entries than the pre-resolved table holds");
-            view.big_leaf = T;
-            view.npre = np;
-            view.pre = s->d_pre;
-            for (int b = 0; b < kMaxPre; ++b) view.pre_rec0[b] = b < np ? s->pre[(size_t)b].rec0 : -1;
-        }
-    }
-    // a remainder stands for its leaf by another first record and count: the leaves the cooperative
-    // turns or the leaf pass take (>= big_leaf entries) must have none (every remainder's leaf has
-    // fewer than kLeafSkipMaxLeaf entries)
-    if (view.nalt != nullptr && view.big_leaf > 0 && view.big_leaf < kLeafSkipMaxLeaf)
-        return fail(PT_ERR_SCENE, "internal: leaf remainders with a big-leaf threshold below their largest leaf");
-    return PT_OK;
-}
-
-// The device table of a list render in the scene's scratch, uploaded on the call's stream: the rows and,
-// for the megakernel, its blocks.  The host copies are pageable, so the runtime has read them when
-// hipMemcpyAsync returns; the device copy is ordered with the call's launches on its stream.
-int upload_rects(pt_scene* s, const RectPlan& plan, const FrameParams& fp, bool blocks, hipStream_t stream, RectList& rl) {
-    const size_t row_bytes = align_up(plan.rows.size() * sizeof(RectRow), 256);
-    std::vector<RectBlock> hb;
-    if (blocks) {
-        if (plan.nblocks > 0x7fffffffull) return fail(PT_ERR_INVALID, "rects: too many 16x16 blocks for one megakernel grid");
-        plan_blocks(plan, hb);
-    }
-    const int rc = s->d_rects.ensure(row_bytes + hb.size() * sizeof(RectBlock), "rectangle table");
-    if (rc != PT_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(s->d_rects.p, plan.rows.data(), plan.rows.size() * sizeof(RectRow), hipMemcpyHostToDevice, stream));
-    if (!hb.empty())
-        HIP_TRY(hipMemcpyAsync(s->d_rects.p + row_bytes, hb.data(), hb.size() * sizeof(RectBlock), hipMemcpyHostToDevice, stream));
-    rl.rows = reinterpret_cast<const RectRow*>(s->d_rects.p);
-    rl.blocks = hb.empty() ? nullptr : reinterpret_cast<const RectBlock*>(s->d_rects.p + row_bytes);
-    rl.n = (uint32_t)plan.rows.size();
-    rl.npix = (uint32_t)plan.npix;
-    rl.nblocks = (uint32_t)hb.size();
-    rl.fx0 = fp.win_x0;
-    rl.fy0 = fp.win_y0;
-    return PT_OK;
-}
-
-// d_out: the window's first pixel, rows row_pitch pixels apart (win NULL: the whole image); d_m2
-// (nullable, accumulating calls): the second moments, laid out like d_out.  rects (nullable,
-// accumulating calls): the call renders these nrects rectangles of the window instead of all of it
-// (pt_render_rects: win is its frame) — "paths per frame" is then the list's pixels everywhere below
-int render_impl(pt_scene* s, const float* meta, uint32_t frame0, uint32_t nframes, uint32_t stride, int max_depth,
-                int mode, bool accum, float* d_out, Counters* d_cnt, hipStream_t stream, const pt_window* win = nullptr,
-                const size_t* pitch = nullptr, float* d_m2 = nullptr, const pt_window* rects = nullptr, size_t nrects = 0) {
-    FrameParams fp{};
-    int rc = make_params(meta, max_depth, fp, win, pitch);
-    if (rc != PT_OK) return rc;
-    RectPlan plan;
-    const bool list = rects != nullptr || nrects != 0;
-    if (list) {
-        std::string err;
-        if ((rc = plan_rects(win, fp.width, fp.height, rects, nrects, plan, err)) != PT_OK) return fail(rc, err);
-    }
-    if (mode != PT_MODE_AUTO && mode != PT_MODE_MEGAKERNEL && mode != PT_MODE_WAVEFRONT)
-        return fail(PT_ERR_INVALID, "unknown mode");
-    if (accum && (uint64_t)frame0 + (uint64_t)(nframes ? nframes - 1 : 0) * stride >= (1ull << 24))
-        return fail(PT_ERR_INVALID, "frame index >= 2^24 (t_k = u32(f32(k)) would round)");
-    HIP_TRY(hipSetDevice(s->device));
-    if (nframes == 0) return PT_OK;
-    const uint64_t npix = list ? plan.npix : (uint64_t)fp.win_w * fp.win_h;  // paths per frame: the list's or the window's
-    ProfScope prof_scope(s);
-    const Opts o = opts_snapshot();
-    const uint64_t paths = npix * (accum ? nframes : 1);
-    SceneView view;
-    if ((rc = shape_view(s, o, fp, mode, paths, view)) != PT_OK) return rc;
-    const LaunchOpts lo = launch_opts(o, mode, paths, view);
-    if ((rc = take_watchdog(s)) != PT_OK) return rc;  // an earlier asynchronous render failed
-    RectList rl{};
-    if (list && (rc = upload_rects(s, plan, fp, !lo.wavefront, stream, rl)) != PT_OK) return rc;
-    const RectList* const prl = list ? &rl : nullptr;
-    if (lo.wavefront) {
-        // the target in whole pairs of frames (a batch's two parts take whole frames each): 4096^2
-        // holds 4 frames (67 M paths), not 2 of the 3.8 that 64 M would hold
-        const uint64_t target0 = (uint64_t)std::max(1L, o.num("wf_paths", (long)kWfTargetPaths));  // A/B
-        const uint64_t pairs = (target0 + 2 * npix - 1) / (2 * npix) * (2 * npix);
-        const uint64_t target = o.has("wf_paths") || pairs > 0x7fffffffull ? target0 : pairs;
-        // at least two frames per batch when the call has two (images above the target, e.g.
-        // 4096^2): the batch's parts run on their own streams and overlap (+29 % at 4096^2)
-        const uint64_t all = npix * (accum ? nframes : 1);
-        const uint64_t two = 2 * npix <= 0x7fffffffull ? 2 * npix : npix;
-        // a call that fits the target runs as one batch: its two parts take whole frames each, so
-        // an odd frame count gets one frame of room more (5 frames: 3 + 2, not batches of 4 and 1)
-        const uint64_t all_even = accum && nframes > 1 && (nframes & 1) ? all + npix : all;
-        const uint64_t want = std::max<uint64_t>(std::min<uint64_t>(all, two), std::min<uint64_t>(all_even, target));
-        int rc2 = ensure_wavefront(s, want);
-        // the batch's state (~188 B/path: 12 GB at the 64 M-path target) may not fit beside other
-        // allocations: halve it down to one frame per batch before giving up
-        const uint64_t floor_paths = std::min<uint64_t>(all, npix);
-        for (uint64_t w = want; rc2 == PT_ERR_NOMEM && w > floor_paths;)
-            rc2 = ensure_wavefront(s, w = std::max<uint64_t>(w / 2, floor_paths));
-        if (rc2 != PT_OK) return rc2;
-        rc2 = ensure_rad(s, s->wf.capacity);
-        if (rc2 != PT_OK) return rc2;
-        if (view.npre > 0) {
-            if ((rc2 = ensure_pres(s, view.npre)) != PT_OK) return rc2;
-        } else {
-            s->wf.pres = nullptr;
-        }
-        HIP_TRY(launch_wavefront(lo, view, fp, s->wf, frame0, nframes, stride, accum, d_cnt != nullptr, d_out, d_cnt,
-                                 stream, s->ws, d_m2, prl));
-        HIP_TRY(hipMemcpyAsync(s->h_ctl, s->wf.ctl, 4 * kMaxParts * WF_CTL_WORDS, hipMemcpyDeviceToHost, stream));
-        return PT_OK;
-    }
-    HIP_TRY(launch_megakernel(lo, view, fp, frame0, nframes, stride, accum, d_cnt != nullptr, d_out, d_cnt, stream, d_m2, prl));
-    return PT_OK;
-}
-
-static_assert(sizeof(pt_tile_noise) == 16 && sizeof(TileNoise) == 16 && offsetof(pt_tile_noise, max_err) == 8 &&
-                  offsetof(TileNoise, max_err) == 8,
-              "pt_tile_noise is 16 bytes");
-
-// the tile grid of the noise and mean calls, checked (host only)
-int make_grid(uint32_t w, uint32_t h, size_t row_pitch, uint32_t tile_w, uint32_t tile_h, TileGrid& g) {
-    if (w < 1 || h < 1 || w > 32768 || h > 32768) return fail(PT_ERR_INVALID, "tiles: w and h must lie in [1, 32768]");
-    if (row_pitch < w) return fail(PT_ERR_INVALID, "row_pitch is smaller than the buffer's width");
-    if (row_pitch > 0xffffffffull) return fail(PT_ERR_INVALID, "row_pitch out of range");
-    if (tile_w < 1 || tile_h < 1) return fail(PT_ERR_INVALID, "tiles: tile_w and tile_h must be at least 1");
-    g = TileGrid{w, h, (uint32_t)row_pitch, tile_w, tile_h, (w - 1) / tile_w + 1, (h - 1) / tile_h + 1};
-    return PT_OK;
-}
-int check_tol(double tol, double floor) {
-    if (!(std::isfinite(tol) && tol > 0.0)) return fail(PT_ERR_INVALID, "tol must be finite and > 0");
-    if (!(std::isfinite(floor) && floor > 0.0)) return fail(PT_ERR_INVALID, "floor must be finite and > 0");
-    return PT_OK;
-}
-int check_adaptive(const pt_adaptive& a) {
-    if (a.tile_w < 1 || a.tile_h < 1) return fail(PT_ERR_INVALID, "pt_adaptive: tile_w and tile_h must be at least 1");
-    if (a.min_frames < 2) return fail(PT_ERR_INVALID, "pt_adaptive: min_frames must be at least 2");
-    if (a.step_frames < 1) return fail(PT_ERR_INVALID, "pt_adaptive: step_frames must be at least 1");
-    if (a.max_frames < a.min_frames) return fail(PT_ERR_INVALID, "pt_adaptive: max_frames must be at least min_frames");
-    if (!(std::isfinite(a.tol) && a.tol > 0.0)) return fail(PT_ERR_INVALID, "pt_adaptive: tol must be finite and > 0");
-    if (!(std::isfinite(a.floor) && a.floor > 0.0)) return fail(PT_ERR_INVALID, "pt_adaptive: floor must be finite and > 0");
-    if (!(a.noisy_fraction >= 0.0 && a.noisy_fraction < 1.0))
-        return fail(PT_ERR_INVALID, "pt_adaptive: noisy_fraction must lie in [0, 1)");
-    return PT_OK;
-}
-
-// The rectangles of a mask of active tiles (pt_selftest_tile_rects): tile rows top to bottom, the
-// maximal runs of active tiles in each; a run with the columns of a rectangle that reached the row
-// above extends it, any other opens a new one.  (tx0, ty0, width, height) in tiles, in opening order.
-void tile_rects(const uint8_t* active, uint32_t tx, uint32_t ty, std::vector<std::array<uint32_t, 4>>& out) {
-    out.clear();
-    std::vector<size_t> open, next;  // rectangles whose last row is the previous / this one
-    for (uint32_t y = 0; y < ty; ++y) {
-        next.clear();
-        const uint8_t* row = active + (size_t)y * tx;
-        for (uint32_t x = 0; x < tx;) {
-            if (!row[x]) { ++x; continue; }
-            uint32_t x1 = x;
-            while (x1 < tx && row[x1]) ++x1;
-            size_t k = out.size();
-            for (size_t c : open)
-                if (out[c][0] == x && out[c][2] == x1 - x) k = c;
-            if (k == out.size()) out.push_back({x, y, x1 - x, 1u});
-            else ++out[k][3];
-            next.push_back(k);
-            x = x1;
-        }
-        open.swap(next);
-    }
-}
-
-}  // namespace
-
-extern "C" {
-
-int pt_render_window_async(pt_scene* s, const float meta[48], const pt_window* win, uint32_t frame0, uint32_t nframes,
-                           uint32_t frame_stride, int max_depth, int mode, float* d_accum, size_t row_pitch,
-                           pt_counters* d_counters, void* stream) {
-    if (!s || !d_accum || !meta) return fail(PT_ERR_INVALID, "null argument");
-    return render_impl(s, meta, frame0, nframes, frame_stride, max_depth, mode, true, d_accum,
-                       reinterpret_cast<Counters*>(d_counters), static_cast<hipStream_t>(stream), win, &row_pitch);
-}
-
-int pt_render_async(pt_scene* s, const float meta[48], uint32_t frame0, uint32_t nframes, uint32_t frame_stride,
-                    int max_depth, int mode, float* d_accum, pt_counters* d_counters, void* stream) {
-    if (!s || !d_accum) return fail(PT_ERR_INVALID, "null argument");
-    return render_impl(s, meta, frame0, nframes, frame_stride, max_depth, mode, true, d_accum,
-                       reinterpret_cast<Counters*>(d_counters), static_cast<hipStream_t>(stream));
-}
-
 int pt_scene_check(pt_scene* s) {
     if (!s) return fail(PT_ERR_INVALID, "null scene");
     HIP_TRY(hipSetDevice(s->device));
@@ -1020,1019 +382,4 @@ int pt_scene_check(pt_scene* s) {
     return take_watchdog(s);
 }
 
-// The blocking calls' own stream, created on first use: asynchronous callers never pay for a
-// stream (HIP multiplexes every stream of the process onto GPU_MAX_HW_QUEUES hardware queues,
-// and an idle extra stream can push the dual-stream wavefront's two onto one queue).
-static int blocking_stream(pt_scene* s) {
-    if (!s->stream && hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess) {
-        s->stream = nullptr;
-        return fail(PT_ERR_HIP, "hipStreamCreate");
-    }
-    return PT_OK;
-}
-
-// The blocking render calls' body: the window's accumulators from the host (pt_render_image: zeroed;
-// a frame, accumulate false: neither), the render, the results back to the host — accum, or rgba
-// (nullable: the tone-mapped image instead), m2 and counters (nullable) — one synchronisation, and
-// the watchdog (a trace wave that hit kTraceWatchdog left a flag, cleared here).
-// rects (nullable): a list render of the window (pt_render_rects: win is its frame) — the list is
-// checked before anything is copied, so a rejected call leaves the host buffers alone.
-static int render_blocking(pt_scene* s, const float* meta, const pt_window* win, uint32_t frame0, uint32_t nframes,
-                           uint32_t stride, int max_depth, int mode, bool accumulate, float* accum, float* m2,
-                           uint8_t* rgba, pt_counters* counters, const pt_window* rects = nullptr, size_t nrects = 0) {
-    FrameParams fp{};
-    int rc = make_params(meta, max_depth, fp, win);
-    if (rc != PT_OK) return rc;
-    if (rects != nullptr || nrects != 0) {
-        RectPlan plan;
-        std::string err;
-        if ((rc = plan_rects(win, fp.width, fp.height, rects, nrects, plan, err)) != PT_OK) return fail(rc, err);
-    }
-    const size_t npix = (size_t)fp.win_w * fp.win_h, n = 3 * npix;
-    HIP_TRY(hipSetDevice(s->device));
-    if ((rc = s->d_accum.ensure(n, "accumulator")) != PT_OK || (m2 && (rc = s->d_m2.ensure(n, "second moments")) != PT_OK) ||
-        (rc = blocking_stream(s)) != PT_OK || (rgba && (rc = s->d_rgba.ensure(4 * npix, "image")) != PT_OK))
-        return rc;
-    Counters* d_cnt = counters ? s->d_counters : nullptr;
-    if (rgba) HIP_TRY(hipMemsetAsync(s->d_accum.p, 0, n * sizeof(float), s->stream));
-    else if (accumulate) HIP_TRY(hipMemcpyAsync(s->d_accum.p, accum, n * sizeof(float), hipMemcpyHostToDevice, s->stream));
-    if (m2) HIP_TRY(hipMemcpyAsync(s->d_m2.p, m2, n * sizeof(float), hipMemcpyHostToDevice, s->stream));
-    if (d_cnt) HIP_TRY(hipMemsetAsync(d_cnt, 0, sizeof(Counters), s->stream));
-    rc = render_impl(s, meta, frame0, nframes, stride, max_depth, mode, accumulate, s->d_accum.p, d_cnt, s->stream, win,
-                     nullptr, m2 ? s->d_m2.p : nullptr, rects, nrects);
-    if (rc != PT_OK) return rc;
-    if (rgba) {
-        if ((rc = pt_tonemap_async(s, s->d_accum.p, npix, nframes, s->d_rgba.p, s->stream)) != PT_OK) return rc;
-        HIP_TRY(hipMemcpyAsync(rgba, s->d_rgba.p, 4 * npix, hipMemcpyDeviceToHost, s->stream));
-    } else {
-        HIP_TRY(hipMemcpyAsync(accum, s->d_accum.p, n * sizeof(float), hipMemcpyDeviceToHost, s->stream));
-    }
-    if (m2) HIP_TRY(hipMemcpyAsync(m2, s->d_m2.p, n * sizeof(float), hipMemcpyDeviceToHost, s->stream));
-    if (d_cnt) HIP_TRY(hipMemcpyAsync(counters, d_cnt, sizeof(Counters), hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    return take_watchdog(s);
-}
-
-int pt_render(pt_scene* s, const float meta[48], uint32_t frame0, uint32_t nframes, uint32_t frame_stride,
-              int max_depth, int mode, float* accum, pt_counters* counters) {
-    return pt_render_window(s, meta, nullptr, frame0, nframes, frame_stride, max_depth, mode, accum, counters);
-}
-
-int pt_render_window(pt_scene* s, const float meta[48], const pt_window* win, uint32_t frame0, uint32_t nframes,
-                     uint32_t frame_stride, int max_depth, int mode, float* accum, pt_counters* counters) {
-    if (!s || !accum || !meta) return fail(PT_ERR_INVALID, "null argument");
-    return render_blocking(s, meta, win, frame0, nframes, frame_stride, max_depth, mode, true, accum, nullptr, nullptr, counters);
-}
-
-int pt_render_moments_async(pt_scene* s, const float meta[48], const pt_window* win, uint32_t frame0, uint32_t nframes,
-                            uint32_t frame_stride, int max_depth, int mode, float* d_accum, float* d_m2,
-                            size_t row_pitch, pt_counters* d_counters, void* stream) {
-    if (!s || !d_accum || !d_m2 || !meta) return fail(PT_ERR_INVALID, "null argument");
-    return render_impl(s, meta, frame0, nframes, frame_stride, max_depth, mode, true, d_accum,
-                       reinterpret_cast<Counters*>(d_counters), static_cast<hipStream_t>(stream), win, &row_pitch, d_m2);
-}
-
-int pt_render_moments(pt_scene* s, const float meta[48], const pt_window* win, uint32_t frame0, uint32_t nframes,
-                      uint32_t frame_stride, int max_depth, int mode, float* accum, float* m2, pt_counters* counters) {
-    if (!s || !accum || !m2 || !meta) return fail(PT_ERR_INVALID, "null argument");
-    return render_blocking(s, meta, win, frame0, nframes, frame_stride, max_depth, mode, true, accum, m2, nullptr, counters);
-}
-
-int pt_render_rects_async(pt_scene* s, const float meta[48], const pt_window* frame, const pt_window* rects, size_t n,
-                          uint32_t frame0, uint32_t nframes, uint32_t frame_stride, int max_depth, int mode, float* d_accum,
-                          float* d_m2, size_t row_pitch, pt_counters* d_counters, void* stream) {
-    if (!s || !d_accum || !meta) return fail(PT_ERR_INVALID, "null argument");
-    if (!rects || !n) return fail(PT_ERR_INVALID, n ? "rects is NULL" : "rects: the list is empty (n must be at least 1)");
-    return render_impl(s, meta, frame0, nframes, frame_stride, max_depth, mode, true, d_accum,
-                       reinterpret_cast<Counters*>(d_counters), static_cast<hipStream_t>(stream), frame, &row_pitch, d_m2,
-                       rects, n);
-}
-
-int pt_render_rects(pt_scene* s, const float meta[48], const pt_window* frame, const pt_window* rects, size_t n,
-                    uint32_t frame0, uint32_t nframes, uint32_t frame_stride, int max_depth, int mode, float* accum,
-                    float* m2, pt_counters* counters) {
-    if (!s || !accum || !meta) return fail(PT_ERR_INVALID, "null argument");
-    if (!rects || !n) return fail(PT_ERR_INVALID, n ? "rects is NULL" : "rects: the list is empty (n must be at least 1)");
-    return render_blocking(s, meta, frame, frame0, nframes, frame_stride, max_depth, mode, true, accum, m2, nullptr, counters,
-                           rects, n);
-}
-
-int pt_selftest_rect_plan(const pt_window* frame, uint32_t W, uint32_t H, const pt_window* rects, size_t n,
-                          uint64_t* first_out, uint64_t* npix_out) {
-    RectPlan plan;
-    std::string err;
-    const int rc = plan_rects(frame, W, H, rects, n, plan, err);
-    if (rc != PT_OK) return fail(rc, err);
-    for (size_t k = 0; first_out && k < n; ++k) first_out[k] = plan.rows[k].first;
-    if (npix_out) *npix_out = plan.npix;
-    return PT_OK;
-}
-
-int pt_noise_tiles_async(pt_scene* s, const float* d_accum, const float* d_m2, uint32_t w, uint32_t h, size_t row_pitch,
-                         uint32_t tile_w, uint32_t tile_h, const uint32_t* d_frames, double tol, double floor,
-                         pt_tile_noise* d_out, void* stream) {
-    if (!s || !d_accum || !d_m2 || !d_frames || !d_out) return fail(PT_ERR_INVALID, "null argument");
-    TileGrid g{};
-    int rc = make_grid(w, h, row_pitch, tile_w, tile_h, g);
-    if (rc != PT_OK || (rc = check_tol(tol, floor)) != PT_OK) return rc;
-    HIP_TRY(hipSetDevice(s->device));
-    ProfScope prof_scope(s);
-    HIP_TRY(launch_noise_tiles(d_accum, d_m2, g, d_frames, tol, floor, reinterpret_cast<TileNoise*>(d_out),
-                               static_cast<hipStream_t>(stream)));
-    return PT_OK;
-}
-
-int pt_tile_mean_async(pt_scene* s, const float* d_accum, uint32_t w, uint32_t h, size_t row_pitch, uint32_t tile_w,
-                       uint32_t tile_h, const uint32_t* d_frames, float* d_mean, void* stream) {
-    if (!s || !d_accum || !d_frames || !d_mean) return fail(PT_ERR_INVALID, "null argument");
-    TileGrid g{};
-    const int rc = make_grid(w, h, row_pitch, tile_w, tile_h, g);
-    if (rc != PT_OK) return rc;
-    HIP_TRY(hipSetDevice(s->device));
-    ProfScope prof_scope(s);
-    HIP_TRY(launch_tile_mean(d_accum, g, d_frames, d_mean, static_cast<hipStream_t>(stream)));
-    return PT_OK;
-}
-
-// the tile scratch of the blocking calls: T verdicts, then T frame counts
-static int ensure_tiles(pt_scene* s, size_t T, pt_tile_noise*& d_noise, uint32_t*& d_frames) {
-    const int rc = s->d_tiles.ensure(T * (sizeof(pt_tile_noise) + sizeof(uint32_t)), "tiles");
-    if (rc != PT_OK) return rc;
-    d_noise = reinterpret_cast<pt_tile_noise*>(s->d_tiles.p);
-    d_frames = reinterpret_cast<uint32_t*>(s->d_tiles.p + T * sizeof(pt_tile_noise));
-    return PT_OK;
-}
-
-int pt_noise_tiles(pt_scene* s, const float* accum, const float* m2, uint32_t w, uint32_t h, uint32_t tile_w,
-                   uint32_t tile_h, const uint32_t* frames, double tol, double floor, pt_tile_noise* out) {
-    if (!s || !accum || !m2 || !frames || !out) return fail(PT_ERR_INVALID, "null argument");
-    TileGrid g{};
-    int rc = make_grid(w, h, w, tile_w, tile_h, g);
-    if (rc != PT_OK || (rc = check_tol(tol, floor)) != PT_OK) return rc;
-    const size_t n = (size_t)w * h * 3, T = (size_t)g.tx * g.ty;
-    HIP_TRY(hipSetDevice(s->device));
-    pt_tile_noise* d_noise = nullptr;
-    uint32_t* d_frames = nullptr;
-    if ((rc = s->d_accum.ensure(n, "accumulator")) != PT_OK || (rc = s->d_m2.ensure(n, "second moments")) != PT_OK ||
-        (rc = ensure_tiles(s, T, d_noise, d_frames)) != PT_OK || (rc = blocking_stream(s)) != PT_OK)
-        return rc;
-    HIP_TRY(hipMemcpyAsync(s->d_accum.p, accum, n * sizeof(float), hipMemcpyHostToDevice, s->stream));
-    HIP_TRY(hipMemcpyAsync(s->d_m2.p, m2, n * sizeof(float), hipMemcpyHostToDevice, s->stream));
-    HIP_TRY(hipMemcpyAsync(d_frames, frames, T * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
-    if ((rc = pt_noise_tiles_async(s, s->d_accum.p, s->d_m2.p, w, h, w, tile_w, tile_h, d_frames, tol, floor, d_noise,
-                                   s->stream)) != PT_OK)
-        return rc;
-    HIP_TRY(hipMemcpyAsync(out, d_noise, T * sizeof(pt_tile_noise), hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    return PT_OK;
-}
-
-int pt_selftest_tile_rects(const uint8_t* active, uint32_t tx, uint32_t ty, uint32_t* rects, size_t cap, size_t* n_out) {
-    if (!active || !n_out || (!rects && cap)) return fail(PT_ERR_INVALID, "null argument");
-    if (tx < 1 || ty < 1 || (uint64_t)tx * ty > (1ull << 30)) return fail(PT_ERR_INVALID, "tile counts out of range");
-    std::vector<std::array<uint32_t, 4>> r;
-    tile_rects(active, tx, ty, r);
-    *n_out = r.size();
-    for (size_t k = 0; k < std::min(cap, r.size()); ++k)
-        for (int c = 0; c < 4; ++c) rects[4 * k + c] = r[k][c];
-    if (r.size() > cap) return fail(PT_ERR_INVALID, "rects holds fewer rectangles than the mask has (*n_out)");
-    return PT_OK;
-}
-
-int pt_render_adaptive(pt_scene* s, const float meta[48], const pt_window* win, const pt_adaptive* ad, uint32_t frame0,
-                       int max_depth, int mode, float* accum, float* m2, uint32_t* tile_frames, pt_tile_noise* tile_noise,
-                       uint8_t* rgba, pt_counters* counters, uint32_t* passes) {
-    if (!s || !meta || !ad || !accum || !tile_frames) return fail(PT_ERR_INVALID, "null argument");
-    int rc = check_adaptive(*ad);
-    if (rc != PT_OK) return rc;
-    if ((uint64_t)frame0 + ad->max_frames > (1ull << 24))
-        return fail(PT_ERR_INVALID, "frame0 + max_frames exceeds 2^24 (t_k = u32(f32(k)) would round)");
-    FrameParams fp{};
-    if ((rc = make_params(meta, max_depth, fp, win)) != PT_OK) return rc;
-    const uint32_t W = fp.win_w, H = fp.win_h;
-    TileGrid g{};
-    if ((rc = make_grid(W, H, W, ad->tile_w, ad->tile_h, g)) != PT_OK) return rc;
-    const size_t npix = (size_t)W * H, n = 3 * npix, T = (size_t)g.tx * g.ty;
-    HIP_TRY(hipSetDevice(s->device));
-    pt_tile_noise* d_noise = nullptr;
-    uint32_t* d_frames = nullptr;
-    if ((rc = s->d_accum.ensure(n, "accumulator")) != PT_OK || (rc = s->d_m2.ensure(n, "second moments")) != PT_OK ||
-        (rc = ensure_tiles(s, T, d_noise, d_frames)) != PT_OK || (rc = blocking_stream(s)) != PT_OK)
-        return rc;
-    if (rgba && ((rc = s->d_mean.ensure(n, "tile mean")) != PT_OK ||
-                 (rc = s->d_rgba.ensure(4 * npix, "image")) != PT_OK))
-        return rc;
-    HIP_TRY(hipMemsetAsync(s->d_accum.p, 0, n * sizeof(float), s->stream));
-    HIP_TRY(hipMemsetAsync(s->d_m2.p, 0, n * sizeof(float), s->stream));
-    HIP_TRY(hipMemsetAsync(d_frames, 0, T * sizeof(uint32_t), s->stream));
-    if (counters) HIP_TRY(hipMemsetAsync(s->d_counters, 0, sizeof(Counters), s->stream));
-    Counters* d_cnt = counters ? s->d_counters : nullptr;
-    // pass 0: the whole window
-    const pt_window whole = {fp.win_x0, fp.win_y0, W, H};
-    if ((rc = render_impl(s, meta, frame0, ad->min_frames, 1, max_depth, mode, true, s->d_accum.p, d_cnt, s->stream, &whole,
-                          nullptr, s->d_m2.p)) != PT_OK)
-        return rc;
-    std::vector<uint32_t> frames(T, ad->min_frames);
-    std::vector<pt_tile_noise> noise(T);
-    std::vector<uint8_t> active(T);
-    std::vector<std::array<uint32_t, 4>> rects;
-    std::vector<pt_window> list;
-    uint32_t done = ad->min_frames, npass = 1;  // done: the frames of every tile still active
-    for (;;) {
-        HIP_TRY(hipMemcpyAsync(d_frames, frames.data(), T * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
-        if ((rc = pt_noise_tiles_async(s, s->d_accum.p, s->d_m2.p, W, H, W, ad->tile_w, ad->tile_h, d_frames, ad->tol,
-                                       ad->floor, d_noise, s->stream)) != PT_OK)
-            return rc;
-        HIP_TRY(hipMemcpyAsync(noise.data(), d_noise, T * sizeof(pt_tile_noise), hipMemcpyDeviceToHost, s->stream));
-        HIP_TRY(hipStreamSynchronize(s->stream));
-        if ((rc = take_watchdog(s)) != PT_OK) return rc;
-        size_t nact = 0;
-        for (size_t t = 0; t < T; ++t) {
-            active[t] = noise[t].noisy > (uint32_t)(ad->noisy_fraction * noise[t].pixels) && frames[t] < ad->max_frames;
-            nact += active[t];
-        }
-        if (nact == 0) break;
-        // the active tiles' next frames: one frame range over the rectangles of the active set, clipped
-        // to the window, as ONE list render in place inside the window's buffers
-        const uint32_t nf = std::min(ad->step_frames, ad->max_frames - done);
-        tile_rects(active.data(), g.tx, g.ty, rects);
-        list.clear();
-        for (const auto& r : rects) {
-            const uint32_t px = r[0] * g.tile_w, py = r[1] * g.tile_h;
-            const uint32_t pw = (uint32_t)std::min<uint64_t>((uint64_t)r[2] * g.tile_w, W - px);
-            const uint32_t ph = (uint32_t)std::min<uint64_t>((uint64_t)r[3] * g.tile_h, H - py);
-            list.push_back(pt_window{fp.win_x0 + px, fp.win_y0 + py, pw, ph});
-        }
-        for (size_t k = 0; k < list.size(); k += kMaxRects)  // (a list call takes kMaxRects rectangles)
-            if ((rc = render_impl(s, meta, frame0 + done, nf, 1, max_depth, mode, true, s->d_accum.p, d_cnt, s->stream, &whole,
-                                  nullptr, s->d_m2.p, list.data() + k, std::min(kMaxRects, list.size() - k))) != PT_OK)
-                return rc;
-        for (size_t t = 0; t < T; ++t)
-            if (active[t]) frames[t] += nf;
-        done += nf;
-        ++npass;
-    }
-    if (rgba) {  // the display transform of the per-tile mean (d_frames holds the final counts)
-        if ((rc = pt_tile_mean_async(s, s->d_accum.p, W, H, W, ad->tile_w, ad->tile_h, d_frames, s->d_mean.p, s->stream)) != PT_OK ||
-            (rc = pt_tonemap_async(s, s->d_mean.p, npix, 1, s->d_rgba.p, s->stream)) != PT_OK)
-            return rc;
-        HIP_TRY(hipMemcpyAsync(rgba, s->d_rgba.p, 4 * npix, hipMemcpyDeviceToHost, s->stream));
-    }
-    HIP_TRY(hipMemcpyAsync(accum, s->d_accum.p, n * sizeof(float), hipMemcpyDeviceToHost, s->stream));
-    if (m2) HIP_TRY(hipMemcpyAsync(m2, s->d_m2.p, n * sizeof(float), hipMemcpyDeviceToHost, s->stream));
-    if (counters) HIP_TRY(hipMemcpyAsync(counters, s->d_counters, sizeof(Counters), hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    std::memcpy(tile_frames, frames.data(), T * sizeof(uint32_t));
-    if (tile_noise) std::memcpy(tile_noise, noise.data(), T * sizeof(pt_tile_noise));
-    if (passes) *passes = npass;
-    return take_watchdog(s);
-}
-
-// ---------------------------------------------------------------------------------------------
-// Guide buffers and the denoiser (pt_features.hip, pt_denoise.hip)
-// ---------------------------------------------------------------------------------------------
-static int features_impl(pt_scene* s, const float* meta, const pt_window* win, const size_t* pitch, uint32_t frame0,
-                         uint32_t nframes, uint32_t stride, float* d_geo, float* d_alb, Counters* d_cnt, hipStream_t stream) {
-    FrameParams fp{};
-    int rc = make_params(meta, 0, fp, win, pitch);
-    if (rc != PT_OK) return rc;
-    if ((uint64_t)frame0 + (uint64_t)(nframes ? nframes - 1 : 0) * stride >= (1ull << 24))
-        return fail(PT_ERR_INVALID, "frame index >= 2^24 (t_k = u32(f32(k)) would round)");
-    if (((uintptr_t)d_geo | (uintptr_t)d_alb) & 15u) return fail(PT_ERR_INVALID, "geo and alb must be 16-byte aligned");
-    HIP_TRY(hipSetDevice(s->device));
-    if (nframes == 0) return PT_OK;
-    ProfScope prof_scope(s);
-    // the scene as the default megakernel instance sees it: no option chooses this kernel's flavour
-    SceneView view;
-    if ((rc = shape_view(s, Opts{}, fp, PT_MODE_MEGAKERNEL, (uint64_t)fp.win_w * fp.win_h * nframes, view)) != PT_OK) return rc;
-    if ((rc = take_watchdog(s)) != PT_OK) return rc;  // an earlier asynchronous render failed
-    HIP_TRY(launch_features(view, fp, frame0, nframes, stride, d_cnt != nullptr, d_geo, d_alb, d_cnt, stream));
-    return PT_OK;
-}
-
-int pt_render_features_async(pt_scene* s, const float meta[48], const pt_window* win, uint32_t frame0, uint32_t nframes,
-                             uint32_t frame_stride, float* d_geo, float* d_alb, size_t row_pitch, pt_counters* d_counters,
-                             void* stream) {
-    if (!s || !meta || !d_geo || !d_alb) return fail(PT_ERR_INVALID, "null argument");
-    return features_impl(s, meta, win, &row_pitch, frame0, nframes, frame_stride, d_geo, d_alb,
-                         reinterpret_cast<Counters*>(d_counters), static_cast<hipStream_t>(stream));
-}
-
-int pt_render_features(pt_scene* s, const float meta[48], const pt_window* win, uint32_t frame0, uint32_t nframes,
-                       uint32_t frame_stride, float* geo, float* alb, pt_counters* counters) {
-    if (!s || !meta || !geo || !alb) return fail(PT_ERR_INVALID, "null argument");
-    FrameParams fp{};
-    int rc = make_params(meta, 0, fp, win);
-    if (rc != PT_OK) return rc;
-    const size_t n = (size_t)4 * fp.win_w * fp.win_h;
-    HIP_TRY(hipSetDevice(s->device));
-    if ((rc = s->d_feat.ensure(2 * n, "guide buffers")) != PT_OK || (rc = blocking_stream(s)) != PT_OK) return rc;
-    float* const d_geo = s->d_feat.p;
-    float* const d_alb = s->d_feat.p + n;
-    Counters* d_cnt = counters ? s->d_counters : nullptr;
-    HIP_TRY(hipMemcpyAsync(d_geo, geo, n * sizeof(float), hipMemcpyHostToDevice, s->stream));
-    HIP_TRY(hipMemcpyAsync(d_alb, alb, n * sizeof(float), hipMemcpyHostToDevice, s->stream));
-    if (d_cnt) HIP_TRY(hipMemsetAsync(d_cnt, 0, sizeof(Counters), s->stream));
-    if ((rc = features_impl(s, meta, win, nullptr, frame0, nframes, frame_stride, d_geo, d_alb, d_cnt, s->stream)) != PT_OK)
-        return rc;
-    HIP_TRY(hipMemcpyAsync(geo, d_geo, n * sizeof(float), hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipMemcpyAsync(alb, d_alb, n * sizeof(float), hipMemcpyDeviceToHost, s->stream));
-    if (d_cnt) HIP_TRY(hipMemcpyAsync(counters, d_cnt, sizeof(Counters), hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    return take_watchdog(s);
-}
-
-// ---------------------------------------------------------------------------------------------
-// Ray queries (pt_query.hip)
-// ---------------------------------------------------------------------------------------------
-static_assert(sizeof(pt_ray) == 32 && sizeof(pt_hit) == 32 && offsetof(pt_ray, d) == 16 && offsetof(pt_hit, n) == 16,
-              "pt_ray and pt_hit are two 16-byte halves");
-
-// the checks that need no device, in the header's order: true when the call ends here with rc (an
-// error, or PT_OK for an empty batch), false to go on
-// align_rays, align_out: the _async forms' device pointers (the blocking forms copy host buffers of any
-// alignment the types allow into the scene's aligned scratch)
-static bool query_args(const void* s, const void* rays, size_t n, const void* out, bool align_rays, bool align_out, int& rc) {
-    if (n > kQueryMaxRays) { rc = fail(PT_ERR_INVALID, "query: n exceeds 2^30 rays"); return true; }
-    if (n > 0 && (!rays || !out)) { rc = fail(PT_ERR_INVALID, "query: null ray or result pointer"); return true; }
-    if (n > 0 && ((align_rays && ((uintptr_t)rays & 15u)) || (align_out && ((uintptr_t)out & 15u)))) {
-        rc = fail(PT_ERR_INVALID, "query: rays and hits must be 16-byte aligned");
-        return true;
-    }
-    if (!s) { rc = fail(PT_ERR_INVALID, "null scene"); return true; }
-    if (n == 0) { rc = PT_OK; return true; }
-    return false;
-}
-
-static int ensure_query_ctl(pt_scene* s) {
-    if (s->d_qctl && s->h_qctl) return PT_OK;
-    const size_t bytes = kQueryCtlWords * sizeof(uint32_t);
-    if (!s->d_qctl) {
-        if (hipMalloc(reinterpret_cast<void**>(&s->d_qctl), bytes) != hipSuccess) {
-            s->d_qctl = nullptr;
-            (void)hipGetLastError();
-            return fail(PT_ERR_NOMEM, "hipMalloc query control words");
-        }
-        HIP_TRY(hipMemset(s->d_qctl, 0, bytes));
-    }
-    if (!s->h_qctl) {
-        if (hipHostMalloc(reinterpret_cast<void**>(&s->h_qctl), bytes) != hipSuccess) {
-            s->h_qctl = nullptr;
-            return fail(PT_ERR_NOMEM, "hipHostMalloc query control mirror");
-        }
-        std::memset(s->h_qctl, 0, bytes);
-    }
-    return PT_OK;
-}
-
-// the blocking calls' scratch, counted in device_bytes while held (as the denoiser's planes)
-static int ensure_query_scratch(pt_scene* s, size_t bytes) {
-    const size_t before = s->d_query.cap;
-    const int rc = s->d_query.ensure(bytes, "query rays and results");
-    if (rc != PT_OK) {
-        s->info.device_bytes -= before;  // (ensure frees before it allocates)
-        return rc;
-    }
-    s->info.device_bytes += s->d_query.cap - before;
-    return PT_OK;
-}
-
-// d_hits or d_occ, the other NULL; the arguments are checked (query_args)
-static int query_impl(pt_scene* s, const pt_ray* d_rays, size_t n, pt_hit* d_hits, uint8_t* d_occ, Counters* d_cnt,
-                      hipStream_t stream) {
-    HIP_TRY(hipSetDevice(s->device));
-    int rc = ensure_query_ctl(s);
-    if (rc != PT_OK) return rc;
-    ProfScope prof_scope(s);
-    const Opts o = opts_snapshot();
-    // the scene as the default megakernel instance sees it (the big-leaf threshold, the leaf
-    // remainders), as the guide buffers; of the options only the query's own and trace_watchdog apply
-    SceneView view;
-    if ((rc = shape_view(s, Opts{}, FrameParams{}, PT_MODE_MEGAKERNEL, n, view)) != PT_OK) return rc;
-    if ((rc = take_watchdog(s)) != PT_OK) return rc;  // an earlier asynchronous call failed
-    HIP_TRY(launch_query(view, d_rays, (uint32_t)n, d_hits, d_occ, d_cnt != nullptr, d_cnt, s->d_qctl,
-                         (uint32_t)o.num("trace_watchdog", 0), o.flag("query_refill", 1), (int)o.num("query_blocks", 0), stream));
-    HIP_TRY(hipMemcpyAsync(s->h_qctl, s->d_qctl, kQueryCtlWords * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    return PT_OK;
-}
-
-static int query_blocking(pt_scene* s, const pt_ray* rays, size_t n, pt_hit* hits, uint8_t* occ, pt_counters* counters) {
-    HIP_TRY(hipSetDevice(s->device));
-    const size_t ray_bytes = n * sizeof(pt_ray), out_bytes = hits ? n * sizeof(pt_hit) : n;
-    int rc;
-    if ((rc = ensure_query_scratch(s, ray_bytes + align_up(out_bytes, 16))) != PT_OK || (rc = blocking_stream(s)) != PT_OK)
-        return rc;
-    pt_ray* const d_rays = reinterpret_cast<pt_ray*>(s->d_query.p);
-    char* const d_out = s->d_query.p + ray_bytes;
-    Counters* d_cnt = counters ? s->d_counters : nullptr;
-    HIP_TRY(hipMemcpyAsync(d_rays, rays, ray_bytes, hipMemcpyHostToDevice, s->stream));
-    if (d_cnt) HIP_TRY(hipMemsetAsync(d_cnt, 0, sizeof(Counters), s->stream));
-    if ((rc = query_impl(s, d_rays, n, hits ? reinterpret_cast<pt_hit*>(d_out) : nullptr,
-                         hits ? nullptr : reinterpret_cast<uint8_t*>(d_out), d_cnt, s->stream)) != PT_OK)
-        return rc;
-    pt_counters got{};
-    HIP_TRY(hipMemcpyAsync(hits ? static_cast<void*>(hits) : static_cast<void*>(occ), d_out, out_bytes, hipMemcpyDeviceToHost,
-                           s->stream));
-    if (d_cnt) HIP_TRY(hipMemcpyAsync(&got, d_cnt, sizeof(Counters), hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    if ((rc = take_watchdog(s)) != PT_OK) return rc;
-    if (counters) {
-        counters->samples += got.samples; counters->ext_queries += got.ext_queries;
-        counters->shadow_queries += got.shadow_queries; counters->nodes += got.nodes;
-        counters->tri_tests += got.tri_tests; counters->box_tests += got.box_tests;
-    }
-    return PT_OK;
-}
-
-int pt_query_hits_async(pt_scene* s, const pt_ray* d_rays, size_t n, pt_hit* d_hits, pt_counters* d_counters, void* stream) {
-    int rc;
-    if (query_args(s, d_rays, n, d_hits, true, true, rc)) return rc;
-    return query_impl(s, d_rays, n, d_hits, nullptr, reinterpret_cast<Counters*>(d_counters), static_cast<hipStream_t>(stream));
-}
-
-int pt_query_occluded_async(pt_scene* s, const pt_ray* d_rays, size_t n, uint8_t* d_occluded, pt_counters* d_counters,
-                            void* stream) {
-    int rc;
-    if (query_args(s, d_rays, n, d_occluded, true, false, rc)) return rc;
-    return query_impl(s, d_rays, n, nullptr, d_occluded, reinterpret_cast<Counters*>(d_counters),
-                      static_cast<hipStream_t>(stream));
-}
-
-int pt_query_hits(pt_scene* s, const pt_ray* rays, size_t n, pt_hit* hits, pt_counters* counters) {
-    int rc;
-    if (query_args(s, rays, n, hits, false, false, rc)) return rc;
-    return query_blocking(s, rays, n, hits, nullptr, counters);
-}
-
-int pt_query_occluded(pt_scene* s, const pt_ray* rays, size_t n, uint8_t* occluded, pt_counters* counters) {
-    int rc;
-    if (query_args(s, rays, n, occluded, false, false, rc)) return rc;
-    return query_blocking(s, rays, n, nullptr, occluded, counters);
-}
-
-static int camera_rays_args(const pt_scene* s, const float* meta, const pt_window* win, uint32_t frame, const void* rays,
-                            bool aligned, FrameParams& fp) {
-    if (frame >= (1u << 24)) return fail(PT_ERR_INVALID, "frame index >= 2^24 (t_k = u32(f32(k)) would round)");
-    if (!meta || !rays) return fail(PT_ERR_INVALID, "null argument");
-    if (aligned && ((uintptr_t)rays & 15u)) return fail(PT_ERR_INVALID, "rays must be 16-byte aligned");
-    if (!s) return fail(PT_ERR_INVALID, "null scene");
-    return make_params(meta, 0, fp, win);
-}
-
-int pt_camera_rays_async(pt_scene* s, const float meta[48], const pt_window* win, uint32_t frame, pt_ray* d_rays,
-                         void* stream) {
-    FrameParams fp{};
-    const int rc = camera_rays_args(s, meta, win, frame, d_rays, true, fp);
-    if (rc != PT_OK) return rc;
-    HIP_TRY(hipSetDevice(s->device));
-    ProfScope prof_scope(s);
-    HIP_TRY(launch_camera_rays(fp, (uint32_t)(float)frame, d_rays, static_cast<hipStream_t>(stream)));
-    return PT_OK;
-}
-
-int pt_camera_rays(pt_scene* s, const float meta[48], const pt_window* win, uint32_t frame, pt_ray* rays) {
-    FrameParams fp{};
-    int rc = camera_rays_args(s, meta, win, frame, rays, false, fp);
-    if (rc != PT_OK) return rc;
-    const size_t bytes = (size_t)fp.win_w * fp.win_h * sizeof(pt_ray);
-    HIP_TRY(hipSetDevice(s->device));
-    if ((rc = ensure_query_scratch(s, bytes)) != PT_OK || (rc = blocking_stream(s)) != PT_OK) return rc;
-    if ((rc = pt_camera_rays_async(s, meta, win, frame, reinterpret_cast<pt_ray*>(s->d_query.p), s->stream)) != PT_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(rays, s->d_query.p, bytes, hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    return PT_OK;
-}
-
-void pt_denoise_defaults(pt_denoise_params* p) {
-    if (p) *p = pt_denoise_params{4u, 0.5f, 0.3f, 0.1f, 4.0f};
-}
-
-static int check_denoise(const pt_denoise_params& p, uint32_t feature_frames) {
-    if (p.iters < 1 || p.iters > 5) return fail(PT_ERR_INVALID, "pt_denoise_params: iters must lie in [1, 5]");
-    const float sg[4] = {p.sigma_n, p.sigma_a, p.sigma_z, p.sigma_l};
-    static const char* const names[4] = {"sigma_n", "sigma_a", "sigma_z", "sigma_l"};
-    for (int k = 0; k < 4; ++k)
-        if (!(std::isfinite(sg[k]) && sg[k] > 0.0f))
-            return fail(PT_ERR_INVALID, std::string("pt_denoise_params: ") + names[k] + " must be finite and > 0");
-    if (feature_frames < 1) return fail(PT_ERR_INVALID, "feature_frames must be at least 1");
-    return PT_OK;
-}
-
-int pt_denoise_async(pt_scene* s, const float* d_accum, const float* d_m2, uint32_t w, uint32_t h, size_t row_pitch,
-                     uint32_t tile_w, uint32_t tile_h, const uint32_t* d_frames, const float* d_geo, const float* d_alb,
-                     uint32_t feature_frames, const pt_denoise_params* p, float* d_out, float* d_var_out, void* stream) {
-    if (!s || !d_accum || !d_m2 || !d_frames || !d_geo || !d_alb || !d_out) return fail(PT_ERR_INVALID, "null argument");
-    pt_denoise_params prm;
-    pt_denoise_defaults(&prm);
-    if (p) prm = *p;
-    TileGrid g{};
-    int rc = check_denoise(prm, feature_frames);
-    if (rc != PT_OK || (rc = make_grid(w, h, row_pitch, tile_w, tile_h, g)) != PT_OK) return rc;
-    if (((uintptr_t)d_geo | (uintptr_t)d_alb) & 15u) return fail(PT_ERR_INVALID, "geo and alb must be 16-byte aligned");
-    const size_t npix = (size_t)w * h;
-    HIP_TRY(hipSetDevice(s->device));
-    {
-        const size_t before = s->d_dn.cap;
-        if ((rc = s->d_dn.ensure(4 * npix, "denoiser planes")) != PT_OK) {
-            s->info.device_bytes -= before * sizeof(float4);  // (ensure frees before it allocates)
-            return rc;
-        }
-        s->info.device_bytes += (s->d_dn.cap - before) * sizeof(float4);
-    }
-    float4* const cv[2] = {s->d_dn.p, s->d_dn.p + npix};
-    float4* const nz = s->d_dn.p + 2 * npix;
-    float4* const ab = s->d_dn.p + 3 * npix;
-    // host constants: double, rounded once
-    const float isn = (float)(1.0 / ((double)prm.sigma_n * (double)prm.sigma_n));
-    const float isa = (float)(1.0 / ((double)prm.sigma_a * (double)prm.sigma_a));
-    const float isz = (float)(1.0 / (double)prm.sigma_z);
-    // option denoise_lds = v: the first v passes (steps 1 .. 2^(v-1)) read their taps through LDS
-    const uint32_t staged = (uint32_t)opts_snapshot().num("denoise_lds", kDenoiseLdsDefault);
-    ProfScope prof_scope(s);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    HIP_TRY(launch_denoise_prepare(d_accum, d_m2, d_geo, d_alb, g, d_frames, feature_frames, cv[0], nz, ab, st));
-    for (uint32_t i = 0; i < prm.iters; ++i) {
-        const uint32_t step = 1u << i;
-        const bool last = i + 1 == prm.iters;
-        HIP_TRY(launch_atrous(cv[i & 1], nz, ab, w, h, step, isn, isa, isz, prm.sigma_l, i < staged && atrous_can_stage(step),
-                              last ? nullptr : cv[(i & 1) ^ 1], last ? d_out : nullptr, last ? d_var_out : nullptr,
-                              g.row_pitch, st));
-    }
-    return PT_OK;
-}
-
-int pt_denoise(pt_scene* s, const float* accum, const float* m2, uint32_t w, uint32_t h, uint32_t tile_w, uint32_t tile_h,
-               const uint32_t* frames, const float* geo, const float* alb, uint32_t feature_frames,
-               const pt_denoise_params* p, float* out, float* var_out) {
-    if (!s || !accum || !m2 || !frames || !geo || !alb || !out) return fail(PT_ERR_INVALID, "null argument");
-    pt_denoise_params prm;
-    pt_denoise_defaults(&prm);
-    if (p) prm = *p;
-    TileGrid g{};
-    int rc = check_denoise(prm, feature_frames);
-    if (rc != PT_OK || (rc = make_grid(w, h, w, tile_w, tile_h, g)) != PT_OK) return rc;
-    const size_t npix = (size_t)w * h, n = 3 * npix, T = (size_t)g.tx * g.ty;
-    HIP_TRY(hipSetDevice(s->device));
-    pt_tile_noise* d_noise = nullptr;
-    uint32_t* d_frames = nullptr;
-    if ((rc = s->d_accum.ensure(n, "accumulator")) != PT_OK || (rc = s->d_m2.ensure(n, "second moments")) != PT_OK ||
-        (rc = s->d_mean.ensure(n, "filtered image")) != PT_OK || (rc = s->d_feat.ensure(8 * npix, "guide buffers")) != PT_OK ||
-        (rc = s->d_var.ensure(npix, "filtered variance")) != PT_OK || (rc = ensure_tiles(s, T, d_noise, d_frames)) != PT_OK ||
-        (rc = blocking_stream(s)) != PT_OK)
-        return rc;
-    float* const d_geo = s->d_feat.p;
-    float* const d_alb = s->d_feat.p + 4 * npix;
-    HIP_TRY(hipMemcpyAsync(s->d_accum.p, accum, n * sizeof(float), hipMemcpyHostToDevice, s->stream));
-    HIP_TRY(hipMemcpyAsync(s->d_m2.p, m2, n * sizeof(float), hipMemcpyHostToDevice, s->stream));
-    HIP_TRY(hipMemcpyAsync(d_geo, geo, 4 * npix * sizeof(float), hipMemcpyHostToDevice, s->stream));
-    HIP_TRY(hipMemcpyAsync(d_alb, alb, 4 * npix * sizeof(float), hipMemcpyHostToDevice, s->stream));
-    HIP_TRY(hipMemcpyAsync(d_frames, frames, T * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
-    if ((rc = pt_denoise_async(s, s->d_accum.p, s->d_m2.p, w, h, w, tile_w, tile_h, d_frames, d_geo, d_alb, feature_frames,
-                               &prm, s->d_mean.p, var_out ? s->d_var.p : nullptr, s->stream)) != PT_OK)
-        return rc;
-    HIP_TRY(hipMemcpyAsync(out, s->d_mean.p, n * sizeof(float), hipMemcpyDeviceToHost, s->stream));
-    if (var_out) HIP_TRY(hipMemcpyAsync(var_out, s->d_var.p, npix * sizeof(float), hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    return PT_OK;
-}
-
-int pt_render_denoised_image(pt_scene* s, const float meta[48], uint32_t frame0, uint32_t nframes, uint32_t frame_stride,
-                             int max_depth, int mode, uint32_t feature_frames, const pt_denoise_params* params,
-                             uint8_t* rgba, pt_counters* counters) {
-    if (!s || !meta || !rgba) return fail(PT_ERR_INVALID, "null argument");
-    if (nframes < 2) return fail(PT_ERR_INVALID, "nframes must be at least 2 (the variance needs two samples)");
-    pt_denoise_params prm;
-    pt_denoise_defaults(&prm);
-    if (params) prm = *params;
-    int rc = check_denoise(prm, feature_frames);
-    if (rc != PT_OK) return rc;
-    FrameParams fp{};
-    if ((rc = make_params(meta, max_depth, fp)) != PT_OK) return rc;
-    const uint32_t W = fp.width, H = fp.height;
-    const size_t npix = (size_t)W * H, n = 3 * npix;
-    HIP_TRY(hipSetDevice(s->device));
-    pt_tile_noise* d_noise = nullptr;
-    uint32_t* d_frames = nullptr;
-    if ((rc = s->d_accum.ensure(n, "accumulator")) != PT_OK || (rc = s->d_m2.ensure(n, "second moments")) != PT_OK ||
-        (rc = s->d_mean.ensure(n, "filtered image")) != PT_OK || (rc = s->d_feat.ensure(8 * npix, "guide buffers")) != PT_OK ||
-        (rc = s->d_rgba.ensure(4 * npix, "image")) != PT_OK || (rc = ensure_tiles(s, 1, d_noise, d_frames)) != PT_OK ||
-        (rc = blocking_stream(s)) != PT_OK)
-        return rc;
-    float* const d_geo = s->d_feat.p;
-    float* const d_alb = s->d_feat.p + 4 * npix;
-    Counters* d_cnt = counters ? s->d_counters : nullptr;
-    HIP_TRY(hipMemsetAsync(s->d_accum.p, 0, n * sizeof(float), s->stream));
-    HIP_TRY(hipMemsetAsync(s->d_m2.p, 0, n * sizeof(float), s->stream));
-    HIP_TRY(hipMemsetAsync(s->d_feat.p, 0, 8 * npix * sizeof(float), s->stream));
-    HIP_TRY(hipMemcpyAsync(d_frames, &nframes, sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
-    if (d_cnt) HIP_TRY(hipMemsetAsync(d_cnt, 0, sizeof(Counters), s->stream));
-    if ((rc = render_impl(s, meta, frame0, nframes, frame_stride, max_depth, mode, true, s->d_accum.p, d_cnt, s->stream, nullptr,
-                          nullptr, s->d_m2.p)) != PT_OK ||
-        (rc = features_impl(s, meta, nullptr, nullptr, frame0, feature_frames, 1, d_geo, d_alb, d_cnt, s->stream)) != PT_OK ||
-        (rc = pt_denoise_async(s, s->d_accum.p, s->d_m2.p, W, H, W, W, H, d_frames, d_geo, d_alb, feature_frames, &prm,
-                               s->d_mean.p, nullptr, s->stream)) != PT_OK ||
-        (rc = pt_tonemap_async(s, s->d_mean.p, npix, 1, s->d_rgba.p, s->stream)) != PT_OK)
-        return rc;
-    HIP_TRY(hipMemcpyAsync(rgba, s->d_rgba.p, 4 * npix, hipMemcpyDeviceToHost, s->stream));
-    if (d_cnt) HIP_TRY(hipMemcpyAsync(counters, d_cnt, sizeof(Counters), hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    return take_watchdog(s);
-}
-
-int pt_frame_async(pt_scene* s, const float meta[48], uint32_t t, int max_depth, float* d_radiance, void* stream) {
-    if (!s || !d_radiance) return fail(PT_ERR_INVALID, "null argument");
-    return render_impl(s, meta, t, 1, 1, max_depth, PT_MODE_AUTO, false, d_radiance, nullptr,
-                       static_cast<hipStream_t>(stream));
-}
-
-int pt_frame(pt_scene* s, const float meta[48], uint32_t t, int max_depth, float* radiance) {
-    return pt_frame_window(s, meta, nullptr, t, max_depth, radiance);
-}
-
-int pt_frame_window(pt_scene* s, const float meta[48], const pt_window* win, uint32_t t, int max_depth, float* radiance) {
-    if (!s || !radiance || !meta) return fail(PT_ERR_INVALID, "null argument");
-    return render_blocking(s, meta, win, t, 1, 1, max_depth, PT_MODE_AUTO, false, radiance, nullptr, nullptr, nullptr);
-}
-
-int pt_tonemap_async(pt_scene* s, const float* d_accum, size_t npix, uint32_t sample_runs, uint8_t* d_rgba,
-                     void* stream) {
-    if (!s || !d_accum || !d_rgba || sample_runs == 0) return fail(PT_ERR_INVALID, "null argument or zero sample_runs");
-    HIP_TRY(hipSetDevice(s->device));
-    ProfScope prof_scope(s);
-    HIP_TRY(launch_tonemap(d_accum, npix, sample_runs, d_rgba, static_cast<hipStream_t>(stream)));
-    return PT_OK;
-}
-
-int pt_readback_async(pt_scene* s, const float* d_src, size_t n, float* h_dst, void* stream) {
-    if (!s) return fail(PT_ERR_INVALID, "null scene");
-    if (n == 0) return PT_OK;
-    if (!d_src || !h_dst) return fail(PT_ERR_INVALID, "null argument");
-    if (((uintptr_t)d_src | (uintptr_t)h_dst) & 15u) return fail(PT_ERR_INVALID, "buffers must be 16-byte aligned");
-    HIP_TRY(hipSetDevice(s->device));
-    void* hd = nullptr;  // pinned host memory: its address in the device's view
-    if (hipHostGetDevicePointer(&hd, h_dst, 0) != hipSuccess || !hd) {
-        (void)hipGetLastError();
-        return fail(PT_ERR_INVALID, "h_dst is not pinned (page-locked) host memory");
-    }
-    HIP_TRY(launch_readback(d_src, static_cast<float*>(hd), n, static_cast<hipStream_t>(stream)));
-    return PT_OK;
-}
-
-int pt_render_image(pt_scene* s, const float meta[48], uint32_t frame0, uint32_t nframes, uint32_t frame_stride,
-                    int max_depth, int mode, uint8_t* rgba, pt_counters* counters) {
-    if (!s || !rgba || !meta) return fail(PT_ERR_INVALID, "null argument");
-    if (nframes == 0) return fail(PT_ERR_INVALID, "nframes == 0 (the image divides by the sample count)");
-    return render_blocking(s, meta, nullptr, frame0, nframes, frame_stride, max_depth, mode, true, nullptr, nullptr, rgba, counters);
-}
-
-int pt_tonemap(const float* acc, size_t npix, uint32_t sample_runs, uint8_t* rgba) {
-    if (!acc || !rgba || sample_runs == 0) return fail(PT_ERR_INVALID, "null argument or zero sample_runs");
-    auto to_int32 = [](double v) -> int32_t {  // ECMAScript ToInt32
-        if (!std::isfinite(v)) return 0;
-        double m = std::fmod(std::trunc(v), 4294967296.0);
-        if (m < 0) m += 4294967296.0;
-        return (int32_t)(uint32_t)m;
-    };
-    auto u8 = [](int32_t v) -> uint8_t { return v < 0 ? 0 : (v > 255 ? 255 : (uint8_t)v); };
-    for (size_t i = 0; i < npix; ++i) {
-        const double r = (double)acc[3 * i] / sample_runs, g = (double)acc[3 * i + 1] / sample_runs,
-                     b = (double)acc[3 * i + 2] / sample_runs;
-        const double lum = (r + g + b) / 3.0;
-        const double f = std::pow(lum / (lum + 1.0), 0.01);
-        rgba[4 * i] = u8(to_int32(r * f * 255.0));
-        rgba[4 * i + 1] = u8(to_int32(g * f * 255.0));
-        rgba[4 * i + 2] = u8(to_int32(b * f * 255.0));
-        rgba[4 * i + 3] = 255;
-    }
-    return PT_OK;
-}
-
-int pt_selftest_math(int device, int fn, const float* a, const float* b, float* out, size_t n) {
-    if (!a || !b || !out || n == 0 || n > (1u << 28)) return fail(PT_ERR_INVALID, "bad argument");
-    if (fn < 0 || fn >= PT_MATH_COUNT_) return fail(PT_ERR_INVALID, "unknown math fn");
-    HIP_TRY(hipSetDevice(device));
-    float *da = nullptr, *db = nullptr, *dout = nullptr;
-    HIP_TRY(hipMalloc(&da, n * 4));
-    HIP_TRY(hipMalloc(&db, n * 4));
-    HIP_TRY(hipMalloc(&dout, n * 4));
-    hipMemcpy(da, a, n * 4, hipMemcpyHostToDevice);
-    hipMemcpy(db, b, n * 4, hipMemcpyHostToDevice);
-    hipError_t e = launch_selftest_math(fn, da, db, dout, (int)n, nullptr);
-    if (e == hipSuccess) e = hipMemcpy(out, dout, n * 4, hipMemcpyDeviceToHost);
-    hipFree(da); hipFree(db); hipFree(dout);
-    if (e != hipSuccess) return fail(PT_ERR_HIP, hipGetErrorString(e));
-    return PT_OK;
-}
-
-int pt_selftest_valu(int device, int iters, int reps, int packed, double* ms_out, uint64_t* fma_wave_instr_out) {
-    if (iters < 1 || reps < 1 || !ms_out) return fail(PT_ERR_INVALID, "bad argument");
-    HIP_TRY(hipSetDevice(device));
-    int cus = 0;
-    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
-    const int blocks = cus * 8;  // 8 blocks of 4 waves per CU: 8 waves per SIMD
-    float* d = nullptr;
-    HIP_TRY(hipMalloc(&d, (size_t)blocks * 256 * sizeof(float)));
-    hipEvent_t a = nullptr, b = nullptr;
-    hipError_t e = hipEventCreate(&a);
-    if (e == hipSuccess) e = hipEventCreate(&b);
-    if (e == hipSuccess) e = launch_selftest_valu(iters, blocks, packed, d, nullptr);  // warm-up (clock ramp)
-    if (e == hipSuccess) e = hipEventRecord(a, nullptr);
-    for (int r = 0; r < reps && e == hipSuccess; ++r) e = launch_selftest_valu(iters, blocks, packed, d, nullptr);
-    if (e == hipSuccess) e = hipEventRecord(b, nullptr);
-    if (e == hipSuccess) e = hipEventSynchronize(b);
-    float ms = 0.0f;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, a, b);
-    if (a) hipEventDestroy(a);
-    if (b) hipEventDestroy(b);
-    hipFree(d);
-    if (e != hipSuccess) return fail(PT_ERR_HIP, hipGetErrorString(e));
-    *ms_out = ms;
-    // v_fma_f32 / v_pk_fma_f32 wave-instructions of the timed launches: 32 per iteration per wave
-    if (fma_wave_instr_out) *fma_wave_instr_out = (uint64_t)reps * blocks * 4 * (uint64_t)iters * 32;
-    return PT_OK;
-}
-
-int pt_scene_leaf_bvh(const pt_scene* s, int leaf, int32_t* first_record, int32_t* entries, int32_t* nodes) {
-    if (!s) return fail(PT_ERR_INVALID, "null scene");
-    if (leaf < 0 || (size_t)leaf >= s->lleaves.size()) return fail(PT_ERR_INVALID, "no such leaf BVH");
-    const auto& l = s->lleaves[(size_t)leaf];
-    if (first_record) *first_record = l[0];
-    if (entries) *entries = l[1];
-    if (nodes) *nodes = l[2];
-    return PT_OK;
-}
-
-int pt_selftest_leaf(pt_scene* s, int leaf, int mode, uint32_t seed, uint32_t nrays, int32_t* out) {
-    if (!s || !out) return fail(PT_ERR_INVALID, "null argument");
-    if (mode < 0 || (mode > 7 && mode < 16) || mode > 31 || nrays == 0 || nrays > (1u << 24))
-        return fail(PT_ERR_INVALID, "bad mode or ray count");
-    const bool pass = mode >= 16;
-    if (!pass && (leaf < 0 || (size_t)leaf >= s->lleaves.size())) return fail(PT_ERR_INVALID, "no such leaf BVH");
-    if (pass && (leaf < 0 || (size_t)leaf >= s->pre.size())) return fail(PT_ERR_INVALID, "no such pre-resolvable leaf");
-    if (pass && ((mode >> 2) & 3) >= 2 && (!s->view.pnodes || s->pre[(size_t)leaf].c1 <= s->pre[(size_t)leaf].c0))
-        return fail(PT_ERR_INVALID, "the leaf has no pass chunks (option leaf_bvh)");
-    HIP_TRY(hipSetDevice(s->device));
-    int32_t* d = nullptr;
-    HIP_TRY(hipMalloc(&d, (size_t)nrays * 6 * sizeof(int32_t)));
-    hipError_t e;
-    if (pass) {
-        SceneView v = s->view;
-        v.pre = s->d_pre;
-        v.npre = (int32_t)s->pre.size();
-        e = launch_selftest_leafpass(v, leaf, mode & 15, seed, nrays, d, nullptr);
-    } else {
-        const auto& l = s->lleaves[(size_t)leaf];
-        e = launch_selftest_leaf(s->view, l[0], l[1], mode, seed, nrays, d, nullptr);
-    }
-    if (e == hipSuccess) e = hipMemcpy(out, d, (size_t)nrays * 6 * sizeof(int32_t), hipMemcpyDeviceToHost);
-    hipFree(d);
-    if (e != hipSuccess) return fail(PT_ERR_HIP, hipGetErrorString(e));
-    return PT_OK;
-}
-
-int pt_selftest_lights(pt_scene* s, const uint32_t* seeds, const float* points, size_t n, float* out) {
-    if (!s || !seeds || !points || !out) return fail(PT_ERR_INVALID, "null argument");
-    if (n == 0 || n > (1u << 24)) return fail(PT_ERR_INVALID, "bad sample count");
-    HIP_TRY(hipSetDevice(s->device));
-    uint32_t* dseeds = nullptr;
-    float *dpts = nullptr, *dout = nullptr;
-    hipError_t e = hipMalloc(&dseeds, n * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc(&dpts, n * 3 * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(&dout, n * 4 * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(dseeds, seeds, n * sizeof(uint32_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dpts, points, n * 3 * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = launch_selftest_lights(s->view, dseeds, dpts, (uint32_t)n, dout, nullptr);
-    if (e == hipSuccess) e = hipMemcpy(out, dout, n * 4 * sizeof(float), hipMemcpyDeviceToHost);
-    hipFree(dseeds); hipFree(dpts); hipFree(dout);
-    if (e != hipSuccess) return fail(PT_ERR_HIP, hipGetErrorString(e));
-    return PT_OK;
-}
-
-int pt_selftest_view_half_h(const float* metas, size_t n, float* out) {
-    if (!metas || !out) return fail(PT_ERR_INVALID, "null argument");
-    for (size_t i = 0; i < n; ++i) {
-        FrameParams fp;
-        if (int rc = make_params(metas + 48 * i, 0, fp); rc != PT_OK) return rc;
-        out[i] = fp.view_half_h;
-    }
-    return PT_OK;
-}
-
-int pt_selftest_rcp(int device, int steps, uint32_t lo_bits, uint32_t hi_bits, uint64_t* mismatches,
-                    uint32_t* failing_bits) {
-    if (!mismatches || steps < -1 || steps > 2 || lo_bits > hi_bits || hi_bits >= 0x80000000u)
-        return fail(PT_ERR_INVALID, "bad argument");
-    if (steps < 0) steps = kRcpSteps;
-    HIP_TRY(hipSetDevice(device));
-    unsigned long long* d = nullptr;
-    HIP_TRY(hipMalloc(&d, 2 * sizeof(unsigned long long)));
-    unsigned long long h[2] = {0, 0};
-    hipError_t e = hipMemset(d, 0, sizeof(h));
-    if (e == hipSuccess) e = launch_selftest_rcp(steps, lo_bits, hi_bits, d, nullptr);
-    if (e == hipSuccess) e = hipMemcpy(h, d, sizeof(h), hipMemcpyDeviceToHost);
-    hipFree(d);
-    if (e != hipSuccess) return fail(PT_ERR_HIP, hipGetErrorString(e));
-    *mismatches = h[0];
-    if (failing_bits) *failing_bits = (uint32_t)h[1];
-    return PT_OK;
-}
-
-
 }  // extern "C"
-
-// ---------------------------------------------------------------------------------------------
-// Multi-GPU (pt_render_multi): one host thread per device renders its frames, then ONE reduction
-// ---------------------------------------------------------------------------------------------
-namespace {
-
-struct RcclApi {
-    bool ok = false;
-    ncclResult_t (*comm_init_all)(ncclComm_t*, int, const int*) = nullptr;
-    ncclResult_t (*comm_destroy)(ncclComm_t) = nullptr;
-    ncclResult_t (*reduce)(const void*, void*, size_t, ncclDataType_t, ncclRedOp_t, int, ncclComm_t, hipStream_t) = nullptr;
-    ncclResult_t (*group_start)() = nullptr;
-    ncclResult_t (*group_end)() = nullptr;
-    const char* (*error_string)(ncclResult_t) = nullptr;
-};
-
-std::mutex g_rccl_mu;
-
-// librccl: the copy already in the process (e.g. torch's) if there is one, else the system's.
-// Resolved once (a function-local static: thread-safe initialisation).
-const RcclApi& rccl_api() {
-    static const RcclApi api = [] {
-        RcclApi a;
-        void* h = nullptr;
-        for (const char* n : {"librccl.so.1", "librccl.so"})
-            if ((h = dlopen(n, RTLD_NOW | RTLD_NOLOAD))) break;
-        for (const char* n : {"librccl.so.1", "/opt/rocm/lib/librccl.so.1"})
-            if (!h) h = dlopen(n, RTLD_NOW | RTLD_GLOBAL);
-        if (!h) return a;
-        a.comm_init_all = reinterpret_cast<decltype(a.comm_init_all)>(dlsym(h, "ncclCommInitAll"));
-        a.comm_destroy = reinterpret_cast<decltype(a.comm_destroy)>(dlsym(h, "ncclCommDestroy"));
-        a.reduce = reinterpret_cast<decltype(a.reduce)>(dlsym(h, "ncclReduce"));
-        a.group_start = reinterpret_cast<decltype(a.group_start)>(dlsym(h, "ncclGroupStart"));
-        a.group_end = reinterpret_cast<decltype(a.group_end)>(dlsym(h, "ncclGroupEnd"));
-        a.error_string = reinterpret_cast<decltype(a.error_string)>(dlsym(h, "ncclGetErrorString"));
-        a.ok = a.comm_init_all && a.comm_destroy && a.reduce && a.group_start && a.group_end && a.error_string;
-        return a;
-    }();
-    return api;
-}
-
-// one communicator set per device list, made on first use and kept until pt_release_communicators
-// or process exit (an atexit handler registered after the HIP runtime started runs before the
-// runtime's own teardown)
-std::map<std::vector<int>, std::vector<ncclComm_t>> g_comms;
-
-int destroy_comms_locked() {
-    const RcclApi& a = rccl_api();
-    ncclResult_t bad = ncclSuccess;
-    for (auto& kv : g_comms)
-        for (ncclComm_t c : kv.second) {
-            const ncclResult_t r = a.comm_destroy(c);
-            if (r != ncclSuccess) bad = r;
-        }
-    g_comms.clear();
-    if (bad != ncclSuccess) return fail(PT_ERR_HIP, std::string("ncclCommDestroy: ") + a.error_string(bad));
-    return PT_OK;
-}
-
-void destroy_comms_at_exit() {
-    std::lock_guard<std::mutex> lk(g_rccl_mu);
-    if (!g_comms.empty()) destroy_comms_locked();
-}
-
-int rccl_reduce(pt_scene* const* sc, int n, size_t count) {
-    std::lock_guard<std::mutex> lk(g_rccl_mu);
-    const RcclApi& a = rccl_api();
-    std::vector<int> devs(n);
-    for (int g = 0; g < n; ++g) devs[g] = sc[g]->device;
-    auto it = g_comms.find(devs);
-    if (it == g_comms.end()) {
-        static bool registered = false;
-        if (!registered) registered = std::atexit(destroy_comms_at_exit) == 0;
-        std::vector<ncclComm_t> c(n);
-        const ncclResult_t r = a.comm_init_all(c.data(), n, devs.data());
-        if (r != ncclSuccess) return fail(PT_ERR_HIP, std::string("ncclCommInitAll: ") + a.error_string(r));
-        it = g_comms.emplace(devs, c).first;
-    }
-    // Nothing returns between ncclGroupStart and ncclGroupEnd: an open group would stay open for the
-    // next RCCL call of the process.  No hipSetDevice inside the group either (each communicator
-    // carries its device, and a failing call there was such a return, verdict r04 weak #3): the
-    // reduces are issued until one fails, the group is always closed, then the error is reported.
-    ncclResult_t r = a.group_start();
-    if (r == ncclSuccess) {
-        for (int g = 0; g < n && r == ncclSuccess; ++g)
-            r = a.reduce(sc[g]->d_accum.p, sc[g]->d_accum.p, count, ncclFloat32, ncclSum, 0, it->second[g], sc[g]->stream);
-        const ncclResult_t r2 = a.group_end();
-        if (r == ncclSuccess) r = r2;
-    }
-    if (r != ncclSuccess) return fail(PT_ERR_HIP, std::string("ncclReduce: ") + a.error_string(r));
-    for (int g = 0; g < n; ++g) {
-        HIP_TRY(hipSetDevice(sc[g]->device));
-        HIP_TRY(hipStreamSynchronize(sc[g]->stream));
-    }
-    return PT_OK;
-}
-
-// device order: partials of scenes 1..n-1 copied to device 0 and added there one after another
-int ordered_reduce(pt_scene* const* sc, int n, size_t count) {
-    pt_scene* s0 = sc[0];
-    HIP_TRY(hipSetDevice(s0->device));
-    const int rc = s0->d_peer.ensure(count, "peer accumulator");
-    if (rc != PT_OK) return rc;
-    for (int g = 1; g < n; ++g) {
-        if (sc[g]->device == s0->device)
-            HIP_TRY(launch_accum_add(s0->d_accum.p, sc[g]->d_accum.p, count, s0->stream));
-        else {
-            HIP_TRY(hipMemcpyPeerAsync(s0->d_peer.p, s0->device, sc[g]->d_accum.p, sc[g]->device, count * sizeof(float),
-                                       s0->stream));
-            HIP_TRY(launch_accum_add(s0->d_accum.p, s0->d_peer.p, count, s0->stream));
-        }
-    }
-    HIP_TRY(hipStreamSynchronize(s0->stream));
-    return PT_OK;
-}
-
-}  // namespace
-
-extern "C" int pt_render_multi(pt_scene* const* scenes, int n, const float meta[48], uint32_t frame0, uint32_t nframes,
-                               uint32_t frame_stride, int max_depth, int mode, float* accum, pt_counters* counters) {
-    if (!scenes || n < 1 || n > 64 || !meta || !accum) return fail(PT_ERR_INVALID, "bad argument");
-    for (int g = 0; g < n; ++g)
-        for (int h = 0; h < g; ++h)
-            if (!scenes[g] || scenes[g] == scenes[h]) return fail(PT_ERR_INVALID, "null or repeated scene");
-    if (!scenes[0]) return fail(PT_ERR_INVALID, "null scene");
-    const Opts o = opts_snapshot();
-    // one device is pt_render itself — unless option reduce=rccl asks for the RCCL branch anyway
-    // (a one-rank communicator: how a one-GPU machine runs that code, tests/test_gpu_multi.py)
-    if (n == 1 && !o.is("reduce", "rccl"))
-        return pt_render(scenes[0], meta, frame0, nframes, frame_stride, max_depth, mode, accum, counters);
-    FrameParams fp{};
-    int rc = make_params(meta, max_depth, fp);
-    if (rc != PT_OK) return rc;
-    if ((uint64_t)frame0 + (uint64_t)(nframes ? nframes - 1 : 0) * frame_stride >= (1ull << 24))
-        return fail(PT_ERR_INVALID, "frame index >= 2^24 (t_k = u32(f32(k)) would round)");
-    const size_t count = (size_t)fp.width * fp.height * 3;
-    bool distinct = true;
-    for (int g = 0; g < n; ++g)
-        for (int h = 0; h < g; ++h) distinct &= scenes[g]->device != scenes[h]->device;
-    const bool want_rccl = !o.is("reduce", "ordered");
-    if (o.is("reduce", "rccl") && (!distinct || !rccl_api().ok))
-        return fail(PT_ERR_INVALID, "option reduce=rccl needs distinct devices and librccl.so.1");
-    const bool use_rccl = want_rccl && distinct && rccl_api().ok;
-    for (int g = 0; g < n; ++g) {  // accumulators: scenes[0]'s from accum, the others zero
-        pt_scene* s = scenes[g];
-        HIP_TRY(hipSetDevice(s->device));
-        if ((rc = s->d_accum.ensure(count, "accumulator")) != PT_OK || (rc = blocking_stream(s)) != PT_OK) return rc;
-        if (g == 0) HIP_TRY(hipMemcpyAsync(s->d_accum.p, accum, count * sizeof(float), hipMemcpyHostToDevice, s->stream));
-        else HIP_TRY(hipMemsetAsync(s->d_accum.p, 0, count * sizeof(float), s->stream));
-        if (counters) HIP_TRY(hipMemsetAsync(s->d_counters, 0, sizeof(Counters), s->stream));
-    }
-    // frames i = g, g + n, ... on scene g, each device on a host thread of its own (the wavefront's
-    // host loop waits on its device; one thread would serialise the devices)
-    std::vector<int> rcs(n, PT_OK);
-    std::vector<std::string> errs(n);
-    std::vector<std::thread> th;
-    for (int g = 0; g < n; ++g)
-        th.emplace_back([&, g]() {
-            pt_scene* s = scenes[g];
-            const uint32_t cnt = nframes > (uint32_t)g ? (nframes - (uint32_t)g + (uint32_t)n - 1) / (uint32_t)n : 0u;
-            int r = hipSetDevice(s->device) == hipSuccess ? PT_OK : fail(PT_ERR_HIP, "hipSetDevice");
-            if (r == PT_OK)
-                r = render_impl(s, meta, frame0 + (uint32_t)g * frame_stride, cnt, (uint32_t)n * frame_stride, max_depth,
-                                mode, true, s->d_accum.p, counters ? s->d_counters : nullptr, s->stream);
-            if (r == PT_OK && hipStreamSynchronize(s->stream) != hipSuccess) r = fail(PT_ERR_HIP, "render stream");
-            if (r == PT_OK) r = take_watchdog(s);
-            rcs[g] = r;
-            if (r != PT_OK) errs[g] = pt_last_error();
-        });
-    for (auto& t : th) t.join();
-    for (int g = 0; g < n; ++g)
-        if (rcs[g] != PT_OK) return fail(rcs[g], "device " + std::to_string(scenes[g]->device) + ": " + errs[g]);
-    rc = use_rccl ? rccl_reduce(scenes, n, count) : ordered_reduce(scenes, n, count);
-    if (rc != PT_OK) return rc;
-    pt_scene* s0 = scenes[0];
-    HIP_TRY(hipSetDevice(s0->device));
-    HIP_TRY(hipMemcpyAsync(accum, s0->d_accum.p, count * sizeof(float), hipMemcpyDeviceToHost, s0->stream));
-    HIP_TRY(hipStreamSynchronize(s0->stream));
-    if (counters) {
-        pt_counters sum{};
-        for (int g = 0; g < n; ++g) {
-            pt_counters c{};
-            HIP_TRY(hipSetDevice(scenes[g]->device));
-            HIP_TRY(hipMemcpy(&c, scenes[g]->d_counters, sizeof c, hipMemcpyDeviceToHost));
-            sum.samples += c.samples; sum.ext_queries += c.ext_queries; sum.shadow_queries += c.shadow_queries;
-            sum.nodes += c.nodes; sum.tri_tests += c.tri_tests; sum.box_tests += c.box_tests;
-        }
-        *counters = sum;
-    }
-    return PT_OK;
-}
-
-extern "C" int pt_release_communicators(void) {
-    std::lock_guard<std::mutex> lk(g_rccl_mu);
-    if (g_comms.empty()) return PT_OK;
-    return destroy_comms_locked();
-}

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""In-process A/B of render options (pt_set_option switches read by every render call, csrc/pt_capi.hip
+"""In-process A/B of render options (pt_set_option switches read by every render call, csrc/pt_capi_render.hip
 launch_opts; keys as "kernel" or the old spelling "PT_KERNEL").  Each variant renders the same workload; results must be
 bit-identical to the first variant's; times are medians of --reps renders, variants interleaved.
 usage: env_ab.py [--scene S --width W --height H --spp N --depth D --reps R] 'A=1,B=2' 'A=0' ..."""

@@ -22,7 +22,7 @@ int main() {
                     for (int mailbox = -1; mailbox < 2; ++mailbox)
                         for (int bf = -1; bf < 2; ++bf)
                             for (int fuse = -1; fuse < 2; ++fuse) {
-                                pt::LaunchOpts lo;  // as pt_capi.hip launch_opts fills it
+                                pt::LaunchOpts lo;  // as pt_capi_render.hip launch_opts fills it
                                 lo.wavefront = wf != 0;
                                 lo.set_flavour_opts(trav, fastrcp, mailbox, bf, fuse);
                                 const bool f0 = facts & 1, f1 = facts & 2, f2 = facts & 4, f3 = facts & 8;

@@ -2,7 +2,7 @@
 // code and message, then per HostLayout array its length, element size and the 64-bit FNV-1a of its
 // bytes (every hashed record is written whole: value-initialised or memset by its builder), the
 // scalars, and the device section plan.  tests/test_scene_layout.py compares the output with
-// tests/golden/scene_layout.txt, recorded from build_layout as it stood inside pt_capi.hip.
+// tests/golden/scene_layout.txt, recorded from build_layout as it stood inside the C ABI file.
 //   C=brown-cs2240-path-tracer_amd/csrc
 //   hipcc -x hip --offload-arch=gfx950 -O2 -std=c++17 -ffp-contract=off -I $C scripts/scene_layout_harness.cpp \
 //       $C/pt_scene_layout.cpp $C/pt_leafbvh.cpp $C/pt_leafskip.cpp -o harness

@@ -19,7 +19,7 @@ HEADER = os.path.join(ROOT, "include", "pt_hip.h")
 def declared_functions():
     text = open(HEADER).read()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(pt_[a-z_]+)\s*\(", text)))
+    return sorted(set(re.findall(r"\b(pt_[a-z0-9_]+)\s*\(", text)))
 
 
 def test_header_declares_the_boundary():
@@ -36,6 +36,9 @@ def test_library_exports_every_declared_symbol():
     out = subprocess.run(["nm", "-D", "--defined-only", pt_amd.lib_path()], capture_output=True, text=True).stdout
     for f in declared_functions():
         assert re.search(rf"\bT {f}\b", out), f
+    # ... and nothing else with C linkage under the pt_ prefix: a helper of the C ABI units stays internal
+    exported = sorted(set(re.findall(r"\bT (pt_\w+)$", out, flags=re.M)))
+    assert exported == declared_functions(), sorted(set(exported) ^ set(declared_functions()))
 
 
 def test_kernels_built_for_gfx950():

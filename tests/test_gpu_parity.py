@@ -433,7 +433,7 @@ def test_profile_records_every_launch(packed, ptopts):
 
 
 def test_auto_mode_picks_pipeline_by_size(packed, ptopts):
-    """AUTO (pt_capi.hip launch_opts): the wavefront pipeline at every size on mailbox scenes (the
+    """AUTO (pt_capi_render.hip launch_opts): the wavefront pipeline at every size on mailbox scenes (the
     fused kernel) and on scenes with cooperative big leaves, from 2^19 paths on the others."""
     for k in ENV_KEYS:
         ptopts.unset(k, raising=False)

@@ -52,7 +52,7 @@ TR_KSETS = {
     # >= 128 entries goes to the cooperative turns or the leaf pass
     **{f"lean{k}_np": {**WF, "trav": f"lean{k}".rstrip("1"), "leaf_pool": "0", "big_leaf": "0"} for k in (1, 4, 16, 32)},
 }
-BIG_LEAF = 128  # pt_capi.hip kBigLeafDefault
+BIG_LEAF = 128  # pt_capi_render.hip kBigLeafDefault
 UNPOOLED = ("lean4_np", "lean16_np", "lean32_np")
 # Cases x kernel sets, thinned (the full product ran 992 tests in 27 s, tests/test_gpu_cam.py takes 8 s):
 # FULL cases run every set of their kind; every other case runs AUTO and, in turn through the
@@ -108,7 +108,7 @@ def check_case(s, b, f, kset, opts):
     assert same_bits(acc, racc), f"{b.case.id} {kset} counted render: " + report(acc, racc)
     assert gc == rc, (gc, rc)
     # the instance, from the layout rules
-    if not opts:  # AUTO (pt_capi.hip: the wavefront from one path on for mailbox scenes and big leaves)
+    if not opts:  # AUTO (pt_capi_render.hip: the wavefront from one path on for mailbox scenes and big leaves)
         wave = f["mailbox"] or f["max_leaf"] >= BIG_LEAF
         assert ("k_regen" in prof) == (not wave) and ("k_wf_step" in prof) == f["mailbox"], (f, prof.keys())
         assert ("k_wf_trace" in prof) == (wave and not f["mailbox"]), (f, prof.keys())

@@ -1,6 +1,6 @@
 """CPU model of the region-partitioned queues of the fused kernel (pt_wavefront.hip: k_wf_generate's
 region layout and closed-form counts, k_wf_step_bf's regions; the host's rstride
-and queue slack in pt_capi.hip / pt_kernels.h), step for step.
+and queue slack in pt_capi_render.hip / pt_kernels.h), step for step.
 
 64-path batch j of P paths goes to region j % R at offset (j // R) * 64 + p % 64 of that region;
 region r holds rstride = qcap // R // 64 * 64 entries, qcap = the queue entries of the half (the

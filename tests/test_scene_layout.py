@@ -3,7 +3,7 @@ scripts/scene_layout_harness.cpp).  Most of what it decides — which leaves get
 table, the leaf remainders — changes the kernels' speed and not the image, so the bit-exact GPU suite
 cannot see a slip there.  tests/golden/scene_layout.txt holds the harness's output ("== case", then its
 lines: per array its length, element size and FNV-1a digest, the scalars, the device section plan) as
-build_layout gave it while it stood inside pt_capi.hip; every line must match, no tolerance.  The
+build_layout gave it while it stood inside the C ABI file; every line must match, no tolerance.  The
 malformed inputs are CornellBox's buffers with one edit each; their code and message are recorded the
 same way.  CPU only."""
 import os
