@@ -137,6 +137,8 @@ struct pt_scene {
     // pinned mirror, copied after every query launch on its stream like h_ctl below
     pt::Scratch<char> d_query{&info.device_bytes};
     pt::Scratch<uint32_t> d_qctl;
+    // pt_query_radiance: the blocking call's rays, seeds and accumulator (counted like d_query)
+    pt::Scratch<char> d_radq{&info.device_bytes};
     pt::PinnedWords h_qctl;
     pt::WfStreams ws;  // dual-stream wavefront: aux stream + fork/join events (created with d_wf)
     // pinned mirror of the wavefront control words, copied after every wavefront render on its
@@ -182,6 +184,12 @@ int check_frames(uint32_t frame0, uint32_t nframes, uint32_t stride);
 int shape_view(pt_scene* s, const Opts& o, const FrameParams& fp, int mode, uint64_t paths, SceneView& view);
 // an earlier asynchronous call's watchdog flag, once its mirror copy has landed: reported and cleared
 int take_watchdog(pt_scene* s);
+// the call's LaunchOpts: pt_flavour.h's defaults, the pipeline (AUTO by paths and scene), the options
+LaunchOpts launch_opts(const Opts& o, int mode, uint64_t paths, const SceneView& view);
+// the wavefront's buffers (s->wf) for a call of nframes frames of npix paths each: one batch's queues and
+// radiance — the option wf_paths or the default target, at least two frames when the call has two, halved
+// down to one frame's paths when the device is short of memory, then PT_ERR_NOMEM — and the view's leaf keys
+int prepare_wavefront(pt_scene* s, const Opts& o, const SceneView& view, uint64_t npix, uint32_t nframes);
 int render_impl(pt_scene* s, const float* meta, uint32_t frame0, uint32_t nframes, uint32_t stride, int max_depth,
                 int mode, bool accum, float* d_out, Counters* d_cnt, hipStream_t stream, const pt_window* win = nullptr,
                 const size_t* pitch = nullptr, float* d_m2 = nullptr, const pt_window* rects = nullptr, size_t nrects = 0);

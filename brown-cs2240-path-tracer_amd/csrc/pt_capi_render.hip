@@ -83,7 +83,7 @@ static bool wants_wavefront(const Opts& o, int mode, uint64_t paths, const Scene
 }
 
 // The call's LaunchOpts: pt_flavour.h's defaults, the pipeline, and whatever pt_set_option overrides
-static LaunchOpts launch_opts(const Opts& o, int mode, uint64_t paths, const SceneView& view) {
+LaunchOpts launch_opts(const Opts& o, int mode, uint64_t paths, const SceneView& view) {
     LaunchOpts lo;
     lo.wavefront = wants_wavefront(o, mode, paths, view);
     lo.literal = o.is("kernel", "literal");
@@ -374,6 +374,39 @@ static int upload_rects(pt_scene* s, const RectPlan& plan, const FrameParams& fp
     return PT_OK;
 }
 
+// The wavefront's buffers for a call of nframes frames of npix paths each (a single-frame call: 1): the
+// queues and the radiance of one batch, and the keys of the view's pre-resolved leaves
+int prepare_wavefront(pt_scene* s, const Opts& o, const SceneView& view, uint64_t npix, uint32_t nframes) {
+    // the target in whole pairs of frames (a batch's two parts take whole frames each): 4096^2
+    // holds 4 frames (67 M paths), not 2 of the 3.8 that 64 M would hold
+    const uint64_t target0 = (uint64_t)std::max(1L, o.num("wf_paths", (long)kWfTargetPaths));  // A/B
+    const uint64_t pairs = (target0 + 2 * npix - 1) / (2 * npix) * (2 * npix);
+    const uint64_t target = o.has("wf_paths") || pairs > 0x7fffffffull ? target0 : pairs;
+    // at least two frames per batch when the call has two (images above the target, e.g.
+    // 4096^2): the batch's parts run on their own streams and overlap (+29 % at 4096^2)
+    const uint64_t all = npix * nframes;
+    const uint64_t two = 2 * npix <= 0x7fffffffull ? 2 * npix : npix;
+    // a call that fits the target runs as one batch: its two parts take whole frames each, so
+    // an odd frame count gets one frame of room more (5 frames: 3 + 2, not batches of 4 and 1)
+    const uint64_t all_even = nframes > 1 && (nframes & 1) ? all + npix : all;
+    const uint64_t want = std::max<uint64_t>(std::min<uint64_t>(all, two), std::min<uint64_t>(all_even, target));
+    int rc2 = ensure_wavefront(s, want);
+    // the batch's state (~188 B/path: 12 GB at the 64 M-path target) may not fit beside other
+    // allocations: halve it down to one frame per batch before giving up
+    const uint64_t floor_paths = std::min<uint64_t>(all, npix);
+    for (uint64_t w = want; rc2 == PT_ERR_NOMEM && w > floor_paths;)
+        rc2 = ensure_wavefront(s, w = std::max<uint64_t>(w / 2, floor_paths));
+    if (rc2 != PT_OK) return rc2;
+    rc2 = ensure_rad(s, s->wf.capacity);
+    if (rc2 != PT_OK) return rc2;
+    if (view.npre > 0) {
+        if ((rc2 = ensure_pres(s, view.npre)) != PT_OK) return rc2;
+    } else {
+        s->wf.pres = nullptr;
+    }
+    return PT_OK;
+}
+
 // d_out: the window's first pixel, rows row_pitch pixels apart (win NULL: the whole image); d_m2
 // (nullable, accumulating calls): the second moments, laid out like d_out.  rects (nullable,
 // accumulating calls): the call renders these nrects rectangles of the window instead of all of it
@@ -407,33 +440,7 @@ int render_impl(pt_scene* s, const float* meta, uint32_t frame0, uint32_t nframe
     if (list && (rc = upload_rects(s, plan, fp, !lo.wavefront, stream, rl)) != PT_OK) return rc;
     const RectList* const prl = list ? &rl : nullptr;
     if (lo.wavefront) {
-        // the target in whole pairs of frames (a batch's two parts take whole frames each): 4096^2
-        // holds 4 frames (67 M paths), not 2 of the 3.8 that 64 M would hold
-        const uint64_t target0 = (uint64_t)std::max(1L, o.num("wf_paths", (long)kWfTargetPaths));  // A/B
-        const uint64_t pairs = (target0 + 2 * npix - 1) / (2 * npix) * (2 * npix);
-        const uint64_t target = o.has("wf_paths") || pairs > 0x7fffffffull ? target0 : pairs;
-        // at least two frames per batch when the call has two (images above the target, e.g.
-        // 4096^2): the batch's parts run on their own streams and overlap (+29 % at 4096^2)
-        const uint64_t all = npix * (accum ? nframes : 1);
-        const uint64_t two = 2 * npix <= 0x7fffffffull ? 2 * npix : npix;
-        // a call that fits the target runs as one batch: its two parts take whole frames each, so
-        // an odd frame count gets one frame of room more (5 frames: 3 + 2, not batches of 4 and 1)
-        const uint64_t all_even = accum && nframes > 1 && (nframes & 1) ? all + npix : all;
-        const uint64_t want = std::max<uint64_t>(std::min<uint64_t>(all, two), std::min<uint64_t>(all_even, target));
-        int rc2 = ensure_wavefront(s, want);
-        // the batch's state (~188 B/path: 12 GB at the 64 M-path target) may not fit beside other
-        // allocations: halve it down to one frame per batch before giving up
-        const uint64_t floor_paths = std::min<uint64_t>(all, npix);
-        for (uint64_t w = want; rc2 == PT_ERR_NOMEM && w > floor_paths;)
-            rc2 = ensure_wavefront(s, w = std::max<uint64_t>(w / 2, floor_paths));
-        if (rc2 != PT_OK) return rc2;
-        rc2 = ensure_rad(s, s->wf.capacity);
-        if (rc2 != PT_OK) return rc2;
-        if (view.npre > 0) {
-            if ((rc2 = ensure_pres(s, view.npre)) != PT_OK) return rc2;
-        } else {
-            s->wf.pres = nullptr;
-        }
+        PT_TRY(prepare_wavefront(s, o, view, npix, accum ? nframes : 1));
         HIP_TRY(launch_wavefront(lo, view, fp, s->wf, frame0, nframes, stride, accum, d_cnt != nullptr, d_out, d_cnt,
                                  stream, s->ws, d_m2, prl));
         HIP_TRY(hipMemcpyAsync(s->h_ctl.p, s->wf.ctl, 4 * kMaxParts * WF_CTL_WORDS, hipMemcpyDeviceToHost, stream));

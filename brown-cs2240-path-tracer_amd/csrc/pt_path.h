@@ -129,6 +129,27 @@ __device__ __forceinline__ Ray path_begin(const FrameParams& fp, uint32_t x, uin
     return ray;
 }
 
+// The tail of path_begin for a ray the caller supplies (pt_query_radiance): radiance() entered with
+// that ray and seed_in = s0 — the prologue's seed chain and the zeroed path state, the very statements
+// of path_begin after camera_ray (which stays as it is: its instances' code does not change).
+__device__ __forceinline__ void path_begin_ray(const Ray& ray, uint32_t s0, PathState& ps) {
+    (void)ray;  // the first segment is the ray as given: nothing of the state depends on it
+    ps.seed = hash1u(hash1u(hash1u(s0)));
+    ps.L = mk(0.0f, 0.0f, 0.0f);
+    ps.beta = mk(1.0f, 1.0f, 1.0f);
+    ps.hp = ps.hn = ps.wi = mk(0.0f, 0.0f, 0.0f);
+    ps.depth = 0;
+    ps.mat_id = 0;
+    ps.spec = false;
+}
+
+// A caller's direction is admitted when |d|^2, taken in f32 as fma(dz, dz, fma(dy, dy, dx * dx)), lies
+// within 2^-18 of 1; a NaN fails the comparison.
+__device__ __forceinline__ bool ray_admitted(float dx, float dy, float dz) {
+    const float q = fmaf(dz, dz, fmaf(dy, dy, dx * dx));
+    return fabsf(q - 1.0f) <= 0x1p-18f;
+}
+
 // :124-151 after the extension trace.  Returns true when the path continues; `ray` then
 // holds the shadow ray and ps the shading point.
 __device__ __forceinline__ bool path_after_ext(const SceneView& sc, int rec, float t, Ray& ray, PathState& ps) {

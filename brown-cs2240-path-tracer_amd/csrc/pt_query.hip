@@ -12,6 +12,7 @@
 //       its ray takes the window's next one at the top of the loop, so lanes do not idle while the
 //       wave's slowest ray is traced (refill = 0 keeps them idle until all 64 are done: the A/B).
 //   k_camera_rays   one lane per pixel of the window: the ray camera_ray gives that pixel and salt.
+//   k_camera_seeds  one lane per pixel of the window: the seed camera_ray hands to radiance() there.
 #include <map>
 #include <mutex>
 #include <utility>
@@ -248,6 +249,23 @@ __global__ __launch_bounds__(kMegaBlock) void k_camera_rays(FrameParams fp, uint
 hipError_t launch_camera_rays(const FrameParams& fp, uint32_t t, void* rays, hipStream_t stream) {
     const dim3 grid((fp.win_w + 15) / 16, (fp.win_h + 15) / 16), block(kMegaBlock);
     PT_LAUNCH(KID_CAMERA_RAYS, stream, k_camera_rays, grid, block, 0, stream, fp, t, static_cast<float4*>(rays));
+    return hipGetLastError();
+}
+
+// camera_ray's seed_out, the value pixel_sample hands to radiance(), for the same pixels in the same
+// order as k_camera_rays (the ray itself is dead code here)
+__global__ __launch_bounds__(kMegaBlock) void k_camera_seeds(FrameParams fp, uint32_t t, uint32_t* __restrict__ seeds) {
+    const uint32_t q = blockIdx.x * kMegaBlock + threadIdx.x;
+    if (q >= fp.win_w * fp.win_h) return;
+    const uint32_t j = q / fp.win_w, i = q - j * fp.win_w;
+    uint32_t seed;
+    (void)camera_ray(fp, fp.win_x0 + i, fp.win_y0 + j, t, seed);
+    seeds[q] = seed;
+}
+
+hipError_t launch_camera_seeds(const FrameParams& fp, uint32_t t, uint32_t* seeds, hipStream_t stream) {
+    const dim3 grid((fp.win_w * fp.win_h + kMegaBlock - 1) / kMegaBlock), block(kMegaBlock);
+    PT_LAUNCH(KID_CAMERA_SEEDS, stream, k_camera_seeds, grid, block, 0, stream, fp, t, seeds);
     return hipGetLastError();
 }
 

@@ -251,6 +251,75 @@ __global__ __launch_bounds__(256) void k_wf_generate(FrameParams fp, WfBuffers w
     if (COUNT) flush_counters(c, cnt_out);
 }
 
+// k_wf_generate for a ray list (pt_query_radiance; RayList, pt_kernels.h): launch slot p < P is sample
+// f = p / n of ray i = p - f n, so neighbouring lanes load neighbouring 32-byte rays (two float4 each)
+// and seeds.  Path id p — the radiance index k_wf_accum_rays reads.  The path's seed_in is the ray's seed
+// for sample 0 of the call and hash1u(seed + s * 16787) for its sample s = sample0 + fbase + f >= 1.
+// A ray that is not admitted (ray_admitted) makes no queue entry and counts nothing: the admitted paths
+// are compacted into the queue — one atomicAdd per block on the queue's count, or, with the fused
+// kernel's regions (wb.nreg > 0), one per wave on the count of the region its 64-slot batch goes to, as
+// k_wf_step_bf appends.  The host zeroes those counts before the launch.  A region receives at most the
+// batches k_wf_generate gives it, so it holds them; the order of the entries changes no path's result.
+template <bool COUNT>
+__global__ __launch_bounds__(1024) void k_wf_generate_rays(WfBuffers wb, RayList ql, uint32_t sample0, uint32_t fbase,
+                                                           uint32_t P, Counters* cnt_out) {
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t R = wb.nreg;
+    bool adm = false;
+    Ray r;
+    PathState ps;
+    if (p < P) {
+        const uint32_t f = p / ql.n, i = p - f * ql.n;
+        const float4 a = ql.rays[2 * (size_t)i], b = ql.rays[2 * (size_t)i + 1];
+        adm = ray_admitted(b.x, b.y, b.z);
+        if (adm) {
+            const uint32_t s = sample0 + fbase + f, s0 = ql.seeds[i];
+            r.o = mk(a.x, a.y, a.z);
+            r.d = mk(b.x, b.y, b.z);
+            r.inv = r.d;  // not stored: the trace kernels take 1 / d when they unpack the entry
+            path_begin_ray(r, s == 0 ? s0 : hash1u(s0 + s * 16787u), ps);
+        }
+    }
+    const uint64_t keep = __ballot(adm);
+    uint32_t slot = 0;
+    if (R) {  // the wave's slots are batch p / 64 of k_wf_generate's layout: its region's next entries
+        if (keep) {  // wave-uniform
+            const uint32_t j = __builtin_amdgcn_readfirstlane(p) / 64;
+            const uint32_t rg = (uint32_t)((uint64_t)(j % R) * wb.rqi % R);
+            uint32_t base = 0;
+            if (lane_id() == 0) base = atomicAdd(&wb.rcnt[rg], (uint32_t)__popcll(keep));
+            slot = rg * wb.rstride + __shfl(base, 0, 64) + rank_below(keep);
+        }
+    } else {  // wave counts -> LDS prefix -> one atomicAdd per block (as k_wf_shade compacts)
+        __shared__ uint32_t s_cnt[16];
+        const uint32_t wv = threadIdx.x / 64;
+        if (lane_id() == 0) s_cnt[wv] = (uint32_t)__popcll(keep);
+        __syncthreads();
+        if (threadIdx.x < 64) {
+            const uint32_t n = threadIdx.x < 16 ? s_cnt[threadIdx.x] : 0u;
+            uint32_t incl = n;
+#pragma unroll
+            for (int off = 1; off < 64; off <<= 1) {
+                const uint32_t v = __shfl_up(incl, off, 64);
+                if (lane_id() >= (uint32_t)off) incl += v;
+            }
+            const uint32_t total = __shfl(incl, 63, 64);
+            uint32_t base = 0;
+            if (threadIdx.x == 0 && total) base = atomicAdd(&wb.ctl[WF_COUNT0], total);
+            base = __shfl(base, 0, 64);
+            if (threadIdx.x < 16) s_cnt[threadIdx.x] = base + incl - n;
+        }
+        __syncthreads();
+        slot = s_cnt[wv] + rank_below(keep);
+    }
+    if (adm) store_entry(wb.ext, slot, r, p, ps);
+    if (COUNT) {
+        Counters c = {};
+        if (adm) { c.samples++; c.ext_queries++; }
+        flush_counters(c, cnt_out);
+    }
+}
+
 // Per-wave LDS staging for k_wf_trace: the current window of 32 queued rays and a ring of
 // hit records.  Keeping both in LDS takes every global load and store out of the traversal
 // loop: on gfx9 loads and stores share the wave's in-order vmcnt, so a per-lane global store
@@ -1228,6 +1297,25 @@ __global__ __launch_bounds__(256) void k_wf_accum(const float* __restrict__ rad,
     o[0] = a.x; o[1] = a.y; o[2] = a.z;
 }
 
+// k_wf_accum for a ray list: acc[3 i + c] += clamp(radiance of sample f of ray i), f = 0 .. F - 1 in order;
+// one lane owns ray i for the whole batch (no atomics).  A ray that is not admitted has no path, so its
+// radiance slots hold nothing: the lane takes the generate kernel's test again and leaves the ray's row
+// of acc alone, bit for bit.
+__global__ __launch_bounds__(256) void k_wf_accum_rays(const float* __restrict__ rad, float* __restrict__ acc, RayList ql,
+                                                       uint32_t F) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= ql.n) return;
+    const float4 b = ql.rays[2 * (size_t)i + 1];
+    if (!ray_admitted(b.x, b.y, b.z)) return;
+    float* o = acc + 3 * (size_t)i;
+    f3 a = mk(o[0], o[1], o[2]);
+    for (uint32_t f = 0; f < F; ++f) {
+        const float* r = rad + 3 * ((size_t)f * ql.n + i);
+        a = add_clamped(a, mk(r[0], r[1], r[2]));
+    }
+    o[0] = a.x; o[1] = a.y; o[2] = a.z;
+}
+
 // ---------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------
@@ -1327,9 +1415,11 @@ static SceneView bf_view(const SceneView& sc) {
 template <bool LDS, int TRAV, bool COUNT>
 static hipError_t wf_render_t(const SceneView& sc_in, const FrameParams& fp, const WfBuffers& wb, uint32_t frame0,
                               uint32_t nframes, uint32_t stride, bool accum, float* out, Counters* cnt,
-                              hipStream_t stream, const WfStreams& ws, const LaunchOpts& lo, float* m2, const RectList* rl) {
+                              hipStream_t stream, const WfStreams& ws, const LaunchOpts& lo, float* m2, const RectList* rl,
+                              const RayList* ql) {
     SceneView sc = bf_view<TRAV, COUNT>(sc_in);
-    const uint32_t npix = rl ? rl->npix : fp.win_w * fp.win_h;  // paths per frame: the list's, else the window's
+    // paths per frame: the list's, else the window's (a ray list: its rays, a "frame" being one sample of each)
+    const uint32_t npix = ql ? ql->n : rl ? rl->npix : fp.win_w * fp.win_h;
     // the batch in lo.parts parts on as many streams when a part holds at least a frame: one
     // part's kernel fills the others' launch tails and boundaries (and, with separate trace and
     // shade kernels, a VALU-bound trace runs beside an HBM-bound shade)
@@ -1373,7 +1463,7 @@ static hipError_t wf_render_t(const SceneView& sc_in, const FrameParams& fp, con
     constexpr bool kNarrowOk = flv_fused(TRAV) && LDS && !COUNT;
     const bool narrow = kNarrowOk && sc.bfnode && sc.bfnarrow;
     if constexpr (flv_fused(TRAV)) {  // the camera batches' table (k_wf_camtab), before every part's GEN launch
-        if (lo.fuse_gen && !rl) {
+        if (lo.fuse_gen && !rl && !ql) {
             if (sc.n_tris - sc.mb_base > 64) return hipErrorInvalidValue;  // mailbox scenes: <= 64 entries
             hipLaunchKernelGGL(k_wf_camtab, dim3(1), dim3(64), 0, stream, sc, fp, wb.camtab);
         }
@@ -1419,10 +1509,17 @@ static hipError_t wf_render_t(const SceneView& sc_in, const FrameParams& fp, con
         // behind the first part's first launch, and the parts ran that far apart (a kernel trace of
         // the bench, r06m)
         // (a rectangle list's camera paths come from k_wf_generate's list instance: the fuse_gen = 0 route)
-        const bool fgen = flv_fused(TRAV) && lo.fuse_gen && !rl;
+        // (and a ray list's from k_wf_generate_rays, which appends to the queue's count or its regions' count
+        // slots 0: zeroed here with slot 1, as k_wf_generate would have set them)
+        const bool fgen = flv_fused(TRAV) && lo.fuse_gen && !rl && !ql;
         if (fgen)
             for (int h = 0; h < nh; ++h)
                 HIP_RETURN_IF(hipMemsetAsync(pv[h].w.rcnt + kRegions, 0, kRegions * sizeof(uint32_t), stream));
+        if (ql)
+            for (int h = 0; h < nh; ++h) {
+                HIP_RETURN_IF(hipMemsetAsync(pv[h].w.ctl + WF_COUNT0, 0, 2 * sizeof(uint32_t), stream));
+                if (flv_fused(TRAV)) HIP_RETURN_IF(hipMemsetAsync(pv[h].w.rcnt, 0, 2 * kRegions * sizeof(uint32_t), stream));
+            }
         if (np > 1) {
             HIP_RETURN_IF(hipEventRecord(ws.fork, stream));
             for (int h = 0; h < nh; ++h) HIP_RETURN_IF(hipStreamWaitEvent(pv[h].st, ws.fork, 0));
@@ -1444,7 +1541,10 @@ static hipError_t wf_render_t(const SceneView& sc_in, const FrameParams& fp, con
         }
         for (int h = 0; h < nh && !fgen; ++h) {
             const dim3 ggrid((std::max(pv[h].P, pv[h].w.nreg) + 255) / 256);
-            if (rl)
+            if (ql)
+                PT_LAUNCH(KID_WF_GENERATE, pv[h].st, (k_wf_generate_rays<COUNT>), dim3((pv[h].P + 1023) / 1024), dim3(1024), 0,
+                          pv[h].st, pv[h].w, *ql, frame0, pv[h].fbase, pv[h].P, cnt);
+            else if (rl)
                 PT_LAUNCH(KID_WF_GENERATE, pv[h].st, (k_wf_generate<COUNT, RectList>), ggrid, dim3(256), 0, pv[h].st,
                           fp, pv[h].w, frame0, stride, pv[h].fbase, pv[h].P, !accum, cnt, *rl);
             else
@@ -1532,7 +1632,9 @@ static hipError_t wf_render_t(const SceneView& sc_in, const FrameParams& fp, con
                 HIP_RETURN_IF(hipStreamWaitEvent(stream, ws.join[h], 0));
             }
         }
-        if (rl)
+        if (ql)
+            PT_LAUNCH(KID_WF_ACCUM, stream, k_wf_accum_rays, dim3((npix + 255) / 256), dim3(256), 0, stream, wb.rad, out, *ql, Fb);
+        else if (rl)
             PT_LAUNCH(KID_WF_ACCUM, stream, (k_wf_accum<RectList>), dim3((npix + 255) / 256), dim3(256), 0, stream, wb.rad, out,
                       npix, fp.win_w, fp.row_pitch, Fb, accum, m2, *rl);
         else
@@ -1544,15 +1646,17 @@ static hipError_t wf_render_t(const SceneView& sc_in, const FrameParams& fp, con
 
 hipError_t launch_wavefront(const LaunchOpts& lo, const SceneView& sc, const FrameParams& fp, const WfBuffers& wb,
                             uint32_t frame0, uint32_t nframes, uint32_t stride, bool accum, bool count, float* out,
-                            Counters* cnt, hipStream_t stream, const WfStreams& ws, float* m2, const RectList* rl) {
-    if ((m2 || rl) && !accum) return hipErrorInvalidValue;
+                            Counters* cnt, hipStream_t stream, const WfStreams& ws, float* m2, const RectList* rl,
+                            const RayList* ql) {
+    if ((m2 || rl || ql) && !accum) return hipErrorInvalidValue;
+    if (ql && (m2 || rl || stride != 1 || ql->n == 0)) return hipErrorInvalidValue;
     if (!accum) { nframes = 1; stride = 1; }
     const bool lds = lo.lds && scene_fits_lds(sc);
     // the leaf pass (FLV_PRE) when the scene's table of pre-resolved leaves holds its big leaves
     // (pt_capi.hip shape_view: option leaf_pre, default on) and the buffers exist
     const int trav = select_wavefront(lo, sc.fast_rcp != 0, sc.mailbox != 0, sc.big_leaf > 0, sc.npre > 0 && sc.pre && wb.pres);
     // sc.node_bias <= 0: chosen per instance in wf_render_t
-#define WF_ARGS sc, fp, wb, frame0, nframes, stride, accum, out, cnt, stream, ws, lo, m2, rl
+#define WF_ARGS sc, fp, wb, frame0, nframes, stride, accum, out, cnt, stream, ws, lo, m2, rl, ql
 #define WF(T)                                                                                                        \
     case T:                                                                                                          \
         return lds ? (count ? wf_render_t<true, T, true>(WF_ARGS) : wf_render_t<true, T, false>(WF_ARGS))            \

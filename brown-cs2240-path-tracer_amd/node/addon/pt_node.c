@@ -640,10 +640,10 @@ static napi_value js_render_denoised(napi_env env, napi_callback_info info) {
     return NULL;
 }
 
-/* a new typed array of n elements (Float32Array or Uint8Array) and its storage */
+/* a new typed array of n elements (Float32Array, Uint32Array or Uint8Array) and its storage */
 static napi_value new_typedarray(napi_env env, napi_typedarray_type type, size_t n, void** data) {
     napi_value ab, ta;
-    const size_t bytes = n * (type == napi_float32_array ? 4 : 1);
+    const size_t bytes = n * (type == napi_uint8_array ? 1 : 4);
     if (napi_create_arraybuffer(env, bytes, data, &ab) != napi_ok || napi_create_typedarray(env, type, n, ab, 0, &ta) != napi_ok) {
         if (!pending_exception(env)) napi_throw_error(env, NULL, "could not allocate the result array");
         return NULL;
@@ -679,9 +679,60 @@ static napi_value query_call(napi_env env, napi_callback_info info, int occluded
 static napi_value js_query_hits(napi_env env, napi_callback_info info) { return query_call(env, info, 0); }
 static napi_value js_query_occluded(napi_env env, napi_callback_info info) { return query_call(env, info, 1); }
 
+/* queryRadiance(scene, Float32Array rays[8n], Uint32Array seeds[n], nsamples, maxDepth, rr, directOnly[,
+ * Float32Array accum[3n]]) -> Float32Array[3n]: pt_query_radiance — per ray the clamped radiance of nsamples
+ * full paths, summed (into a copy of accum when given).  Blocking. */
+static napi_value js_query_radiance(napi_env env, napi_callback_info info) {
+    size_t argc = 8;
+    napi_value argv[8];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    float *rays, *acc = NULL;
+    size_t rl, sl = 0, al = 0;
+    uint32_t* seeds = NULL;
+    pt_radiance_params prm;
+    double rr = 0.0;
+    bool direct = false;
+    pt_scene* s = argc >= 7 ? get_scene(env, argv[0]) : NULL;
+    int ok = s && get_f32(env, argv[1], &rays, &rl) && rl % 8 == 0;
+    if (ok) {
+        bool is_ta = false;
+        napi_typedarray_type t;
+        void* p;
+        napi_value ab;
+        size_t off;
+        ok = napi_is_typedarray(env, argv[2], &is_ta) == napi_ok && is_ta &&
+             napi_get_typedarray_info(env, argv[2], &t, &sl, &p, &ab, &off) == napi_ok && t == napi_uint32_array && sl == rl / 8;
+        seeds = (uint32_t*)p;
+    }
+    ok = ok && get_u32(env, argv[3], &prm.nsamples) && get_i32(env, argv[4], &prm.max_depth) &&
+         napi_get_value_double(env, argv[5], &rr) == napi_ok && napi_get_value_bool(env, argv[6], &direct) == napi_ok;
+    if (ok && argc >= 8) {
+        napi_valuetype vt;
+        if (napi_typeof(env, argv[7], &vt) != napi_ok) ok = 0;
+        else if (vt != napi_undefined && vt != napi_null) ok = get_f32(env, argv[7], &acc, &al) && al == rl / 8 * 3;
+    }
+    if (!ok) {
+        if (!pending_exception(env))
+            napi_throw_type_error(env, NULL, "queryRadiance(scene, Float32Array rays[8n], Uint32Array seeds[n], nsamples, maxDepth, "
+                                             "rr, directOnly[, Float32Array accum[3n]])");
+        return NULL;
+    }
+    prm.rr_prob = (float)rr;
+    prm.direct_only = direct ? 1 : 0;
+    const size_t n = rl / 8;
+    void* out = NULL;
+    napi_value res = new_typedarray(env, napi_float32_array, 3 * n, &out);
+    if (!res) return NULL;
+    if (acc) memcpy(out, acc, 3 * n * sizeof(float));  /* a new ArrayBuffer is zeroed */
+    const int rc = pt_query_radiance(s, (const pt_ray*)rays, seeds, n, &prm, (float*)out, NULL);
+    if (rc) return throw_pt(env, rc);
+    return res;
+}
+
 /* cameraRays(scene, meta, frame[, [x0, y0, w, h]]) -> Float32Array[8 w h]: pt_camera_rays, the rays the render
- * traces for the window's pixels in that frame, row-major, tmax = +inf */
-static napi_value js_camera_rays(napi_env env, napi_callback_info info) {
+ * traces for the window's pixels in that frame, row-major, tmax = +inf.
+ * cameraSeeds(same arguments) -> Uint32Array[w h]: pt_camera_seeds, the seeds it hands to radiance() there. */
+static napi_value camera_call(napi_env env, napi_callback_info info, int seeds) {
     size_t argc = 4;
     napi_value argv[4];
     CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
@@ -698,7 +749,9 @@ static napi_value js_camera_rays(napi_env env, napi_callback_info info) {
         else if (vt != napi_undefined && vt != napi_null) ok = has_win = parse_window(env, argv[3], &win);
     }
     if (!ok) {
-        if (!pending_exception(env)) napi_throw_type_error(env, NULL, "cameraRays(scene, Float32Array meta[48], frame[, [x0, y0, w, h]])");
+        if (!pending_exception(env))
+            napi_throw_type_error(env, NULL, seeds ? "cameraSeeds(scene, Float32Array meta[48], frame[, [x0, y0, w, h]])"
+                                                   : "cameraRays(scene, Float32Array meta[48], frame[, [x0, y0, w, h]])");
         return NULL;
     }
     /* the result's size is the window's, so the window is checked against the image (the library's own
@@ -714,12 +767,16 @@ static napi_value js_camera_rays(napi_env env, napi_callback_info info) {
     }
     const double npix = has_win ? (double)win.w * (double)win.h : W * H;
     void* out = NULL;
-    napi_value res = new_typedarray(env, napi_float32_array, 8 * (size_t)npix, &out);
+    napi_value res = seeds ? new_typedarray(env, napi_uint32_array, (size_t)npix, &out)
+                           : new_typedarray(env, napi_float32_array, 8 * (size_t)npix, &out);
     if (!res) return NULL;
-    const int rc = pt_camera_rays(s, meta, has_win ? &win : NULL, frame, (pt_ray*)out);
+    const int rc = seeds ? pt_camera_seeds(s, meta, has_win ? &win : NULL, frame, (uint32_t*)out)
+                         : pt_camera_rays(s, meta, has_win ? &win : NULL, frame, (pt_ray*)out);
     if (rc) return throw_pt(env, rc);
     return res;
 }
+static napi_value js_camera_rays(napi_env env, napi_callback_info info) { return camera_call(env, info, 0); }
+static napi_value js_camera_seeds(napi_env env, napi_callback_info info) { return camera_call(env, info, 1); }
 
 /* tonemap(accum Float32Array, sampleRuns, out Uint8Array[npix*4]) */
 static napi_value js_tonemap(napi_env env, napi_callback_info info) {
@@ -875,6 +932,8 @@ static napi_value init(napi_env env, napi_value exports) {
         {"queryHits", NULL, js_query_hits, NULL, NULL, NULL, napi_default, NULL},
         {"queryOccluded", NULL, js_query_occluded, NULL, NULL, NULL, napi_default, NULL},
         {"cameraRays", NULL, js_camera_rays, NULL, NULL, NULL, napi_default, NULL},
+        {"cameraSeeds", NULL, js_camera_seeds, NULL, NULL, NULL, napi_default, NULL},
+        {"queryRadiance", NULL, js_query_radiance, NULL, NULL, NULL, napi_default, NULL},
         {"frame", NULL, js_frame, NULL, NULL, NULL, napi_enumerable, NULL},
         {"tonemap", NULL, js_tonemap, NULL, NULL, NULL, napi_enumerable, NULL},
         {"profileEnable", NULL, js_profile_enable, NULL, NULL, NULL, napi_enumerable, NULL},

@@ -13,6 +13,17 @@
 //  library's; the whole image only, without --counters, --spp at least 2) [--feature-frames N] (frames of its guide buffers, default 4)
 // [--pick x,y] (print what the frame-0 camera ray of pixel (x, y) hits — point, distance, normal, material —
 //  as one JSON line and render nothing: pt_camera_rays + pt_query_hits)
+// [--projection pinhole|equirect|ortho] (pinhole: the render above, the default.  The other two trace rays made
+//  here through pt_query_radiance, the whole image only, one ray per pixel through its centre (u, v) = ((x + 0.5) / W,
+//  (y + 0.5) / H), with the camera's axes R, U, B = columns 0..2 of cam_to_world (look L = -B) and its position P:
+//    equirect  the full sphere: azimuth phi = (u - 0.5) 2 pi about U from L, elevation th = (0.5 - v) pi;
+//              d = cos th (sin phi R + cos phi L) + sin th U, from P
+//    ortho     d = L from P + (u - 0.5) a h R + (0.5 - v) h U, h = 2 tan(heightangle / 2) |focus - P| (what the pinhole
+//              sees in the plane through the focus), a = W / H
+//  all in doubles, then unitRays' f32 normalisation.  Seeds: pixel index i = x + y W has seed hash1u(hash1u(i * 16787))
+//  for its sample 0 and, the library's rule, hash1u(seed + s * 16787) for sample s of --spp, frame after frame.)
+// [--dump-rays FILE] (with equirect or ortho: the rays, 8 f32 each, then the seeds, one u32 each, as made)
+// [--dump-accum FILE] (with equirect or ortho: the accumulator, 3 f32 per pixel, before the tone map)
 const fs = require('fs');
 const path = require('path');
 const host = require('..');
@@ -53,6 +64,14 @@ async function main(argv) {
         denoise = { iters: +it, featureFrames: +ff };
     }
     if (args.pick !== undefined) return pick(args);
+    const projection = args.projection === undefined ? 'pinhole' : String(args.projection);
+    if (!['pinhole', 'equirect', 'ortho'].includes(projection) ||
+        (projection !== 'pinhole' && (window || rects || denoise || args.counters === '1'))) {
+        console.error(`usage: pt-render.js <scene.ini> --projection pinhole|equirect|ortho (equirect and ortho: the whole image, ` +
+                      `not with --window, --denoise or --counters 1): --projection ${args.projection}`);
+        process.exit(2);
+    }
+    if (projection !== 'pinhole') return project(args, projection);
     const t0 = Date.now();
     const s = host.load_scene_from_ini(args._[0], { web_root: args.web_root, quiet: true });
     if (args.spp) s.scene_description.Settings.samplesPerPixel = parseInt(args.spp);
@@ -69,6 +88,64 @@ async function main(argv) {
     const samples = (rects ? rects.reduce((a, w) => a + w[2] * w[3], 0) : W * H) * r.sample_runs;
     console.log(JSON.stringify({ output: out, width: W, height: H, window, rects, spp: r.sample_runs, scene_ms: t1 - t0,
         denoise, render_ms: t2 - t1, msamples_per_s: samples / ((t2 - t1) / 1000) / 1e6, counters: r.counters }));
+}
+// hash.wgsl's hash1u in u32 arithmetic
+function hash1u(n) {
+    n = ((n << 13) ^ n) >>> 0;
+    return ((Math.imul(n, (Math.imul(Math.imul(n, n), 15731) + 789221) | 0) + 1376312589) >>> 0) & 0x7fffffff;
+}
+// --projection equirect|ortho: the rays and seeds the header documents, through queryRadiance
+function project(args, projection) {
+    const t0 = Date.now();
+    const s = host.load_scene_from_ini(args._[0], { web_root: args.web_root, quiet: true });
+    if (args.spp) s.scene_description.Settings.samplesPerPixel = parseInt(args.spp);
+    const [W, H] = s.screenDimension;
+    const spp = s.scene_description.Settings.samplesPerPixel;
+    const meta = host.make_meta(s.screenDimension, s.camera_data, s.scene_description, 0);
+    const M = meta.subarray(28, 44), P = [meta[4], meta[5], meta[6]];
+    const R = [M[0], M[1], M[2]], U = [M[4], M[5], M[6]], L = [-M[8], -M[9], -M[10]];
+    const focus = s.camera_data.focus.toArray(), pos = s.camera_data.pos.toArray();
+    const dist = Math.hypot(focus[0] - pos[0], focus[1] - pos[1], focus[2] - pos[2]);
+    const h = 2 * Math.tan(s.camera_data.heightangle * Math.PI / 360) * dist, a = W / H;
+    const o = new Float64Array(3 * W * H), d = new Float64Array(3 * W * H), seeds = new Uint32Array(W * H);
+    for (let y = 0; y < H; ++y) {
+        for (let x = 0; x < W; ++x) {
+            const i = x + y * W, u = (x + 0.5) / W, v = (y + 0.5) / H;
+            for (let c = 0; c < 3; ++c) {
+                if (projection === 'equirect') {
+                    const phi = (u - 0.5) * 2 * Math.PI, th = (0.5 - v) * Math.PI;
+                    o[3 * i + c] = P[c];
+                    d[3 * i + c] = Math.cos(th) * (Math.sin(phi) * R[c] + Math.cos(phi) * L[c]) + Math.sin(th) * U[c];
+                } else {
+                    o[3 * i + c] = P[c] + (u - 0.5) * a * h * R[c] + (0.5 - v) * h * U[c];
+                    d[3 * i + c] = L[c];
+                }
+            }
+            seeds[i] = hash1u(hash1u(Math.imul(i, 16787) >>> 0));
+        }
+    }
+    const rays = host.unitRays(o, d);
+    const t1 = Date.now();
+    const pt = host.native();
+    const scene = pt.sceneCreate(s.primitive_data[0].triangle_data, s.primitive_data[0].bvh_data, parseInt(args.device || '0'));
+    let accum;
+    try {
+        if (args.vertex_normals === '1') pt.sceneSetVertexNormals(scene, true);
+        accum = host.queryRadiance(scene, rays, seeds, { nsamples: spp, maxDepth: parseInt(args.max_depth || '16'), rr: meta[45], directOnly: meta[46] > 0 });
+    } finally {
+        pt.sceneDestroy(scene);
+    }
+    const t2 = Date.now();
+    const rgba = new Uint8Array(W * H * 4);
+    pt.tonemap(accum, spp, rgba);
+    const out = path.join(args.out_root || '.', s.scene_description.IO.output || 'out.png');
+    fs.mkdirSync(path.dirname(out), { recursive: true });
+    fs.writeFileSync(out, host.encode_png(rgba, W, H));
+    const bytes = (ta) => Buffer.from(ta.buffer, ta.byteOffset, ta.byteLength);
+    if (args.dump_rays) fs.writeFileSync(args.dump_rays, Buffer.concat([bytes(rays), bytes(seeds)]));
+    if (args.dump_accum) fs.writeFileSync(args.dump_accum, bytes(accum));
+    console.log(JSON.stringify({ output: out, width: W, height: H, projection, spp, scene_ms: t1 - t0, render_ms: t2 - t1,
+        msamples_per_s: W * H * spp / ((t2 - t1) / 1000) / 1e6 }));
 }
 // --pick x,y: what the camera ray of pixel (x, y), frame 0, hits (pt_camera_rays + pt_query_hits), as one
 // JSON line; nothing is rendered or written.  `bits`: the eight 32-bit words of the hit record.

@@ -24,6 +24,32 @@ const addon = require('./lib/addon');
 const queryHits = (scene, rays) => addon.load().queryHits(scene, rays);
 const queryOccluded = (scene, rays) => addon.load().queryOccluded(scene, rays);
 const cameraRays = (scene, meta, frame, window) => addon.load().cameraRays(scene, meta, frame, check_window(window));
+// Radiance queries: full paths from the caller's rays (unit directions: unitRays makes them).
+//   queryRadiance(scene, rays, seeds, { nsamples = 1, maxDepth = 8, rr = 0.9, directOnly = false, accum }) ->
+//       Float32Array[3n]: per ray the clamped radiance of nsamples paths, summed (onto a copy of accum if given);
+//       seeds: Uint32Array[n], the seed of sample 0 (sample s >= 1 takes hash1u(seed + s * 16787)); a ray whose
+//       |d|^2 is further than 2^-18 from 1 is not traced and adds nothing
+//   cameraSeeds(scene, meta, frame, window?) -> Uint32Array[w h]: the seeds the render hands to its paths there;
+//       with cameraRays and queryRadiance({ nsamples: 1 }) they repeat that frame of the render
+//   unitRays(o, d) -> Float32Array[8n]: rays with d normalised in f32 (o, d: arrays of 3n numbers)
+const queryRadiance = (scene, rays, seeds, params = {}) => {
+    const { nsamples = 1, maxDepth = 8, rr = 0.9, directOnly = false, accum = null } = params;
+    return addon.load().queryRadiance(scene, rays, seeds, nsamples, maxDepth, rr, !!directOnly, accum);
+};
+const cameraSeeds = (scene, meta, frame, window) => addon.load().cameraSeeds(scene, meta, frame, check_window(window));
+const unitRays = (o, d) => {
+    const n = Math.floor(d.length / 3), rays = new Float32Array(8 * n), v = new Float32Array(3), f = Math.fround;
+    for (let i = 0; i < n; ++i) {
+        // scaled by a power of two so that no square overflows, then the reference's normalize in f32: the
+        // squares and sums are taken in doubles and rounded to f32 after each step, as one fused multiply-add is
+        const m = Math.max(Math.abs(d[3 * i]), Math.abs(d[3 * i + 1]), Math.abs(d[3 * i + 2]));
+        const k = m > 0 && isFinite(m) ? Math.pow(2, -Math.floor(Math.log2(m))) : 1;
+        for (let c = 0; c < 3; ++c) v[c] = d[3 * i + c] * k;
+        const len = f(Math.sqrt(f(v[2] * v[2] + f(v[1] * v[1] + f(v[0] * v[0])))));
+        rays.set([o[3 * i], o[3 * i + 1], o[3 * i + 2], Infinity, f(v[0] / len), f(v[1] / len), f(v[2] / len), 0], 8 * i);
+    }
+    return rays;
+};
 
 module.exports = {
     parse_ini_file, ini_file_to_ini_scene, parse_obj, BVH, pack_scene_object_group, pack_bvh,
@@ -33,5 +59,5 @@ module.exports = {
     screen_dimension: scene.screen_dimension, load_scene_from_ini: scene.load_scene_from_ini,
     load_scene_xml_file: scene.load_scene_xml_file,
     programEntry, make_meta, check_window, check_rects, MODE, encode_png, native: addon.load,
-    queryHits, queryOccluded, cameraRays,
+    queryHits, queryOccluded, cameraRays, queryRadiance, cameraSeeds, unitRays,
 };

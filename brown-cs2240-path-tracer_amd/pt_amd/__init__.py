@@ -22,6 +22,7 @@ from ._lib import (  # noqa: F401
     Hit,
     PtError,
     RAY_DTYPE,
+    RadianceParams,
     Ray,
     Scene,
     SceneInfo,
@@ -51,5 +52,6 @@ from ._lib import (  # noqa: F401
     source_hash,
     tile_rects,
     tonemap,
+    unit_rays,
 )
 from .host import PackedScene, load_scene, program_entry  # noqa: F401

@@ -13,7 +13,7 @@ ABI_VERSION = 3  # include/pt_hip.h PT_ABI_VERSION
 _CSRC = os.path.join(_PKG_ROOT, "csrc")
 # csrc/Makefile BUILD_SRCS: the sources whose SHA-256 the library carries as pt_build_id()
 _BUILD_SRCS = ["pt_kernels.hip", "pt_wavefront.hip", "pt_leafpass.hip", "pt_image.hip", "pt_features.hip", "pt_denoise.hip", "pt_query.hip", "pt_capi.hip", "pt_capi_render.hip",
-               "pt_capi_adaptive.hip", "pt_capi_denoise.hip", "pt_capi_query.hip", "pt_capi_selftest.hip",
+               "pt_capi_adaptive.hip", "pt_capi_denoise.hip", "pt_capi_query.hip", "pt_capi_radiance.hip", "pt_capi_selftest.hip",
                "pt_capi_multi.hip", "pt_capi_internal.h", "pt_math.h", "pt_flavour.h", "pt_layout.h",
                "pt_device.h", "pt_path.h", "pt_kernels.h", "../../include/pt_hip.h", "pt_bvh.cpp", "pt_leafbvh.h",
                "pt_leafbvh.cpp", "pt_leafskip.cpp", "pt_scene_layout.h", "pt_scene_layout.cpp", "pt_rect_plan.h",
@@ -47,6 +47,12 @@ class SceneInfo(ctypes.Structure):
 
     def as_dict(self):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+class RadianceParams(ctypes.Structure):
+    """pt_radiance_params."""
+    _fields_ = [("rr_prob", ctypes.c_float), ("direct_only", ctypes.c_int32), ("max_depth", ctypes.c_int32),
+                ("nsamples", ctypes.c_uint32)]
 
 
 class Window(ctypes.Structure):
@@ -216,6 +222,54 @@ def _rays(rays) -> np.ndarray:
     return a.reshape(-1, 8)
 
 
+def _fma32(a, b, c):
+    """fmaf(a, b, c) for f32 arrays, correctly rounded: the product is exact in f64; the sum is taken in f64
+    with its rounding error (TwoSum), which decides the one case where rounding f64 -> f32 would round
+    twice — an f64 sum that sits exactly half way between two f32 values."""
+    p = a.astype(np.float64) * b.astype(np.float64)
+    c64 = c.astype(np.float64)
+    with np.errstate(over="ignore", invalid="ignore"):
+        s = p + c64
+        bb = s - p
+        err = (p - (s - bb)) + (c64 - bb)
+        r = s.astype(np.float32)
+        fin = np.isfinite(s) & np.isfinite(r) & (err != 0.0)
+        other = np.where(err > 0.0, np.nextafter(r, np.float32(np.inf)), np.nextafter(r, np.float32(-np.inf)))
+        # r was a tie broken the wrong way when s is the midpoint of r and its neighbour on err's side
+        tie = fin & np.isfinite(other) & ((r.astype(np.float64) + other.astype(np.float64)) * 0.5 == s) & \
+            (np.sign(s - r.astype(np.float64)) == np.sign(err))
+    return np.where(tie, other, r).astype(np.float32)
+
+
+def unit_rays(o, d) -> np.ndarray:
+    """[n, 8] f32 rays for query_radiance from origins o and directions d (both [n, 3], any length):
+    tmax = +inf, reserved = 0, and d normalised in f32 with the reference's operations — d / sqrt(fma(dz,
+    dz, fma(dy, dy, dx * dx))) — after a scaling by the power of two that brings the largest
+    component into [0.5, 1) (exact but for components 2^-100 below it), so that no square overflows and the
+    sum does not underflow.  The result of a
+    finite non-zero direction is always admitted (|d|^2 within 2^-18 of 1); a zero or non-finite
+    direction gives a ray that is not (NaN or zero direction)."""
+    o32 = np.ascontiguousarray(o, np.float32).reshape(-1, 3)
+    d32 = np.ascontiguousarray(d, np.float32).reshape(-1, 3)
+    if o32.shape != d32.shape:
+        raise PtError(-1, f"o and d must hold as many vectors ({o32.shape[0]} and {d32.shape[0]})")
+    with np.errstate(all="ignore"):
+        m = np.max(np.abs(d32), axis=1)
+        _, e = np.frexp(np.where(np.isfinite(m) & (m > 0), m, np.float32(1.0)))
+        # two exact steps: one power of two of up to 2^149 is not an f32
+        h = e // 2
+        v = np.ldexp(np.ldexp(d32, -h[:, None]), -(e - h)[:, None]).astype(np.float32)
+        x, y, z = v[:, 0], v[:, 1], v[:, 2]
+        q = _fma32(z, z, _fma32(y, y, (x * x).astype(np.float32)))
+        ln = np.sqrt(q, dtype=np.float32)
+        u = (v / ln[:, None]).astype(np.float32)
+    rays = np.zeros((o32.shape[0], 8), np.float32)
+    rays[:, 0:3] = o32
+    rays[:, 3] = np.inf
+    rays[:, 4:7] = u
+    return rays
+
+
 def _extent(meta, win):
     """(w, h) of a call's result: the window's, or the image's of meta[0..1]."""
     return (int(win.w), int(win.h)) if win is not None else (int(meta[0]), int(meta[1]))
@@ -311,6 +365,12 @@ def load_library():
     L.pt_query_occluded_async.argtypes = [p, p, sz, p, p, p]
     L.pt_camera_rays.argtypes = [p, p, wp, u32, p]
     L.pt_camera_rays_async.argtypes = [p, p, wp, u32, p, p]
+    L.pt_query_radiance.argtypes = [p, p, p, sz, ctypes.POINTER(RadianceParams), p, p]
+    L.pt_query_radiance_async.argtypes = [p, p, p, sz, ctypes.POINTER(RadianceParams), p, p, p]
+    L.pt_camera_seeds.argtypes = [p, p, wp, u32, p]
+    L.pt_camera_seeds_async.argtypes = [p, p, wp, u32, p, p]
+    for fn in ("pt_query_radiance", "pt_query_radiance_async", "pt_camera_seeds", "pt_camera_seeds_async"):
+        getattr(L, fn).restype = i
     L.pt_denoise_defaults.argtypes = [dpp]
     L.pt_denoise_defaults.restype = None
     L.pt_denoise.argtypes = [p, p, p, u32, u32, u32, u32, p, p, p, u32, dpp, p, p]
@@ -804,6 +864,60 @@ class Scene:
         _check(self._lib.pt_camera_rays_async(self._h, _ptr(meta), ctypes.byref(win) if win is not None else None,
                                               _uint(frame, "frame"), ctypes.c_void_p(d_rays_ptr or None),
                                               ctypes.c_void_p(stream_ptr or None)))
+
+    def query_radiance(self, rays, seeds, nsamples: int = 1, max_depth: int = 8, rr: float = 0.9, direct_only: bool = False,
+                       out=None, counters: bool = False):
+        """pt_query_radiance: nsamples full paths from every ray (rays: [n, 8] f32 as for query_hits, unit
+        directions — see unit_rays; seeds: [n] uint32, the seed of sample 0), clamped and added per ray.
+        Returns [n, 3] f32: the sums, added to `out` ([n, 3] f32, left untouched) if given; and the
+        counters if requested.  A ray whose direction is not admitted (|d|^2 further than 2^-18 from 1)
+        is not traced and adds nothing."""
+        r = _rays(rays)
+        sd = np.ascontiguousarray(seeds, np.uint32).reshape(-1)
+        n = r.shape[0]
+        if sd.shape[0] != n:
+            raise PtError(-1, f"seeds must hold one uint32 per ray ({n}), not {sd.shape[0]}")
+        if out is None:
+            acc = np.zeros((n, 3), np.float32)
+        else:
+            acc = np.array(out, np.float32, copy=True, order="C")
+            if acc.shape != (n, 3):
+                raise PtError(-1, f"out must be [n, 3] f32 with n = {n}, not {acc.shape}")
+        prm = RadianceParams(float(rr), 1 if direct_only else 0, int(max_depth), _uint(nsamples, "nsamples"))
+        c = Counters()
+        _check(self._lib.pt_query_radiance(self._h, _ptr(r), _ptr(sd), n, ctypes.byref(prm), _ptr(acc),
+                                           ctypes.byref(c) if counters else None))
+        return (acc, c.as_dict()) if counters else acc
+
+    def query_radiance_async(self, d_rays_ptr: int, d_seeds_ptr: int, n: int, d_accum_ptr: int, nsamples: int = 1,
+                             max_depth: int = 8, rr: float = 0.9, direct_only: bool = False, stream_ptr: int = 0,
+                             d_counters_ptr: int = 0):
+        """pt_query_radiance_async: n pt_ray records (16-byte aligned), n uint32 seeds and the [n, 3] f32
+        accumulator (in/out) in device memory, asynchronous on the stream."""
+        prm = RadianceParams(float(rr), 1 if direct_only else 0, int(max_depth), _uint(nsamples, "nsamples"))
+        _check(self._lib.pt_query_radiance_async(self._h, ctypes.c_void_p(d_rays_ptr or None),
+                                                 ctypes.c_void_p(d_seeds_ptr or None), n, ctypes.byref(prm),
+                                                 ctypes.c_void_p(d_accum_ptr or None),
+                                                 ctypes.c_void_p(d_counters_ptr or None), ctypes.c_void_p(stream_ptr or None)))
+
+    def camera_seeds(self, meta, window=None, frame: int = 0) -> np.ndarray:
+        """pt_camera_seeds: [h, w] uint32, the seed the render hands to radiance() for the window's pixels
+        in `frame` — with camera_rays, the inputs with which query_radiance(nsamples=1) repeats that frame."""
+        meta = _f32(meta)
+        win = _window(window)
+        W, H = _extent(meta, win)
+        out = np.zeros((H, W), np.uint32)
+        _check(self._lib.pt_camera_seeds(self._h, _ptr(meta), ctypes.byref(win) if win is not None else None,
+                                         _uint(frame, "frame"), _ptr(out)))
+        return out
+
+    def camera_seeds_async(self, meta, frame: int, d_seeds_ptr: int, stream_ptr: int = 0, window=None):
+        """pt_camera_seeds_async: the window's w * h uint32 seeds to d_seeds_ptr (4-byte aligned)."""
+        meta = _f32(meta)
+        win = _window(window)
+        _check(self._lib.pt_camera_seeds_async(self._h, _ptr(meta), ctypes.byref(win) if win is not None else None,
+                                               _uint(frame, "frame"), ctypes.c_void_p(d_seeds_ptr or None),
+                                               ctypes.c_void_p(stream_ptr or None)))
 
     def denoise(self, accum, m2, geo, alb, feature_frames: int, frames, tile=None, params=None):
         """pt_denoise: the variance-guided a-trous filter over the host accumulators accum, m2 [h, w, 3]

@@ -383,6 +383,53 @@ int pt_camera_rays(pt_scene* scene, const float meta[48], const pt_window* win, 
 int pt_camera_rays_async(pt_scene* scene, const float meta[48], const pt_window* win, uint32_t frame, pt_ray* d_rays,
                          void* stream);
 
+/* Radiance queries: full paths from rays the caller supplies — how bright is it along this ray.  For
+ * ray i and sample s, L(i, s) is the reference's radiance(ray, seed) (program-raymarch.wgsl:104-303),
+ * bit for bit, whatever kernel, batch size or option computes it, called with
+ *   ray.p = (o, 1), ray.d = (d, 0), d_inv = 1 / d per component by IEEE division;
+ *   rr_prob, direct_only != 0 and max_depth from the params;
+ *   seed_in = (int32)seeds[i] for s = 0, and (int32)hash1u(seeds[i] + s * 16787u) (u32 wrap) for s >= 1.
+ * tmax and reserved of the ray are ignored.  pt_scene_set_vertex_normals is honoured.
+ *   accum[3 i + c] += (L_c >= 0 ? L_c : 0)   for s = 0 .. nsamples - 1, in that order
+ * — the render's rule, so calls compose as renders of frame ranges do; the caller divides by its total
+ * sample count.  (Sample s >= 1 of a call is NOT sample 0 of a call with other seeds unless the caller
+ * derives them by the rule above.)
+ * Directions must be unit: the kernels are the render's, proved for the directions a render makes.  A
+ * ray is ADMITTED iff q = fmaf(d.z, d.z, fmaf(d.y, d.y, d.x * d.x)) in f32 satisfies |q - 1| <= 2^-18
+ * (a NaN q fails) — wider than any f32 normalisation leaves.  A ray that is not admitted
+ * is never traced: it contributes exactly nothing — its three accumulator words keep their bits — and
+ * adds to no counter.
+ * Counters (nullable, added to): samples += admitted rays * nsamples; ext_queries, shadow_queries, nodes,
+ * tri_tests and box_tests the paths' sums, with the render's exception (a cooperative big-leaf turn counts
+ * by wave).
+ * n = 0 or nsamples = 0: PT_OK, nothing is touched.  PT_ERR_INVALID: params NULL; n > 2^26 (one sample of
+ * every ray must fit a wavefront batch); max_depth < 0 or > 1024 (the render's limit; -1 is NOT "default"
+ * here); a null pointer with n > 0; and, in the _async form, d_rays not 16-byte aligned or d_seeds /
+ * d_accum not 4-byte aligned.  rr_prob is taken as the render takes meta[45]: unchecked, a NaN included
+ * (roulette then never ends a path and the throughput becomes NaN, as in the reference).
+ * The call always runs the wavefront pipeline, in batches of whole samples of all n rays: option wf_paths
+ * or the default target, never fewer than min(nsamples, 2) samples per batch while memory allows, halved
+ * down to one sample per batch when the device is short of memory, then PT_ERR_NOMEM.  Options as for a
+ * render, except kernel=mega|literal, regen and fuse_gen, which do not apply, and leaf_pre, whose default
+ * (a probe from the render's camera) is off here: leaf_pre=1 turns the leaf pass on.
+ * The blocking form copies rays, seeds and accum through scene-owned scratch (counted in device_bytes
+ * while held) on the scene's own stream; the _async form takes device pointers.  Device-side failures and
+ * the watchdog surface as in pt_render_async / pt_scene_check. */
+typedef struct { float rr_prob; int32_t direct_only; int32_t max_depth; uint32_t nsamples; } pt_radiance_params;
+int pt_query_radiance(pt_scene* scene, const pt_ray* rays, const uint32_t* seeds, size_t n,
+                      const pt_radiance_params* params, float* accum, pt_counters* counters);
+int pt_query_radiance_async(pt_scene* scene, const pt_ray* d_rays, const uint32_t* d_seeds, size_t n,
+                            const pt_radiance_params* params, float* d_accum, pt_counters* d_counters, void* stream);
+
+/* The radiance seeds of a window, laid out as pt_camera_rays lays out its rays and under its argument
+ * rules: seeds[(y - y0) * w + (x - x0)] is the value the reference's main() hands to radiance() for pixel
+ * (x, y) in frame `frame`.  So pt_camera_rays + pt_camera_seeds + pt_query_radiance(nsamples = 1, the
+ * meta's rr_prob and direct_only) into a zeroed buffer equals pt_frame_window with negative components
+ * clamped to 0, bit for bit.  d_seeds: device memory, 4-byte aligned. */
+int pt_camera_seeds(pt_scene* scene, const float meta[48], const pt_window* win, uint32_t frame, uint32_t* seeds);
+int pt_camera_seeds_async(pt_scene* scene, const float meta[48], const pt_window* win, uint32_t frame, uint32_t* d_seeds,
+                          void* stream);
+
 /* Completion check of the asynchronous calls: waits for every render of the scene to finish
  * (blocking) and reports a device-side failure of any of them — a wavefront traversal wave that
  * gave up after its watchdog limit leaves a flag instead of hanging, and the accumulators of
