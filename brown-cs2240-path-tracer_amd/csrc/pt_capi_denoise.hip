@@ -43,7 +43,9 @@ static int features_impl(pt_scene* s, const float* meta, const pt_window* win, c
     SceneView view;
     if ((rc = shape_view(s, Opts{}, fp, PT_MODE_MEGAKERNEL, (uint64_t)fp.win_w * fp.win_h * nframes, view)) != PT_OK) return rc;
     if ((rc = take_watchdog(s)) != PT_OK) return rc;  // an earlier asynchronous render failed
-    HIP_TRY(launch_features(view, fp, frame0, nframes, stride, d_cnt != nullptr, d_geo, d_alb, d_cnt, stream));
+    LensCam lens;  // pt_scene_set_camera: the guides follow the model's rays
+    HIP_TRY(launch_features(view, fp, frame0, nframes, stride, d_cnt != nullptr, d_geo, d_alb, d_cnt, stream,
+                            scene_camera(s, lens)));
     return PT_OK;
 }
 

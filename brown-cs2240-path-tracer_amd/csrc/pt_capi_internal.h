@@ -165,6 +165,7 @@ struct pt_scene {
     std::vector<int32_t> leaf_sizes;
     const pt::PreLeaf* d_pre = nullptr;
     pt::Scratch<uint64_t> d_pres;
+    pt_camera cam{};  // pt_scene_set_camera, as given after validation (model 0: the pinhole)
 };
 
 namespace pt {
@@ -193,6 +194,10 @@ int prepare_wavefront(pt_scene* s, const Opts& o, const SceneView& view, uint64_
 int render_impl(pt_scene* s, const float* meta, uint32_t frame0, uint32_t nframes, uint32_t stride, int max_depth,
                 int mode, bool accum, float* d_out, Counters* d_cnt, hipStream_t stream, const pt_window* win = nullptr,
                 const size_t* pitch = nullptr, float* d_m2 = nullptr, const pt_window* rects = nullptr, size_t nrects = 0);
+// pt_capi_camera.hip
+// the scene's camera as a call's launches take it, read once per call: lc filled and returned for a lens
+// model, nullptr for the pinhole (the call then launches the pinhole's own kernels)
+const LensCam* scene_camera(const pt_scene* s, LensCam& lc);
 // pt_capi_adaptive.hip
 // the tile grid of the noise, mean and denoise calls, checked (host only)
 int make_grid(uint32_t w, uint32_t h, size_t row_pitch, uint32_t tile_w, uint32_t tile_h, TileGrid& g);

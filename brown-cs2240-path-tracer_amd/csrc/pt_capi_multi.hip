@@ -132,6 +132,9 @@ extern "C" int pt_render_multi(pt_scene* const* scenes, int n, const float meta[
         for (int h = 0; h < g; ++h)
             if (!scenes[g] || scenes[g] == scenes[h]) return fail(PT_ERR_INVALID, "null or repeated scene");
     if (!scenes[0]) return fail(PT_ERR_INVALID, "null scene");
+    for (int g = 1; g < n; ++g)  // one image: one camera model (pt_scene_set_camera)
+        if (std::memcmp(&scenes[g]->cam, &scenes[0]->cam, sizeof(pt_camera)) != 0)
+            return fail(PT_ERR_INVALID, "the scenes' cameras (pt_scene_set_camera) differ");
     const Opts o = opts_snapshot();
     // one device is pt_render itself — unless option reduce=rccl asks for the RCCL branch anyway
     // (a one-rank communicator: how a one-GPU machine runs that code, tests/test_gpu_multi.py)

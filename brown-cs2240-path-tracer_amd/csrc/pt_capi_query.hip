@@ -113,7 +113,8 @@ int pt_camera_rays_async(pt_scene* s, const float meta[48], const pt_window* win
     if (rc != PT_OK) return rc;
     HIP_TRY(hipSetDevice(s->device));
     ProfScope prof_scope(s);
-    HIP_TRY(launch_camera_rays(fp, (uint32_t)(float)frame, d_rays, static_cast<hipStream_t>(stream)));
+    LensCam lens;  // pt_scene_set_camera: the model's rays
+    HIP_TRY(launch_camera_rays(fp, (uint32_t)(float)frame, d_rays, static_cast<hipStream_t>(stream), scene_camera(s, lens)));
     return PT_OK;
 }
 

@@ -432,9 +432,19 @@ int render_impl(pt_scene* s, const float* meta, uint32_t frame0, uint32_t nframe
     ProfScope prof_scope(s);
     const Opts o = opts_snapshot();
     const uint64_t paths = npix * (accum ? nframes : 1);
+    // a lens camera (pt_scene_set_camera): the wavefront pipeline with camera paths from the generate
+    // kernel, whatever the mode and the options kernel, fuse_gen and regen say — as a ray list's
+    // (pt_query_radiance); nothing else of the call changes
+    LensCam lens;
+    const LensCam* const cam = scene_camera(s, lens);
+    if (cam) mode = PT_MODE_WAVEFRONT;
     SceneView view;
     if ((rc = shape_view(s, o, fp, mode, paths, view)) != PT_OK) return rc;
-    const LaunchOpts lo = launch_opts(o, mode, paths, view);
+    LaunchOpts lo = launch_opts(o, mode, paths, view);
+    if (cam) {
+        lo.wavefront = true;
+        lo.literal = false;
+    }
     if ((rc = take_watchdog(s)) != PT_OK) return rc;  // an earlier asynchronous render failed
     RectList rl{};
     if (list && (rc = upload_rects(s, plan, fp, !lo.wavefront, stream, rl)) != PT_OK) return rc;
@@ -442,7 +452,7 @@ int render_impl(pt_scene* s, const float* meta, uint32_t frame0, uint32_t nframe
     if (lo.wavefront) {
         PT_TRY(prepare_wavefront(s, o, view, npix, accum ? nframes : 1));
         HIP_TRY(launch_wavefront(lo, view, fp, s->wf, frame0, nframes, stride, accum, d_cnt != nullptr, d_out, d_cnt,
-                                 stream, s->ws, d_m2, prl));
+                                 stream, s->ws, d_m2, prl, nullptr, cam));
         HIP_TRY(hipMemcpyAsync(s->h_ctl.p, s->wf.ctl, 4 * kMaxParts * WF_CTL_WORDS, hipMemcpyDeviceToHost, stream));
         return PT_OK;
     }

@@ -1288,6 +1288,76 @@ __device__ __forceinline__ Ray camera_ray(const FrameParams& fp, uint32_t x, uin
     return r;
 }
 
+// The lens cameras (pt_hip.h pt_camera): camera_ray's prologue — seed chain, jitter,
+// norm_x / norm_y, vx / vy, radiance seed — statement for statement, then the model's ray, every
+// operation f32 and rounded once, FMAs exactly where written:
+//   X(c)  cam_to_world applied to the point c, camera_ray's own chain
+//   N3(v) v / |v| with |v| = sqrt(fma(z, z, fma(y, y, x * x)))
+//   THIN_LENS  a point of the lens disc (radius lens_radius, in the camera's xy plane through M's
+//              translation) towards the pinhole ray's point on the plane of focus at focus_distance
+//   ORTHO      parallel rays along -M's third column from the pinhole's extent at focus_distance
+//   EQUIRECT   longitude norm_x * 2 pi, latitude norm_y * pi about the camera's axes, from cam[]
+// seed_out does not depend on the model.  The direction is not tested here (ray_admitted, pt_path.h).
+template <uint32_t MODEL>
+__device__ __forceinline__ Ray camera_ray_model(const FrameParams& fp, const LensCam& lc, uint32_t x, uint32_t y, uint32_t t,
+                                                uint32_t& seed_out) {
+    static_assert(MODEL == CAM_THIN_LENS || MODEL == CAM_ORTHO || MODEL == CAM_EQUIRECT, "a lens model");
+    uint32_t index = x + y * fp.width;
+    uint32_t ts = index * 16787u + t;
+    ts = hash1u(ts);
+    ts = hash1u(ts);
+    float jx, jy;
+    hash2(ts, jx, jy);
+    float gx = (float)x + (jx - 0.5f), gy = (float)y + (jy - 0.5f);
+    float norm_x = fmaf(gx + 0.5f, fp.inv_w, -0.5f);
+    float norm_y = fmaf(((fp.H - 1.0f) - gy) + 0.5f, fp.inv_h, -0.5f);
+    ts = hash1u(ts);
+    const float* M = fp.M;
+    auto X = [M](f3 c) {
+        return mk(fmaf(M[12], 1.0f, fmaf(M[8], c.z, fmaf(M[4], c.y, M[0] * c.x))),
+                  fmaf(M[13], 1.0f, fmaf(M[9], c.z, fmaf(M[5], c.y, M[1] * c.x))),
+                  fmaf(M[14], 1.0f, fmaf(M[10], c.z, fmaf(M[6], c.y, M[2] * c.x))));
+    };
+    auto N3 = [](f3 v) {
+        const float l = sqrtf(fmaf(v.z, v.z, fmaf(v.y, v.y, v.x * v.x)));
+        return mk(v.x / l, v.y / l, v.z / l);
+    };
+    Ray r;
+    if constexpr (MODEL == CAM_EQUIRECT) {
+        float phi = norm_x * (2.0f * kPI);
+        float th = norm_y * kPI;
+        float sp, cp, st, ct;
+        sincos_p(phi, sp, cp);
+        sincos_p(th, st, ct);
+        f3 c = mk(ct * sp, st, -(ct * cp));
+        r.o = mk(fp.cam[0], fp.cam[1], fp.cam[2]);
+        r.d = N3(mk(fmaf(M[8], c.z, fmaf(M[4], c.y, M[0] * c.x)), fmaf(M[9], c.z, fmaf(M[5], c.y, M[1] * c.x)),
+                    fmaf(M[10], c.z, fmaf(M[6], c.y, M[2] * c.x))));
+    } else {
+        float vhw = fp.view_half_h * fp.aspect;
+        float vx = vhw * norm_x, vy = fp.view_half_h * norm_y;
+        float k = lc.focus_distance / fp.focal;
+        if constexpr (MODEL == CAM_THIN_LENS) {
+            uint32_t hl = hash1u(ts + 0x9e3779b9u);
+            float u1, u2;
+            hash2(hl, u1, u2);
+            float rr = lc.lens_radius * sqrtf(u1);
+            float phi = (2.0f * kPI) * u2;
+            float sn, cs;
+            sincos_p(phi, sn, cs);
+            r.o = X(mk(rr * cs, rr * sn, 0.0f));
+            f3 q = X(mk(vx * k, vy * k, -lc.focus_distance));
+            r.d = N3(mk(q.x - r.o.x, q.y - r.o.y, q.z - r.o.z));
+        } else {
+            r.o = X(mk(vx * k, vy * k, 0.0f));
+            r.d = N3(mk(-M[8], -M[9], -M[10]));
+        }
+    }
+    r.inv = rcp3(r.d);
+    seed_out = hash1u(ts + (index * 67u + t));
+    return r;
+}
+
 // Stress rays of the leaf self-tests (pt_selftest_leaf: k_selftest_leaf, k_selftest_leafpass) for
 // ray i against the leaf of records rec0 .. rec0 + n - 1, family `mode`: 0 origins within 5 units of
 // a random point of an entry, directions uniform; 1 aimed at such a point from 10^-3 .. 20 units

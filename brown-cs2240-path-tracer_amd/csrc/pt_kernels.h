@@ -148,10 +148,13 @@ struct RayList {
 // ql (nullable, accumulating calls, without m2 and rl): the call traces samples frame0 .. frame0 +
 // nframes - 1 (stride 1) of the rays of the list instead of camera paths — paths per "frame" ql->n,
 // k_wf_generate_rays and k_wf_accum_rays; of fp only rr_prob, direct_only and max_depth are read
+// cam (nullable, without ql; a lens model, never CAM_PINHOLE): the camera paths come from
+// k_wf_generate_cam's instance of the model, over the window's or the list's slot map (whatever
+// lo.fuse_gen and lo.regen say); everything after the generate kernel is the pinhole's
 hipError_t launch_wavefront(const LaunchOpts& lo, const SceneView& sc, const FrameParams& fp, const WfBuffers& wb,
                             uint32_t frame0, uint32_t nframes, uint32_t stride, bool accum, bool count, float* out,
                             Counters* cnt, hipStream_t stream, const WfStreams& ws, float* m2 = nullptr,
-                            const RectList* rl = nullptr, const RayList* ql = nullptr);
+                            const RectList* rl = nullptr, const RayList* ql = nullptr, const LensCam* cam = nullptr);
 
 // set width (32 / 64 bits) of the stackless replay in the fused kernel launched last in this process
 // (0: none yet, or the stack walk) — pt_last_bf_width, for the tests of the narrow instance
@@ -180,7 +183,8 @@ hipError_t launch_tile_mean(const float* acc, const TileGrid& g, const uint32_t*
 // guide buffers of the first hit (pt_features.hip; pt_hip.h pt_render_features_async): geo += (n, t),
 // alb += (albedo, 1) per frame and hit, four floats per pixel, rows fp.row_pitch pixels apart
 hipError_t launch_features(const SceneView& sc, const FrameParams& fp, uint32_t frame0, uint32_t nframes, uint32_t stride,
-                           bool count, float* geo, float* alb, Counters* cnt, hipStream_t stream);
+                           bool count, float* geo, float* alb, Counters* cnt, hipStream_t stream,
+                           const LensCam* cam = nullptr);  // cam (nullable, a lens model): k_features_cam traces its rays
 // the a-trous denoiser (pt_denoise.hip; pt_hip.h pt_denoise_async).  prepare: the accumulators and the
 // guides (g: the tile grid of frames, g.row_pitch the pitch of all four inputs) -> three dense planes
 // of g.w * g.h float4: cv (c.rgb, var), nz (N.xyz, Z), ab (A.rgb, 0).  atrous: one pass with step s
@@ -203,7 +207,8 @@ constexpr int kQueryCtlWords = 10;
 hipError_t launch_query(const SceneView& sc, const void* rays, uint32_t n, void* hits, uint8_t* occluded, bool count,
                         Counters* cnt, uint32_t* ctl, uint32_t watchdog, int refill, int blocks, hipStream_t stream);
 // the window's camera rays of salt t, row-major, as pt_ray records (tmax = +inf, reserved = 0)
-hipError_t launch_camera_rays(const FrameParams& fp, uint32_t t, void* rays, hipStream_t stream);
+// cam (nullable, a lens model): the model's rays (k_camera_rays_cam), admitted or not
+hipError_t launch_camera_rays(const FrameParams& fp, uint32_t t, void* rays, hipStream_t stream, const LensCam* cam = nullptr);
 // the window's radiance seeds of salt t, row-major: camera_ray's seed_out per pixel (pt_camera_seeds)
 hipError_t launch_camera_seeds(const FrameParams& fp, uint32_t t, uint32_t* seeds, hipStream_t stream);
 // n floats from device memory to pinned host memory (h_dst_dev: its device address; pt_image.hip)

@@ -245,4 +245,15 @@ struct FrameParams {
     uint32_t row_pitch;   // pixels between rows of the destination, >= win_w
 };
 
+// A lens camera (pt_hip.h pt_camera) as the kernels that evaluate one take it: an
+// argument of their own beside FrameParams, which stays as it is — the pinhole's instances take no new
+// word.  model: pt_camera_model's values; CAM_PINHOLE never reaches a kernel (the host launches the
+// pinhole's own instances for it).
+enum : uint32_t { CAM_PINHOLE = 0, CAM_THIN_LENS = 1, CAM_ORTHO = 2, CAM_EQUIRECT = 3 };
+struct LensCam {
+    uint32_t model;
+    float lens_radius;     // THIN_LENS
+    float focus_distance;  // THIN_LENS, ORTHO
+};
+
 }  // namespace pt

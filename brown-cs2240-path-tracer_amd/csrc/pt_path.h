@@ -150,6 +150,19 @@ __device__ __forceinline__ bool ray_admitted(float dx, float dy, float dz) {
     return fabsf(q - 1.0f) <= 0x1p-18f;
 }
 
+// path_begin under a lens camera (camera_ray_model): the model's ray, the admission test
+// a caller's ray takes, and path_begin_ray's state.  false: the direction is not admitted (a lens point
+// that coincides with its target gives NaN) — the sample has no path, and ps is not written.
+template <uint32_t MODEL>
+__device__ __forceinline__ bool path_begin_model(const FrameParams& fp, const LensCam& lc, uint32_t x, uint32_t y, uint32_t t,
+                                                 Ray& ray, PathState& ps) {
+    uint32_t s0;
+    ray = camera_ray_model<MODEL>(fp, lc, x, y, t, s0);
+    if (!ray_admitted(ray.d.x, ray.d.y, ray.d.z)) return false;
+    path_begin_ray(ray, s0, ps);
+    return true;
+}
+
 // :124-151 after the extension trace.  Returns true when the path continues; `ray` then
 // holds the shadow ray and ps the shading point.
 __device__ __forceinline__ bool path_after_ext(const SceneView& sc, int rec, float t, Ray& ray, PathState& ps) {

@@ -246,9 +246,29 @@ __global__ __launch_bounds__(kMegaBlock) void k_camera_rays(FrameParams fp, uint
     rays[o + 1] = make_float4(r.d.x, r.d.y, r.d.z, 0.0f);
 }
 
-hipError_t launch_camera_rays(const FrameParams& fp, uint32_t t, void* rays, hipStream_t stream) {
+// k_camera_rays under a lens camera: camera_ray_model<MODEL>'s ray as computed, whether the render
+// would admit its direction or not (no compaction: ray q of the window is record q)
+template <uint32_t MODEL>
+__global__ __launch_bounds__(kMegaBlock) void k_camera_rays_cam(FrameParams fp, LensCam lc, uint32_t t, float4* __restrict__ rays) {
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const uint32_t i = blockIdx.x * 16 + (wv & 1) * 8 + (lane & 7);
+    const uint32_t j = blockIdx.y * 16 + (wv >> 1) * 8 + (lane >> 3);
+    if (i >= fp.win_w || j >= fp.win_h) return;
+    uint32_t seed;
+    const Ray r = camera_ray_model<MODEL>(fp, lc, fp.win_x0 + i, fp.win_y0 + j, t, seed);
+    const size_t o = 2 * ((size_t)j * fp.win_w + i);
+    rays[o] = make_float4(r.o.x, r.o.y, r.o.z, __builtin_inff());
+    rays[o + 1] = make_float4(r.d.x, r.d.y, r.d.z, 0.0f);
+}
+
+hipError_t launch_camera_rays(const FrameParams& fp, uint32_t t, void* rays, hipStream_t stream, const LensCam* cam) {
     const dim3 grid((fp.win_w + 15) / 16, (fp.win_h + 15) / 16), block(kMegaBlock);
-    PT_LAUNCH(KID_CAMERA_RAYS, stream, k_camera_rays, grid, block, 0, stream, fp, t, static_cast<float4*>(rays));
+    float4* const r4 = static_cast<float4*>(rays);
+    if (!cam) PT_LAUNCH(KID_CAMERA_RAYS, stream, k_camera_rays, grid, block, 0, stream, fp, t, r4);
+    else if (cam->model == CAM_THIN_LENS) PT_LAUNCH(KID_CAMERA_RAYS, stream, k_camera_rays_cam<CAM_THIN_LENS>, grid, block, 0, stream, fp, *cam, t, r4);
+    else if (cam->model == CAM_ORTHO) PT_LAUNCH(KID_CAMERA_RAYS, stream, k_camera_rays_cam<CAM_ORTHO>, grid, block, 0, stream, fp, *cam, t, r4);
+    else if (cam->model == CAM_EQUIRECT) PT_LAUNCH(KID_CAMERA_RAYS, stream, k_camera_rays_cam<CAM_EQUIRECT>, grid, block, 0, stream, fp, *cam, t, r4);
+    else return hipErrorInvalidValue;
     return hipGetLastError();
 }
 

@@ -320,6 +320,65 @@ __global__ __launch_bounds__(1024) void k_wf_generate_rays(WfBuffers wb, RayList
     }
 }
 
+// k_wf_generate under a lens camera (LensCam): k_wf_generate's slot maps — the window,
+// the rectangle list, raw_salt — with path_begin_model<MODEL> for path_begin, and k_wf_generate_rays'
+// compaction for the samples whose direction is not admitted: such a sample makes no queue entry and
+// counts nothing, and its radiance slot gets (-0, -0, -0), the one value k_wf_accum's acc + (L >= 0 ? L : 0)
+// adds without changing a bit of acc (x + -0 = x for every x, -0 included).  The host zeroes the queue's
+// and the regions' counts before the launch, as for a ray list.
+template <bool COUNT, uint32_t MODEL, class... RL>
+__global__ __launch_bounds__(256) void k_wf_generate_cam(FrameParams fp, LensCam lc, WfBuffers wb, uint32_t frame0,
+                                                         uint32_t stride, uint32_t fbase, uint32_t P, bool raw_salt,
+                                                         Counters* cnt_out, RL... rl) {
+    static_assert(sizeof...(RL) <= 1, "at most the one rectangle list");
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t R = wb.nreg;
+    bool adm = false;
+    Ray r;
+    PathState ps;
+    if (p < P) {  // p: the launch slot = the path id (slot_path)
+        uint32_t x, y, f;
+        if constexpr (sizeof...(RL) > 0) (void)slot_path(p, rl..., x, y, f);
+        else (void)slot_path(p, fp, x, y, f);
+        const uint32_t t = raw_salt ? frame0 : (uint32_t)(float)(frame0 + (fbase + f) * stride);
+        adm = path_begin_model<MODEL>(fp, lc, x, y, t, r, ps);
+        if (!adm) {
+            float* o = wb.rad + 3 * (size_t)p;
+            o[0] = -0.0f; o[1] = -0.0f; o[2] = -0.0f;
+        }
+    }
+    const uint64_t keep = __ballot(adm);
+    uint32_t slot = 0;
+    if (R) {  // the wave's slots are batch p / 64 of k_wf_generate's layout: its region's next entries
+        if (keep) {  // wave-uniform
+            const uint32_t j = __builtin_amdgcn_readfirstlane(p) / 64;
+            const uint32_t rg = (uint32_t)((uint64_t)(j % R) * wb.rqi % R);
+            uint32_t base = 0;
+            if (lane_id() == 0) base = atomicAdd(&wb.rcnt[rg], (uint32_t)__popcll(keep));
+            slot = rg * wb.rstride + __shfl(base, 0, 64) + rank_below(keep);
+        }
+    } else {  // wave counts -> one atomicAdd per block (four waves)
+        __shared__ uint32_t s_cnt[4];
+        __shared__ uint32_t s_base;
+        const uint32_t wv = threadIdx.x / 64;
+        if (lane_id() == 0) s_cnt[wv] = (uint32_t)__popcll(keep);
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const uint32_t total = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+            s_base = total ? atomicAdd(&wb.ctl[WF_COUNT0], total) : 0u;
+        }
+        __syncthreads();
+        slot = s_base + rank_below(keep);
+        for (uint32_t w = 0; w < wv; ++w) slot += s_cnt[w];
+    }
+    if (adm) store_entry(wb.ext, slot, r, p, ps);
+    if (COUNT) {
+        Counters c = {};
+        if (adm) { c.samples++; c.ext_queries++; }
+        flush_counters(c, cnt_out);
+    }
+}
+
 // Per-wave LDS staging for k_wf_trace: the current window of 32 queued rays and a ring of
 // hit records.  Keeping both in LDS takes every global load and store out of the traversal
 // loop: on gfx9 loads and stores share the wave's in-order vmcnt, so a per-lane global store
@@ -1416,7 +1475,7 @@ template <bool LDS, int TRAV, bool COUNT>
 static hipError_t wf_render_t(const SceneView& sc_in, const FrameParams& fp, const WfBuffers& wb, uint32_t frame0,
                               uint32_t nframes, uint32_t stride, bool accum, float* out, Counters* cnt,
                               hipStream_t stream, const WfStreams& ws, const LaunchOpts& lo, float* m2, const RectList* rl,
-                              const RayList* ql) {
+                              const RayList* ql, const LensCam* cam) {
     SceneView sc = bf_view<TRAV, COUNT>(sc_in);
     // paths per frame: the list's, else the window's (a ray list: its rays, a "frame" being one sample of each)
     const uint32_t npix = ql ? ql->n : rl ? rl->npix : fp.win_w * fp.win_h;
@@ -1463,7 +1522,7 @@ static hipError_t wf_render_t(const SceneView& sc_in, const FrameParams& fp, con
     constexpr bool kNarrowOk = flv_fused(TRAV) && LDS && !COUNT;
     const bool narrow = kNarrowOk && sc.bfnode && sc.bfnarrow;
     if constexpr (flv_fused(TRAV)) {  // the camera batches' table (k_wf_camtab), before every part's GEN launch
-        if (lo.fuse_gen && !rl && !ql) {
+        if (lo.fuse_gen && !rl && !ql && !cam) {
             if (sc.n_tris - sc.mb_base > 64) return hipErrorInvalidValue;  // mailbox scenes: <= 64 entries
             hipLaunchKernelGGL(k_wf_camtab, dim3(1), dim3(64), 0, stream, sc, fp, wb.camtab);
         }
@@ -1511,11 +1570,12 @@ static hipError_t wf_render_t(const SceneView& sc_in, const FrameParams& fp, con
         // (a rectangle list's camera paths come from k_wf_generate's list instance: the fuse_gen = 0 route)
         // (and a ray list's from k_wf_generate_rays, which appends to the queue's count or its regions' count
         // slots 0: zeroed here with slot 1, as k_wf_generate would have set them)
-        const bool fgen = flv_fused(TRAV) && lo.fuse_gen && !rl && !ql;
+        // (and a lens camera's from k_wf_generate_cam, which compacts as k_wf_generate_rays does)
+        const bool fgen = flv_fused(TRAV) && lo.fuse_gen && !rl && !ql && !cam;
         if (fgen)
             for (int h = 0; h < nh; ++h)
                 HIP_RETURN_IF(hipMemsetAsync(pv[h].w.rcnt + kRegions, 0, kRegions * sizeof(uint32_t), stream));
-        if (ql)
+        if (ql || cam)
             for (int h = 0; h < nh; ++h) {
                 HIP_RETURN_IF(hipMemsetAsync(pv[h].w.ctl + WF_COUNT0, 0, 2 * sizeof(uint32_t), stream));
                 if (flv_fused(TRAV)) HIP_RETURN_IF(hipMemsetAsync(pv[h].w.rcnt, 0, 2 * kRegions * sizeof(uint32_t), stream));
@@ -1541,15 +1601,31 @@ static hipError_t wf_render_t(const SceneView& sc_in, const FrameParams& fp, con
         }
         for (int h = 0; h < nh && !fgen; ++h) {
             const dim3 ggrid((std::max(pv[h].P, pv[h].w.nreg) + 255) / 256);
-            if (ql)
+            if (ql) {
                 PT_LAUNCH(KID_WF_GENERATE, pv[h].st, (k_wf_generate_rays<COUNT>), dim3((pv[h].P + 1023) / 1024), dim3(1024), 0,
                           pv[h].st, pv[h].w, *ql, frame0, pv[h].fbase, pv[h].P, cnt);
-            else if (rl)
+            } else if (cam) {
+                const dim3 cgrid((pv[h].P + 255) / 256);
+#define PT_GEN_CAM(M)                                                                                                   \
+    do {                                                                                                                \
+        if (rl)                                                                                                         \
+            PT_LAUNCH(KID_WF_GENERATE, pv[h].st, (k_wf_generate_cam<COUNT, M, RectList>), cgrid, dim3(256), 0, pv[h].st, \
+                      fp, *cam, pv[h].w, frame0, stride, pv[h].fbase, pv[h].P, !accum, cnt, *rl);                       \
+        else                                                                                                            \
+            PT_LAUNCH(KID_WF_GENERATE, pv[h].st, (k_wf_generate_cam<COUNT, M>), cgrid, dim3(256), 0, pv[h].st, fp,      \
+                      *cam, pv[h].w, frame0, stride, pv[h].fbase, pv[h].P, !accum, cnt);                                \
+    } while (0)
+                if (cam->model == CAM_THIN_LENS) PT_GEN_CAM(CAM_THIN_LENS);
+                else if (cam->model == CAM_ORTHO) PT_GEN_CAM(CAM_ORTHO);
+                else PT_GEN_CAM(CAM_EQUIRECT);
+#undef PT_GEN_CAM
+            } else if (rl) {
                 PT_LAUNCH(KID_WF_GENERATE, pv[h].st, (k_wf_generate<COUNT, RectList>), ggrid, dim3(256), 0, pv[h].st,
                           fp, pv[h].w, frame0, stride, pv[h].fbase, pv[h].P, !accum, cnt, *rl);
-            else
+            } else {
                 PT_LAUNCH(KID_WF_GENERATE, pv[h].st, (k_wf_generate<COUNT>), ggrid, dim3(256), 0, pv[h].st,
                           fp, pv[h].w, frame0, stride, pv[h].fbase, pv[h].P, !accum, cnt);
+            }
         }
         // launch `it` of part h (in_q: the queue the trace kernels read, it & 1)
         auto step = [&](int h, int it) -> hipError_t {
@@ -1647,8 +1723,9 @@ static hipError_t wf_render_t(const SceneView& sc_in, const FrameParams& fp, con
 hipError_t launch_wavefront(const LaunchOpts& lo, const SceneView& sc, const FrameParams& fp, const WfBuffers& wb,
                             uint32_t frame0, uint32_t nframes, uint32_t stride, bool accum, bool count, float* out,
                             Counters* cnt, hipStream_t stream, const WfStreams& ws, float* m2, const RectList* rl,
-                            const RayList* ql) {
+                            const RayList* ql, const LensCam* cam) {
     if ((m2 || rl || ql) && !accum) return hipErrorInvalidValue;
+    if (cam && (ql || cam->model < CAM_THIN_LENS || cam->model > CAM_EQUIRECT)) return hipErrorInvalidValue;
     if (ql && (m2 || rl || stride != 1 || ql->n == 0)) return hipErrorInvalidValue;
     if (!accum) { nframes = 1; stride = 1; }
     const bool lds = lo.lds && scene_fits_lds(sc);
@@ -1656,7 +1733,7 @@ hipError_t launch_wavefront(const LaunchOpts& lo, const SceneView& sc, const Fra
     // (pt_capi.hip shape_view: option leaf_pre, default on) and the buffers exist
     const int trav = select_wavefront(lo, sc.fast_rcp != 0, sc.mailbox != 0, sc.big_leaf > 0, sc.npre > 0 && sc.pre && wb.pres);
     // sc.node_bias <= 0: chosen per instance in wf_render_t
-#define WF_ARGS sc, fp, wb, frame0, nframes, stride, accum, out, cnt, stream, ws, lo, m2, rl, ql
+#define WF_ARGS sc, fp, wb, frame0, nframes, stride, accum, out, cnt, stream, ws, lo, m2, rl, ql, cam
 #define WF(T)                                                                                                        \
     case T:                                                                                                          \
         return lds ? (count ? wf_render_t<true, T, true>(WF_ARGS) : wf_render_t<true, T, false>(WF_ARGS))            \

@@ -887,6 +887,57 @@ static napi_value js_scene_set_vertex_normals(napi_env env, napi_callback_info i
     return NULL;
 }
 
+/* sceneSetCamera(scene, {model, lensRadius = 0, focusDistance = 1}): the camera model of later calls on the
+ * scene (pt_scene_set_camera).  model: 'pinhole' | 'thin_lens' (or 'thinlens') | 'ortho' | 'equirect', or its
+ * number; null or undefined instead of the object: the pinhole. */
+static napi_value js_scene_set_camera(napi_env env, napi_callback_info info) {
+    size_t argc = 2;
+    napi_value argv[2];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    pt_scene* s = argc ? get_scene(env, argv[0]) : NULL;
+    pt_camera cam = {PT_CAMERA_PINHOLE, 0.0f, 1.0f, 0};
+    bool ok = s != NULL;
+    napi_valuetype t = napi_undefined;
+    if (ok && argc > 1) napi_typeof(env, argv[1], &t);
+    if (ok && t == napi_object) {
+        napi_value v;
+        napi_valuetype vt = napi_undefined;
+        ok = napi_get_named_property(env, argv[1], "model", &v) == napi_ok && napi_typeof(env, v, &vt) == napi_ok;
+        if (ok && vt == napi_string) {
+            char name[16] = "";
+            size_t len = 0;
+            ok = napi_get_value_string_utf8(env, v, name, sizeof name, &len) == napi_ok;
+            if (!strcmp(name, "pinhole")) cam.model = PT_CAMERA_PINHOLE;
+            else if (!strcmp(name, "thin_lens") || !strcmp(name, "thinlens")) cam.model = PT_CAMERA_THIN_LENS;
+            else if (!strcmp(name, "ortho")) cam.model = PT_CAMERA_ORTHO;
+            else if (!strcmp(name, "equirect")) cam.model = PT_CAMERA_EQUIRECT;
+            else ok = false;
+        } else if (ok && vt == napi_number) {
+            ok = napi_get_value_uint32(env, v, &cam.model) == napi_ok;
+        } else {
+            ok = false;
+        }
+        const char* keys[2] = {"lensRadius", "focusDistance"};
+        float* dst[2] = {&cam.lens_radius, &cam.focus_distance};
+        for (int k = 0; k < 2 && ok; ++k) {
+            double d;
+            if (napi_get_named_property(env, argv[1], keys[k], &v) != napi_ok || napi_typeof(env, v, &vt) != napi_ok) ok = false;
+            else if (vt == napi_number) { ok = napi_get_value_double(env, v, &d) == napi_ok; *dst[k] = (float)d; }
+            else if (vt != napi_undefined) ok = false;
+        }
+    } else if (ok && t != napi_undefined && t != napi_null) {
+        ok = false;
+    }
+    if (!ok) {
+        if (!pending_exception(env))
+            napi_throw_type_error(env, NULL, "sceneSetCamera(scene, {model: 'pinhole'|'thin_lens'|'ortho'|'equirect', lensRadius, focusDistance})");
+        return NULL;
+    }
+    int rc = pt_scene_set_camera(s, &cam);
+    if (rc) return throw_pt(env, rc);
+    return NULL;
+}
+
 /* profileRead(scene) -> {kernel: {launches, totalMs, minMs, maxMs, busyMs}} */
 static napi_value js_profile_read(napi_env env, napi_callback_info info) {
     size_t argc = 1;
@@ -940,6 +991,7 @@ static napi_value init(napi_env env, napi_value exports) {
         {"profileRead", NULL, js_profile_read, NULL, NULL, NULL, napi_enumerable, NULL},
         {"bvhBuild", NULL, js_bvh_build, NULL, NULL, NULL, napi_enumerable, NULL},
         {"sceneSetVertexNormals", NULL, js_scene_set_vertex_normals, NULL, NULL, NULL, napi_enumerable, NULL},
+        {"sceneSetCamera", NULL, js_scene_set_camera, NULL, NULL, NULL, napi_default, NULL},
     };
     napi_define_properties(env, exports, sizeof props / sizeof props[0], props);
     return exports;

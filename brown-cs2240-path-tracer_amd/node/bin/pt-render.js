@@ -13,6 +13,10 @@
 //  library's; the whole image only, without --counters, --spp at least 2) [--feature-frames N] (frames of its guide buffers, default 4)
 // [--pick x,y] (print what the frame-0 camera ray of pixel (x, y) hits — point, distance, normal, material —
 //  as one JSON line and render nothing: pt_camera_rays + pt_query_hits)
+// [--camera thinlens|ortho|equirect] [--aperture R] [--focus-distance F] (a lens camera evaluated on the device,
+//  pt_scene_set_camera: jittered like the pinhole, thinlens with depth of field from a lens of radius R (default 0)
+//  focused at distance F (default |focus - position| of the scene's camera); combines with --window, the rectangle
+//  list, --denoise and --counters; --dump-accum FILE writes the accumulator, 3 f32 per pixel, before the tone map)
 // [--projection pinhole|equirect|ortho] (pinhole: the render above, the default.  The other two trace rays made
 //  here through pt_query_radiance, the whole image only, one ray per pixel through its centre (u, v) = ((x + 0.5) / W,
 //  (y + 0.5) / H), with the camera's axes R, U, B = columns 0..2 of cam_to_world (look L = -B) and its position P:
@@ -22,6 +26,7 @@
 //              sees in the plane through the focus), a = W / H
 //  all in doubles, then unitRays' f32 normalisation.  Seeds: pixel index i = x + y W has seed hash1u(hash1u(i * 16787))
 //  for its sample 0 and, the library's rule, hash1u(seed + s * 16787) for sample s of --spp, frame after frame.)
+//  (--camera ortho|equirect renders these projections on the device, jittered, with every other option.)
 // [--dump-rays FILE] (with equirect or ortho: the rays, 8 f32 each, then the seeds, one u32 each, as made)
 // [--dump-accum FILE] (with equirect or ortho: the accumulator, 3 f32 per pixel, before the tone map)
 const fs = require('fs');
@@ -72,21 +77,36 @@ async function main(argv) {
         process.exit(2);
     }
     if (projection !== 'pinhole') return project(args, projection);
+    const models = { thinlens: 'thin_lens', thin_lens: 'thin_lens', ortho: 'ortho', equirect: 'equirect' };
+    const num = (v) => (v === undefined ? undefined : Number(v));
+    if ((args.camera !== undefined && !models[args.camera]) || (args.camera === undefined && (args.aperture !== undefined || args.focus_distance !== undefined)) ||
+        [args.aperture, args.focus_distance].some((v) => v !== undefined && !Number.isFinite(Number(v)))) {
+        console.error(`usage: pt-render.js <scene.ini> --camera thinlens|ortho|equirect [--aperture R] [--focus-distance F]: ` +
+                      `--camera ${args.camera} --aperture ${args.aperture} --focus-distance ${args.focus_distance}`);
+        process.exit(2);
+    }
     const t0 = Date.now();
     const s = host.load_scene_from_ini(args._[0], { web_root: args.web_root, quiet: true });
     if (args.spp) s.scene_description.Settings.samplesPerPixel = parseInt(args.spp);
+    let camera = null;
+    if (args.camera !== undefined) {
+        const focus = s.camera_data.focus.toArray(), pos = s.camera_data.pos.toArray();
+        const dist = Math.hypot(focus[0] - pos[0], focus[1] - pos[1], focus[2] - pos[2]);
+        camera = { model: models[args.camera], lensRadius: num(args.aperture) || 0, focusDistance: args.focus_distance === undefined ? dist : num(args.focus_distance) };
+    }
     const t1 = Date.now();
     const r = await host.programEntry(s.screenDimension, s.primitive_data, s.camera_data, s.scene_description, {
         device: parseInt(args.device || '0'), maxDepth: parseInt(args.max_depth || '16'), mode: args.mode || 'auto',
-        vertexNormals: args.vertex_normals === '1', counters: args.counters === '1', window, rects, denoise,
+        vertexNormals: args.vertex_normals === '1', counters: args.counters === '1', window, rects, denoise, camera,
     });
     const t2 = Date.now();
     const [W, H] = window ? [window[2], window[3]] : s.screenDimension;
     const out = path.join(args.out_root || '.', s.scene_description.IO.output || 'out.png');
     fs.mkdirSync(path.dirname(out), { recursive: true });
     fs.writeFileSync(out, host.encode_png(r.rgba, W, H));
+    if (args.dump_accum && r.accum) fs.writeFileSync(args.dump_accum, Buffer.from(r.accum.buffer, r.accum.byteOffset, r.accum.byteLength));
     const samples = (rects ? rects.reduce((a, w) => a + w[2] * w[3], 0) : W * H) * r.sample_runs;
-    console.log(JSON.stringify({ output: out, width: W, height: H, window, rects, spp: r.sample_runs, scene_ms: t1 - t0,
+    console.log(JSON.stringify({ output: out, width: W, height: H, window, rects, camera, spp: r.sample_runs, scene_ms: t1 - t0,
         denoise, render_ms: t2 - t1, msamples_per_s: samples / ((t2 - t1) / 1000) / 1e6, counters: r.counters }));
 }
 // hash.wgsl's hash1u in u32 arithmetic

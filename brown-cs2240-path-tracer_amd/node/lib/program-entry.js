@@ -54,6 +54,8 @@ function check_rects(rects) {
  * options: {device=0, devices=[...] (several GPUs: pt_render_multi), maxDepth=16, mode='auto', frame0=0, chunk=spp,
  *           onFrames(done, total), imageOnly=false,
  *           vertexNormals=false (the reference's commented-out smooth-normal branch; changes results),
+ *           camera={model: 'thin_lens'|'ortho'|'equirect'|'pinhole', lensRadius=0, focusDistance=1} (a lens camera
+ *           evaluated on the device, pt_scene_set_camera: combines with every other option),
  *           counters=false (work counters: the kernels' counting builds, slower; counters is null without),
  *           window=[x0, y0, w, h] (render that rectangle of the image only: accum is w*h*3 and rgba w*h*4, the
  *           crop of the windowless result — every pixel's samples and its tone map are the full image's; not
@@ -89,6 +91,7 @@ async function programEntry(screenDimension, primitive_data, camera_data, scene_
     // when V8 happens to collect the handle
     try {
         if (o.vertexNormals) pt.sceneSetVertexNormals(scene, true);
+        if (o.camera) pt.sceneSetCamera(scene, o.camera);
         const spp = scene_description.Settings.samplesPerPixel;
         const chunk = Math.max(1, o.chunk || spp);
         const scene_info = pt.sceneInfo(scene);
@@ -130,6 +133,7 @@ async function programEntryMulti(pt, meta, W, H, primitive_data, scene_descripti
     try {
         for (const d of o.devices) scenes.push(pt.sceneCreate(primitive_data[0].triangle_data, primitive_data[0].bvh_data, d));
         if (o.vertexNormals) for (const s of scenes) pt.sceneSetVertexNormals(s, true);
+        if (o.camera) for (const s of scenes) pt.sceneSetCamera(s, o.camera);
         const spp = scene_description.Settings.samplesPerPixel;
         const scene_info = pt.sceneInfo(scenes[0]);
         const accum = new Float32Array(W * H * 3);

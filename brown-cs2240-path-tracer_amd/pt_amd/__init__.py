@@ -13,6 +13,8 @@ no GPU is visible, calls raise `PtError`.
 from ._lib import (  # noqa: F401
     ABI_VERSION,
     Adaptive,
+    CAMERA_MODELS,
+    Camera,
     MODE_AUTO,
     MODE_MEGAKERNEL,
     MODE_WAVEFRONT,

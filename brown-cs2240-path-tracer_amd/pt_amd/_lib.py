@@ -14,7 +14,7 @@ _CSRC = os.path.join(_PKG_ROOT, "csrc")
 # csrc/Makefile BUILD_SRCS: the sources whose SHA-256 the library carries as pt_build_id()
 _BUILD_SRCS = ["pt_kernels.hip", "pt_wavefront.hip", "pt_leafpass.hip", "pt_image.hip", "pt_features.hip", "pt_denoise.hip", "pt_query.hip", "pt_capi.hip", "pt_capi_render.hip",
                "pt_capi_adaptive.hip", "pt_capi_denoise.hip", "pt_capi_query.hip", "pt_capi_radiance.hip", "pt_capi_selftest.hip",
-               "pt_capi_multi.hip", "pt_capi_internal.h", "pt_math.h", "pt_flavour.h", "pt_layout.h",
+               "pt_capi_multi.hip", "pt_capi_camera.hip", "pt_capi_internal.h", "pt_math.h", "pt_flavour.h", "pt_layout.h",
                "pt_device.h", "pt_path.h", "pt_kernels.h", "../../include/pt_hip.h", "pt_bvh.cpp", "pt_leafbvh.h",
                "pt_leafbvh.cpp", "pt_leafskip.cpp", "pt_scene_layout.h", "pt_scene_layout.cpp", "pt_rect_plan.h",
                "pt_rect_plan.cpp", "pt_query_plan.h", "pt_step_addr.h", "Makefile"]
@@ -53,6 +53,15 @@ class RadianceParams(ctypes.Structure):
     """pt_radiance_params."""
     _fields_ = [("rr_prob", ctypes.c_float), ("direct_only", ctypes.c_int32), ("max_depth", ctypes.c_int32),
                 ("nsamples", ctypes.c_uint32)]
+
+
+CAMERA_MODELS = ("pinhole", "thin_lens", "ortho", "equirect")  # pt_camera_model, by value
+
+
+class Camera(ctypes.Structure):
+    """pt_camera (16 B): the model and its lens (Scene.set_camera)."""
+    _fields_ = [("model", ctypes.c_uint32), ("lens_radius", ctypes.c_float), ("focus_distance", ctypes.c_float),
+                ("reserved", ctypes.c_uint32)]
 
 
 class Window(ctypes.Structure):
@@ -391,6 +400,9 @@ def load_library():
     L.pt_render_image.argtypes = [p, p, u32, u32, u32, i, i, p, p]
     L.pt_profile_read.argtypes = [p, ctypes.POINTER(KernelTime), i, ctypes.POINTER(i)]
     L.pt_scene_set_vertex_normals.argtypes = [p, i]
+    L.pt_scene_set_camera.argtypes = [p, ctypes.POINTER(Camera)]
+    L.pt_scene_get_camera.argtypes = [p, ctypes.POINTER(Camera)]
+    L.pt_scene_set_camera.restype = L.pt_scene_get_camera.restype = i
     L.pt_scene_check.argtypes = [p]
     L.pt_render_multi.argtypes = [ctypes.POINTER(p), i, p, u32, u32, u32, i, i, p, p]
     L.pt_set_hw_queues.argtypes = [i]
@@ -544,6 +556,24 @@ class Scene:
     def set_vertex_normals(self, enable: bool = True):
         """Vertex-normal shading (pt_scene_set_vertex_normals; off = the reference's behaviour)."""
         _check(self._lib.pt_scene_set_vertex_normals(self._h, 1 if enable else 0))
+
+    def set_camera(self, model="pinhole", lens_radius: float = 0.0, focus_distance: float = 1.0):
+        """pt_scene_set_camera: the camera model of later calls on the scene — "pinhole" (the reference's,
+        the default), "thin_lens" (lens_radius, focus_distance), "ortho" (focus_distance) or "equirect";
+        a model's number (CAMERA_MODELS' index) is taken as it is."""
+        m = CAMERA_MODELS.index(model) if isinstance(model, str) and model in CAMERA_MODELS else model
+        if isinstance(m, str):
+            raise ValueError(f"unknown camera model {model!r} (one of {CAMERA_MODELS})")
+        cam = Camera(int(m), float(lens_radius), float(focus_distance), 0)
+        _check(self._lib.pt_scene_set_camera(self._h, ctypes.byref(cam)))
+
+    @property
+    def camera(self) -> dict:
+        """pt_scene_get_camera: {"model", "lens_radius", "focus_distance"} as set."""
+        cam = Camera()
+        _check(self._lib.pt_scene_get_camera(self._h, ctypes.byref(cam)))
+        name = CAMERA_MODELS[cam.model] if cam.model < len(CAMERA_MODELS) else cam.model
+        return {"model": name, "lens_radius": cam.lens_radius, "focus_distance": cam.focus_distance}
 
     @property
     def info(self) -> dict:

@@ -111,6 +111,46 @@ int pt_scene_get_info(const pt_scene* scene, pt_scene_info* info_out);
  * with vertex normals.  Applies to later renders of the scene. */
 int pt_scene_set_vertex_normals(pt_scene* scene, int enable);
 
+/* Lens cameras, evaluated on the device where a render makes its camera paths.  A
+ * scene-level setting like pt_scene_set_vertex_normals: it applies to later calls on the scene and
+ * reaches every entry point that makes camera paths — pt_render*, pt_render_window*, pt_render_moments*,
+ * pt_render_rects*, pt_render_adaptive, pt_render_features*, pt_render_denoised_image, pt_render_image,
+ * pt_frame*, pt_camera_rays* — while pt_camera_seeds is independent of it.  cam NULL or model
+ * PT_CAMERA_PINHOLE: the reference's jittered pinhole, and every call launches what it always launched.
+ *
+ * Every model keeps the pinhole's prologue (program-raymarch.wgsl:50-76): the pixel's seed chain, its
+ * jitter, norm_x / norm_y, vx / vy and the radiance seed — so the anti-aliasing jitter and the seed of a
+ * (pixel, frame) do not depend on the model.  With M = cam_to_world (meta[28..43], column-major),
+ * X(c)_k = fma(M[12+k], 1, fma(M[8+k], c.z, fma(M[4+k], c.y, M[k] * c.x))) and N3(v) = v / sqrt(fma(v.z,
+ * v.z, fma(v.y, v.y, v.x * v.x))), every operation f32 and rounded once, sincos the pinned one, PI 3.14159f:
+ *   THIN_LENS  hl = hash1u(ts + 0x9e3779b9) (ts: the chain after its third hash), (u1, u2) = hash2(hl),
+ *              r = lens_radius * sqrt(u1), phi = (2 PI) * u2, l = (r cos phi, r sin phi, 0),
+ *              k = focus_distance / focal, c = (vx * k, vy * k, -focus_distance),
+ *              o = X(l), d = N3(X(c) - o).
+ *              The origin comes from M's translation column, not from meta[4..6]; every meta the hosts
+ *              make has the two equal.  lens_radius = 0 is a pinhole that differs from the reference's
+ *              in rounding only.
+ *   ORTHO      k = focus_distance / focal, o = X((vx * k, vy * k, 0)), d = N3((-M[8], -M[9], -M[10])):
+ *              what the pinhole sees at the plane of focus, in parallel projection.
+ *   EQUIRECT   phi = norm_x * (2 PI), th = norm_y * PI, c = (cos th sin phi, sin th, -(cos th cos phi)),
+ *              o = meta[4..6], d = N3(M's rotation applied to c); aspect, focal and vfov play no part.
+ * Contract: a pixel's sample of frame k is the reference's radiance(ray, seed) for that ray (inv = 1 / d)
+ * and the pinhole's seed, clamped and added in frame order — per frame, pt_query_radiance(nsamples = 1)
+ * on pt_camera_rays and pt_camera_seeds.  A direction that pt_query_radiance would not admit (a lens
+ * point that coincides with its target gives NaN) contributes nothing to that sample — the accumulator
+ * keeps its bits — and adds to no counter; pt_camera_rays reports it as computed.  (pt_frame* writes -0
+ * for such a sample, and pt_render_moments turns a second moment of -0 into +0.)
+ * With a model set a call always runs the wavefront pipeline with camera paths from the generate kernel:
+ * options kernel=mega|literal, fuse_gen and regen do not apply, as for pt_query_radiance.
+ * Errors (PT_ERR_INVALID): unknown model; THIN_LENS with lens_radius not finite or < 0, or
+ * focus_distance not finite or <= 0; ORTHO with focus_distance not finite or <= 0.  Fields a model does
+ * not use are ignored (lens_radius by ORTHO and EQUIRECT, focus_distance by EQUIRECT).
+ * pt_render_multi needs the same pt_camera (bytewise) on all its scenes. */
+typedef enum { PT_CAMERA_PINHOLE = 0, PT_CAMERA_THIN_LENS = 1, PT_CAMERA_ORTHO = 2, PT_CAMERA_EQUIRECT = 3 } pt_camera_model;
+typedef struct { uint32_t model; float lens_radius; float focus_distance; uint32_t reserved; } pt_camera; /* 16 B */
+int pt_scene_set_camera(pt_scene* scene, const pt_camera* cam);
+int pt_scene_get_camera(const pt_scene* scene, pt_camera* cam_out);
+
 /* Render frames k = frame0 + i*frame_stride, i < nframes, each 1 spp per pixel, and add
  * clamp(L) (v >= 0 ? v : 0, NaN -> 0) into accum in frame order — the render_loop of
  * program-raymarch.ts:226-335 without the per-frame readback.  accum: host f32

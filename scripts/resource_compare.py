@@ -1,6 +1,6 @@
 """Compare the kernels' resource blocks of two trees: scripts/resource_compare.py PARENT_ASM_DIR NEW_ASM_DIR
 
-Each directory holds pt_kernels.s, pt_wavefront.s, pt_leafpass.s and pt_query.s, made from a tree's csrc/ by
+Each directory holds pt_kernels.s, pt_wavefront.s, pt_leafpass.s, pt_query.s and pt_features.s, made from a tree's csrc/ by
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-slp-vectorize --cuda-device-only -S X.hip -o DIR/X.s
 (csrc/Makefile's flags; no GPU needed).  Per kernel instance the .amdhsa block (next free VGPR and SGPR,
 accum_offset, private segment = scratch, group segment = static LDS) and the compiler's NumVgprs, NumAgprs,
@@ -28,7 +28,7 @@ def dem(names):
 lines = []
 same = diff = 0
 newk = []
-for f in ["pt_kernels", "pt_wavefront", "pt_leafpass", "pt_query"]:
+for f in ["pt_kernels", "pt_wavefront", "pt_leafpass", "pt_query", "pt_features"]:
     a, b = parse(f"{sys.argv[1]}/{f}.s"), parse(f"{sys.argv[2]}/{f}.s")
     names = dem(sorted(set(a) | set(b)))
     for k in sorted(b):
