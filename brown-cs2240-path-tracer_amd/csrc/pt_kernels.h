@@ -24,14 +24,15 @@ namespace pt {
 enum KernelId : int {
     KID_MEGA = 0, KID_REGEN, KID_WF_GENERATE, KID_WF_TRACE, KID_WF_SHADE_EXT, KID_WF_SHADE_SHADOW, KID_WF_ACCUM,
     KID_TONEMAP, KID_WF_STEP, KID_WF_LEAF, KID_NOISE_TILES, KID_TILE_MEAN, KID_FEATURES, KID_DENOISE_PREPARE, KID_ATROUS,
-    KID_QUERY_HITS, KID_QUERY_OCCLUDED, KID_CAMERA_RAYS, KID_CAMERA_SEEDS, KID_COUNT
+    KID_QUERY_HITS, KID_QUERY_OCCLUDED, KID_CAMERA_RAYS, KID_CAMERA_SEEDS, KID_GATHER_RAYS,
+    KID_COUNT
 };
 inline const char* kernel_name(int k) {
     static const char* const n[KID_COUNT] = {"k_mega",         "k_regen",           "k_wf_generate", "k_wf_trace",
                                              "k_wf_shade_ext", "k_wf_shade_shadow", "k_wf_accum",    "k_tonemap",
                                              "k_wf_step",      "k_wf_leafpass",     "k_noise_tiles", "k_tile_mean",
                                              "k_features",     "k_denoise_prepare", "k_atrous",      "k_query_hits",
-                                             "k_query_occluded", "k_camera_rays", "k_camera_seeds"};
+                                             "k_query_occluded", "k_camera_rays", "k_camera_seeds", "k_gather_rays"};
     return (k >= 0 && k < KID_COUNT) ? n[k] : "?";
 }
 struct KernelProfiler {
@@ -142,6 +143,15 @@ struct RayList {
     const uint32_t* seeds;  // n
     uint32_t n;
 };
+// A gather list on the device (pt_gather): the fifth slot map.  The ray list's map —
+// "frame" f is sample f of every point, path id f * n + i — with the sample's ray drawn by the generate
+// kernel (k_wf_generate_gather) and the radiance added to out + 3 * i (GATHER_COSINE) or, weighted by the
+// nine SH basis values of the direction, to out + 27 * i (GATHER_SH9) by k_wf_accum_gather.
+struct GatherList {
+    const float4* pts;  // n pt_gather_point records, two float4 each: (p, seed bits), (n, reserved)
+    uint32_t n;
+    uint32_t mode;      // GATHER_COSINE / GATHER_SH9 (pt_path.h)
+};
 // rl (nullable, accumulating calls): the call renders the rectangles of the list instead of fp's
 // window — paths per frame rl->npix, camera paths by k_wf_generate's list instance (whatever
 // lo.fuse_gen and lo.regen say), k_wf_accum's list instance
@@ -151,10 +161,14 @@ struct RayList {
 // cam (nullable, without ql; a lens model, never CAM_PINHOLE): the camera paths come from
 // k_wf_generate_cam's instance of the model, over the window's or the list's slot map (whatever
 // lo.fuse_gen and lo.regen say); everything after the generate kernel is the pinhole's
+// gl (nullable, accumulating calls, without m2, rl, ql and cam): as ql, for the points of the gather list
 hipError_t launch_wavefront(const LaunchOpts& lo, const SceneView& sc, const FrameParams& fp, const WfBuffers& wb,
                             uint32_t frame0, uint32_t nframes, uint32_t stride, bool accum, bool count, float* out,
                             Counters* cnt, hipStream_t stream, const WfStreams& ws, float* m2 = nullptr,
-                            const RectList* rl = nullptr, const RayList* ql = nullptr, const LensCam* cam = nullptr);
+                            const RectList* rl = nullptr, const RayList* ql = nullptr, const LensCam* cam = nullptr,
+                            const GatherList* gl = nullptr);
+// sample `sample` of every point of the list as pt_ray records and radiance seeds (pt_gather_rays)
+hipError_t launch_gather_rays(const GatherList& gl, uint32_t sample, void* rays, uint32_t* seeds, hipStream_t stream);
 
 // set width (32 / 64 bits) of the stackless replay in the fused kernel launched last in this process
 // (0: none yet, or the stack walk) — pt_last_bf_width, for the tests of the narrow instance

@@ -163,6 +163,50 @@ __device__ __forceinline__ bool path_begin_model(const FrameParams& fp, const Le
     return true;
 }
 
+// Irradiance gathers (pt_gather).  A gather point is two float4: (p, seed bits) and
+// (n, reserved).  Sample s of a point draws its direction with sd = gather_seed(seed, s) — the radiance
+// queries' rule — and its path enters radiance() with seed_in = hash1u(sd + 7), the reference's idiom for
+// "the next decision".
+constexpr uint32_t GATHER_COSINE = 0, GATHER_SH9 = 1;
+
+__device__ __forceinline__ uint32_t gather_seed(uint32_t seed, uint32_t s) { return s == 0 ? seed : hash1u(seed + s * 16787u); }
+
+// SH9 mode's direction: uniform on the sphere from the sampler's own two numbers
+__device__ __forceinline__ f3 gather_sphere_dir(uint32_t sd) {
+    float xi1, xi2;
+    hash2(sd * 7u + 11u, xi1, xi2);
+    const float phi = (2.0f * kPI) * xi1;
+    const float z = fmaf(-2.0f, xi2, 1.0f);
+    const float r = sqrtf(fmaxf(fmaf(-z, z, 1.0f), 0.0f));
+    float sn, cs;
+    sincos_p(phi, sn, cs);
+    return mk(r * cs, r * sn, z);
+}
+
+// The ray of a sample drawn with sd.  COSINE: the point is admitted iff nn = |n|^2 (fma chain) lies in
+// [2^-80, 2^80] (a NaN fails); the ray is the reference's diffuse bounce from p about n / sqrt(nn) —
+// sample_hemisphere and ray_with_epsilon.  SH9: gather_sphere_dir from p itself, the normal ignored.
+// false: the point or the generated direction (ray_admitted) is not admitted, and `ray` is not written.
+// ray.inv is not set: the queues do not store it.
+template <uint32_t MODE>
+__device__ __forceinline__ bool gather_ray(const float4& a, const float4& b, uint32_t sd, Ray& ray) {
+    f3 d;
+    if constexpr (MODE == GATHER_COSINE) {
+        const float nn = fmaf(b.z, b.z, fmaf(b.y, b.y, b.x * b.x));
+        if (!(nn >= 0x1p-80f && nn <= 0x1p80f)) return false;
+        const float len = sqrtf(nn);
+        float pdf;  // not used: the estimator's weight is the constant pi
+        d = sample_hemisphere(mk(b.x / len, b.y / len, b.z / len), sd, pdf);
+    } else {
+        d = gather_sphere_dir(sd);
+    }
+    if (!ray_admitted(d.x, d.y, d.z)) return false;
+    if constexpr (MODE == GATHER_COSINE) ray.o = mk(fmaf(0.001f, d.x, a.x), fmaf(0.001f, d.y, a.y), fmaf(0.001f, d.z, a.z));
+    else ray.o = mk(a.x, a.y, a.z);
+    ray.d = d;
+    return true;
+}
+
 // :124-151 after the extension trace.  Returns true when the path continues; `ray` then
 // holds the shadow ray and ps the shading point.
 __device__ __forceinline__ bool path_after_ext(const SceneView& sc, int rec, float t, Ray& ray, PathState& ps) {

@@ -379,6 +379,93 @@ __global__ __launch_bounds__(256) void k_wf_generate_cam(FrameParams fp, LensCam
     }
 }
 
+// k_wf_generate for a gather list (pt_gather; GatherList, pt_kernels.h): launch slot
+// p < P is sample f = p / n of point i = p - f n, so neighbouring lanes load neighbouring 32-byte points
+// (two float4 each).  Path id p.  The sample's direction is drawn on the spot (gather_ray<MODE>) with
+// sd = gather_seed(seed, sample0 + fbase + f) and its path enters with seed_in = hash1u(sd + 7).  A point
+// or a sample that is not admitted makes no queue entry and counts nothing; its radiance slot gets the
+// lens cameras' (-0, -0, -0), which no traced path can leave there (a path's L starts at +0 and is only
+// added to), so k_wf_accum_gather skips it.  The admitted paths are compacted exactly as
+// k_wf_generate_rays compacts them (the statements are repeated here so that that kernel's code does not
+// change); the host zeroes the counts before the launch.
+template <bool COUNT, uint32_t MODE>
+__global__ __launch_bounds__(1024) void k_wf_generate_gather(WfBuffers wb, GatherList gl, uint32_t sample0, uint32_t fbase,
+                                                             uint32_t P, Counters* cnt_out) {
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t R = wb.nreg;
+    bool adm = false;
+    Ray r;
+    PathState ps;
+    if (p < P) {
+        const uint32_t f = p / gl.n, i = p - f * gl.n;
+        const float4 a = gl.pts[2 * (size_t)i], b = gl.pts[2 * (size_t)i + 1];
+        const uint32_t sd = gather_seed(__float_as_uint(a.w), sample0 + fbase + f);
+        adm = gather_ray<MODE>(a, b, sd, r);
+        if (adm) {
+            r.inv = r.d;  // not stored: the trace kernels take 1 / d when they unpack the entry
+            path_begin_ray(r, hash1u(sd + 7u), ps);
+        } else {
+            float* o = wb.rad + 3 * (size_t)p;
+            o[0] = -0.0f; o[1] = -0.0f; o[2] = -0.0f;
+        }
+    }
+    const uint64_t keep = __ballot(adm);
+    uint32_t slot = 0;
+    if (R) {  // the wave's slots are batch p / 64 of k_wf_generate's layout: its region's next entries
+        if (keep) {  // wave-uniform
+            const uint32_t j = __builtin_amdgcn_readfirstlane(p) / 64;
+            const uint32_t rg = (uint32_t)((uint64_t)(j % R) * wb.rqi % R);
+            uint32_t base = 0;
+            if (lane_id() == 0) base = atomicAdd(&wb.rcnt[rg], (uint32_t)__popcll(keep));
+            slot = rg * wb.rstride + __shfl(base, 0, 64) + rank_below(keep);
+        }
+    } else {  // wave counts -> LDS prefix -> one atomicAdd per block (as k_wf_generate_rays)
+        __shared__ uint32_t s_cnt[16];
+        const uint32_t wv = threadIdx.x / 64;
+        if (lane_id() == 0) s_cnt[wv] = (uint32_t)__popcll(keep);
+        __syncthreads();
+        if (threadIdx.x < 64) {
+            const uint32_t n = threadIdx.x < 16 ? s_cnt[threadIdx.x] : 0u;
+            uint32_t incl = n;
+#pragma unroll
+            for (int off = 1; off < 64; off <<= 1) {
+                const uint32_t v = __shfl_up(incl, off, 64);
+                if (lane_id() >= (uint32_t)off) incl += v;
+            }
+            const uint32_t total = __shfl(incl, 63, 64);
+            uint32_t base = 0;
+            if (threadIdx.x == 0 && total) base = atomicAdd(&wb.ctl[WF_COUNT0], total);
+            base = __shfl(base, 0, 64);
+            if (threadIdx.x < 16) s_cnt[threadIdx.x] = base + incl - n;
+        }
+        __syncthreads();
+        slot = s_cnt[wv] + rank_below(keep);
+    }
+    if (adm) store_entry(wb.ext, slot, r, p, ps);
+    if (COUNT) {
+        Counters c = {};
+        if (adm) { c.samples++; c.ext_queries++; }
+        flush_counters(c, cnt_out);
+    }
+}
+
+// One sample of every point as the ray and seed a radiance query takes (pt_gather_rays): pt_ray
+// {o, +inf, d, 0} and seed_in; a point or sample that is not admitted gets d = 0 (o = p) and seed 0.
+template <uint32_t MODE>
+__global__ __launch_bounds__(256) void k_gather_rays(GatherList gl, uint32_t sample, float4* __restrict__ rays,
+                                                     uint32_t* __restrict__ seeds) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= gl.n) return;
+    const float4 a = gl.pts[2 * (size_t)i], b = gl.pts[2 * (size_t)i + 1];
+    const uint32_t sd = gather_seed(__float_as_uint(a.w), sample);
+    Ray r;
+    const bool adm = gather_ray<MODE>(a, b, sd, r);
+    if (!adm) { r.o = mk(a.x, a.y, a.z); r.d = mk(0.0f, 0.0f, 0.0f); }
+    rays[2 * (size_t)i] = make_float4(r.o.x, r.o.y, r.o.z, __uint_as_float(0x7f800000u));
+    rays[2 * (size_t)i + 1] = make_float4(r.d.x, r.d.y, r.d.z, 0.0f);
+    seeds[i] = adm ? hash1u(sd + 7u) : 0u;
+}
+
 // Per-wave LDS staging for k_wf_trace: the current window of 32 queued rays and a ring of
 // hit records.  Keeping both in LDS takes every global load and store out of the traversal
 // loop: on gfx9 loads and stores share the wave's in-order vmcnt, so a per-lane global store
@@ -1375,6 +1462,56 @@ __global__ __launch_bounds__(256) void k_wf_accum_rays(const float* __restrict__
     o[0] = a.x; o[1] = a.y; o[2] = a.z;
 }
 
+// k_wf_accum for a gather list: one lane owns point i for the whole batch (no atomics) and adds its F
+// samples in order.  COSINE: acc[3 i + c] += clamp(L_c).  SH9: acc[27 i + 9 c + k] = fmaf(clamp(L_c), Y_k,
+// acc[..]) with the nine basis values of the sample's direction, drawn again from its seed (sbase: the
+// call's sample index of the batch's first sample); the 27 sums stay in registers.  A sample whose
+// radiance slot holds k_wf_generate_gather's -0 mark has no path and is skipped outright (fmaf(-0, Y, acc)
+// with Y < 0 would turn a -0 word into +0); a point none of whose samples has a path is not written.
+template <uint32_t MODE>
+__global__ __launch_bounds__(256) void k_wf_accum_gather(const float* __restrict__ rad, float* __restrict__ acc, GatherList gl,
+                                                         uint32_t sbase, uint32_t F) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= gl.n) return;
+    constexpr int W = MODE == GATHER_SH9 ? 27 : 3;
+    float* o = acc + W * (size_t)i;
+    float a[W];
+#pragma unroll
+    for (int k = 0; k < W; ++k) a[k] = o[k];
+    uint32_t seed = 0;
+    if constexpr (MODE == GATHER_SH9) seed = __float_as_uint(gl.pts[2 * (size_t)i].w);
+    bool any = false;
+    for (uint32_t f = 0; f < F; ++f) {
+        const float* r = rad + 3 * ((size_t)f * gl.n + i);
+        const float lx = r[0], ly = r[1], lz = r[2];
+        if (__float_as_uint(lx) == 0x80000000u) continue;  // no path
+        any = true;
+        const float L[3] = {lx >= 0.0f ? lx : 0.0f, ly >= 0.0f ? ly : 0.0f, lz >= 0.0f ? lz : 0.0f};
+        if constexpr (MODE == GATHER_SH9) {
+            const f3 d = gather_sphere_dir(gather_seed(seed, sbase + f));
+            const float Y[9] = {0.282095f,
+                                0.488603f * d.y,
+                                0.488603f * d.z,
+                                0.488603f * d.x,
+                                1.092548f * (d.x * d.y),
+                                1.092548f * (d.y * d.z),
+                                0.315392f * fmaf(3.0f * d.z, d.z, -1.0f),
+                                1.092548f * (d.x * d.z),
+                                0.546274f * fmaf(d.x, d.x, -(d.y * d.y))};
+#pragma unroll
+            for (int c = 0; c < 3; ++c)
+#pragma unroll
+                for (int k = 0; k < 9; ++k) a[9 * c + k] = fmaf(L[c], Y[k], a[9 * c + k]);
+        } else {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) a[c] = a[c] + L[c];
+        }
+    }
+    if (!any) return;
+#pragma unroll
+    for (int k = 0; k < W; ++k) o[k] = a[k];
+}
+
 // ---------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------
@@ -1475,10 +1612,10 @@ template <bool LDS, int TRAV, bool COUNT>
 static hipError_t wf_render_t(const SceneView& sc_in, const FrameParams& fp, const WfBuffers& wb, uint32_t frame0,
                               uint32_t nframes, uint32_t stride, bool accum, float* out, Counters* cnt,
                               hipStream_t stream, const WfStreams& ws, const LaunchOpts& lo, float* m2, const RectList* rl,
-                              const RayList* ql, const LensCam* cam) {
+                              const RayList* ql, const LensCam* cam, const GatherList* gl) {
     SceneView sc = bf_view<TRAV, COUNT>(sc_in);
     // paths per frame: the list's, else the window's (a ray list: its rays, a "frame" being one sample of each)
-    const uint32_t npix = ql ? ql->n : rl ? rl->npix : fp.win_w * fp.win_h;
+    const uint32_t npix = gl ? gl->n : ql ? ql->n : rl ? rl->npix : fp.win_w * fp.win_h;
     // the batch in lo.parts parts on as many streams when a part holds at least a frame: one
     // part's kernel fills the others' launch tails and boundaries (and, with separate trace and
     // shade kernels, a VALU-bound trace runs beside an HBM-bound shade)
@@ -1522,7 +1659,7 @@ static hipError_t wf_render_t(const SceneView& sc_in, const FrameParams& fp, con
     constexpr bool kNarrowOk = flv_fused(TRAV) && LDS && !COUNT;
     const bool narrow = kNarrowOk && sc.bfnode && sc.bfnarrow;
     if constexpr (flv_fused(TRAV)) {  // the camera batches' table (k_wf_camtab), before every part's GEN launch
-        if (lo.fuse_gen && !rl && !ql && !cam) {
+        if (lo.fuse_gen && !rl && !ql && !cam && !gl) {
             if (sc.n_tris - sc.mb_base > 64) return hipErrorInvalidValue;  // mailbox scenes: <= 64 entries
             hipLaunchKernelGGL(k_wf_camtab, dim3(1), dim3(64), 0, stream, sc, fp, wb.camtab);
         }
@@ -1571,11 +1708,12 @@ static hipError_t wf_render_t(const SceneView& sc_in, const FrameParams& fp, con
         // (and a ray list's from k_wf_generate_rays, which appends to the queue's count or its regions' count
         // slots 0: zeroed here with slot 1, as k_wf_generate would have set them)
         // (and a lens camera's from k_wf_generate_cam, which compacts as k_wf_generate_rays does)
-        const bool fgen = flv_fused(TRAV) && lo.fuse_gen && !rl && !ql && !cam;
+        // (and a gather list's from k_wf_generate_gather, likewise)
+        const bool fgen = flv_fused(TRAV) && lo.fuse_gen && !rl && !ql && !cam && !gl;
         if (fgen)
             for (int h = 0; h < nh; ++h)
                 HIP_RETURN_IF(hipMemsetAsync(pv[h].w.rcnt + kRegions, 0, kRegions * sizeof(uint32_t), stream));
-        if (ql || cam)
+        if (ql || cam || gl)
             for (int h = 0; h < nh; ++h) {
                 HIP_RETURN_IF(hipMemsetAsync(pv[h].w.ctl + WF_COUNT0, 0, 2 * sizeof(uint32_t), stream));
                 if (flv_fused(TRAV)) HIP_RETURN_IF(hipMemsetAsync(pv[h].w.rcnt, 0, 2 * kRegions * sizeof(uint32_t), stream));
@@ -1601,7 +1739,15 @@ static hipError_t wf_render_t(const SceneView& sc_in, const FrameParams& fp, con
         }
         for (int h = 0; h < nh && !fgen; ++h) {
             const dim3 ggrid((std::max(pv[h].P, pv[h].w.nreg) + 255) / 256);
-            if (ql) {
+            if (gl) {
+                const dim3 qgrid((pv[h].P + 1023) / 1024);
+                if (gl->mode == GATHER_SH9)
+                    PT_LAUNCH(KID_WF_GENERATE, pv[h].st, (k_wf_generate_gather<COUNT, GATHER_SH9>), qgrid, dim3(1024), 0,
+                              pv[h].st, pv[h].w, *gl, frame0, pv[h].fbase, pv[h].P, cnt);
+                else
+                    PT_LAUNCH(KID_WF_GENERATE, pv[h].st, (k_wf_generate_gather<COUNT, GATHER_COSINE>), qgrid, dim3(1024), 0,
+                              pv[h].st, pv[h].w, *gl, frame0, pv[h].fbase, pv[h].P, cnt);
+            } else if (ql) {
                 PT_LAUNCH(KID_WF_GENERATE, pv[h].st, (k_wf_generate_rays<COUNT>), dim3((pv[h].P + 1023) / 1024), dim3(1024), 0,
                           pv[h].st, pv[h].w, *ql, frame0, pv[h].fbase, pv[h].P, cnt);
             } else if (cam) {
@@ -1708,7 +1854,13 @@ static hipError_t wf_render_t(const SceneView& sc_in, const FrameParams& fp, con
                 HIP_RETURN_IF(hipStreamWaitEvent(stream, ws.join[h], 0));
             }
         }
-        if (ql)
+        if (gl && gl->mode == GATHER_SH9)
+            PT_LAUNCH(KID_WF_ACCUM, stream, (k_wf_accum_gather<GATHER_SH9>), dim3((npix + 255) / 256), dim3(256), 0, stream,
+                      wb.rad, out, *gl, frame0 + fb, Fb);
+        else if (gl)
+            PT_LAUNCH(KID_WF_ACCUM, stream, (k_wf_accum_gather<GATHER_COSINE>), dim3((npix + 255) / 256), dim3(256), 0, stream,
+                      wb.rad, out, *gl, frame0 + fb, Fb);
+        else if (ql)
             PT_LAUNCH(KID_WF_ACCUM, stream, k_wf_accum_rays, dim3((npix + 255) / 256), dim3(256), 0, stream, wb.rad, out, *ql, Fb);
         else if (rl)
             PT_LAUNCH(KID_WF_ACCUM, stream, (k_wf_accum<RectList>), dim3((npix + 255) / 256), dim3(256), 0, stream, wb.rad, out,
@@ -1723,8 +1875,9 @@ static hipError_t wf_render_t(const SceneView& sc_in, const FrameParams& fp, con
 hipError_t launch_wavefront(const LaunchOpts& lo, const SceneView& sc, const FrameParams& fp, const WfBuffers& wb,
                             uint32_t frame0, uint32_t nframes, uint32_t stride, bool accum, bool count, float* out,
                             Counters* cnt, hipStream_t stream, const WfStreams& ws, float* m2, const RectList* rl,
-                            const RayList* ql, const LensCam* cam) {
-    if ((m2 || rl || ql) && !accum) return hipErrorInvalidValue;
+                            const RayList* ql, const LensCam* cam, const GatherList* gl) {
+    if ((m2 || rl || ql || gl) && !accum) return hipErrorInvalidValue;
+    if (gl && (m2 || rl || ql || cam || stride != 1 || gl->n == 0 || gl->mode > GATHER_SH9)) return hipErrorInvalidValue;
     if (cam && (ql || cam->model < CAM_THIN_LENS || cam->model > CAM_EQUIRECT)) return hipErrorInvalidValue;
     if (ql && (m2 || rl || stride != 1 || ql->n == 0)) return hipErrorInvalidValue;
     if (!accum) { nframes = 1; stride = 1; }
@@ -1733,7 +1886,7 @@ hipError_t launch_wavefront(const LaunchOpts& lo, const SceneView& sc, const Fra
     // (pt_capi.hip shape_view: option leaf_pre, default on) and the buffers exist
     const int trav = select_wavefront(lo, sc.fast_rcp != 0, sc.mailbox != 0, sc.big_leaf > 0, sc.npre > 0 && sc.pre && wb.pres);
     // sc.node_bias <= 0: chosen per instance in wf_render_t
-#define WF_ARGS sc, fp, wb, frame0, nframes, stride, accum, out, cnt, stream, ws, lo, m2, rl, ql, cam
+#define WF_ARGS sc, fp, wb, frame0, nframes, stride, accum, out, cnt, stream, ws, lo, m2, rl, ql, cam, gl
 #define WF(T)                                                                                                        \
     case T:                                                                                                          \
         return lds ? (count ? wf_render_t<true, T, true>(WF_ARGS) : wf_render_t<true, T, false>(WF_ARGS))            \
@@ -1742,6 +1895,18 @@ hipError_t launch_wavefront(const LaunchOpts& lo, const SceneView& sc, const Fra
 #undef WF_ARGS
 #undef WF
     return hipErrorInvalidValue;
+}
+
+hipError_t launch_gather_rays(const GatherList& gl, uint32_t sample, void* rays, uint32_t* seeds, hipStream_t stream) {
+    if (gl.n == 0 || gl.mode > GATHER_SH9) return hipErrorInvalidValue;
+    const dim3 grid((gl.n + 255) / 256), block(256);
+    if (gl.mode == GATHER_SH9)
+        PT_LAUNCH(KID_GATHER_RAYS, stream, (k_gather_rays<GATHER_SH9>), grid, block, 0, stream, gl, sample,
+                  static_cast<float4*>(rays), seeds);
+    else
+        PT_LAUNCH(KID_GATHER_RAYS, stream, (k_gather_rays<GATHER_COSINE>), grid, block, 0, stream, gl, sample,
+                  static_cast<float4*>(rays), seeds);
+    return hipGetLastError();
 }
 
 }  // namespace pt

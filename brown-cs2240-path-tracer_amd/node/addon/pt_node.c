@@ -729,6 +729,74 @@ static napi_value js_query_radiance(napi_env env, napi_callback_info info) {
     return res;
 }
 
+/* gather(scene, Float32Array points[8n], nsamples, sample0, mode, maxDepth, rr, directOnly[, Float32Array
+ * accum[3n | 27n]]) -> Float32Array[3n | 27n]: pt_gather — points are pt_gather_point records (p.xyz, seed as
+ * uint32 bits, n.xyz, 0); mode 0 = cosine (3 sums per point), 1 = SH9 (27).  Blocking.
+ * gatherRays(scene, points, sample, mode) -> { rays: Float32Array[8n], seeds: Uint32Array[n] }: pt_gather_rays. */
+static napi_value js_gather(napi_env env, napi_callback_info info) {
+    size_t argc = 9;
+    napi_value argv[9];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    float *pts, *acc = NULL;
+    size_t pl, al = 0;
+    pt_gather_params prm;
+    double rr = 0.0;
+    bool direct = false;
+    pt_scene* s = argc >= 8 ? get_scene(env, argv[0]) : NULL;
+    int ok = s && get_f32(env, argv[1], &pts, &pl) && pl % 8 == 0;
+    ok = ok && get_u32(env, argv[2], &prm.nsamples) && get_u32(env, argv[3], &prm.sample0) && get_u32(env, argv[4], &prm.mode) &&
+         prm.mode <= PT_GATHER_SH9 && get_i32(env, argv[5], &prm.max_depth) && napi_get_value_double(env, argv[6], &rr) == napi_ok &&
+         napi_get_value_bool(env, argv[7], &direct) == napi_ok;
+    const size_t n = ok ? pl / 8 : 0, w = ok && prm.mode == PT_GATHER_SH9 ? 27 : 3;
+    if (ok && argc >= 9) {
+        napi_valuetype vt;
+        if (napi_typeof(env, argv[8], &vt) != napi_ok) ok = 0;
+        else if (vt != napi_undefined && vt != napi_null) ok = get_f32(env, argv[8], &acc, &al) && al == w * n;
+    }
+    if (!ok) {
+        if (!pending_exception(env))
+            napi_throw_type_error(env, NULL, "gather(scene, Float32Array points[8n], nsamples, sample0, mode (0 | 1), maxDepth, rr, "
+                                             "directOnly[, Float32Array accum[3n | 27n]])");
+        return NULL;
+    }
+    prm.rr_prob = (float)rr;
+    prm.direct_only = direct ? 1 : 0;
+    void* out = NULL;
+    napi_value res = new_typedarray(env, napi_float32_array, w * n, &out);
+    if (!res) return NULL;
+    if (acc) memcpy(out, acc, w * n * sizeof(float));  /* a new ArrayBuffer is zeroed */
+    const int rc = pt_gather(s, (const pt_gather_point*)pts, n, &prm, (float*)out, NULL);
+    if (rc) return throw_pt(env, rc);
+    return res;
+}
+
+static napi_value js_gather_rays(napi_env env, napi_callback_info info) {
+    size_t argc = 4;
+    napi_value argv[4];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    float* pts;
+    size_t pl;
+    uint32_t sample, mode;
+    pt_scene* s = argc >= 4 ? get_scene(env, argv[0]) : NULL;
+    if (!s || !get_f32(env, argv[1], &pts, &pl) || pl % 8 != 0 || !get_u32(env, argv[2], &sample) || !get_u32(env, argv[3], &mode)) {
+        if (!pending_exception(env)) napi_throw_type_error(env, NULL, "gatherRays(scene, Float32Array points[8n], sample, mode (0 | 1))");
+        return NULL;
+    }
+    const size_t n = pl / 8;
+    void *rays = NULL, *seeds = NULL;
+    napi_value jr = new_typedarray(env, napi_float32_array, 8 * n, &rays);
+    if (!jr) return NULL;
+    napi_value js = new_typedarray(env, napi_uint32_array, n, &seeds);
+    if (!js) return NULL;
+    const int rc = pt_gather_rays(s, (const pt_gather_point*)pts, n, mode, sample, (pt_ray*)rays, (uint32_t*)seeds);
+    if (rc) return throw_pt(env, rc);
+    napi_value res;
+    CHECK_NAPI(env, napi_create_object(env, &res));
+    CHECK_NAPI(env, napi_set_named_property(env, res, "rays", jr));
+    CHECK_NAPI(env, napi_set_named_property(env, res, "seeds", js));
+    return res;
+}
+
 /* cameraRays(scene, meta, frame[, [x0, y0, w, h]]) -> Float32Array[8 w h]: pt_camera_rays, the rays the render
  * traces for the window's pixels in that frame, row-major, tmax = +inf.
  * cameraSeeds(same arguments) -> Uint32Array[w h]: pt_camera_seeds, the seeds it hands to radiance() there. */
@@ -985,6 +1053,8 @@ static napi_value init(napi_env env, napi_value exports) {
         {"cameraRays", NULL, js_camera_rays, NULL, NULL, NULL, napi_default, NULL},
         {"cameraSeeds", NULL, js_camera_seeds, NULL, NULL, NULL, napi_default, NULL},
         {"queryRadiance", NULL, js_query_radiance, NULL, NULL, NULL, napi_default, NULL},
+        {"gather", NULL, js_gather, NULL, NULL, NULL, napi_default, NULL},
+        {"gatherRays", NULL, js_gather_rays, NULL, NULL, NULL, napi_default, NULL},
         {"frame", NULL, js_frame, NULL, NULL, NULL, napi_enumerable, NULL},
         {"tonemap", NULL, js_tonemap, NULL, NULL, NULL, napi_enumerable, NULL},
         {"profileEnable", NULL, js_profile_enable, NULL, NULL, NULL, napi_enumerable, NULL},

@@ -13,6 +13,10 @@
 //  library's; the whole image only, without --counters, --spp at least 2) [--feature-frames N] (frames of its guide buffers, default 4)
 // [--pick x,y] (print what the frame-0 camera ray of pixel (x, y) hits — point, distance, normal, material —
 //  as one JSON line and render nothing: pt_camera_rays + pt_query_hits)
+// [--irradiance x,y,z,nx,ny,nz] [--probe x,y,z] [--samples N] [--seed S] (print, as one JSON line, what pt_gather
+//  collects at that point and render nothing: --irradiance the cosine-weighted irradiance at a surface point
+//  with normal n (any length), pi / N times the gather's sums; --probe the 27 SH9 radiance coefficients of a
+//  probe, 4 pi / N times the sums, channel c's coefficient k at 9 c + k; N = --samples, default 256)
 // [--camera thinlens|ortho|equirect] [--aperture R] [--focus-distance F] (a lens camera evaluated on the device,
 //  pt_scene_set_camera: jittered like the pinhole, thinlens with depth of field from a lens of radius R (default 0)
 //  focused at distance F (default |focus - position| of the scene's camera); combines with --window, the rectangle
@@ -69,6 +73,7 @@ async function main(argv) {
         denoise = { iters: +it, featureFrames: +ff };
     }
     if (args.pick !== undefined) return pick(args);
+    if (args.irradiance !== undefined || args.probe !== undefined) return gather(args);
     const projection = args.projection === undefined ? 'pinhole' : String(args.projection);
     if (!['pinhole', 'equirect', 'ortho'].includes(projection) ||
         (projection !== 'pinhole' && (window || rects || denoise || args.counters === '1'))) {
@@ -191,6 +196,33 @@ function pick(args) {
             ray: { o: Array.from(ray.subarray(0, 3)), d: Array.from(ray.subarray(4, 7)) },
             p: Array.from(h.subarray(0, 3)), t: h[3], n: Array.from(h.subarray(4, 7)), material,
             bits: Array.from(new Uint32Array(h.buffer, h.byteOffset, 8)) }));
+    } finally {
+        pt.sceneDestroy(scene);
+    }
+}
+// --irradiance x,y,z,nx,ny,nz | --probe x,y,z: one gather point through pt_gather, scaled, as one JSON line
+function gather(args) {
+    const probe = args.probe !== undefined, text = String(probe ? args.probe : args.irradiance);
+    const v = text.split(',').map(Number), ns = args.samples === undefined ? 256 : Number(args.samples);
+    const seed = args.seed === undefined ? 1 : Number(args.seed);
+    if (v.length !== (probe ? 3 : 6) || !v.every(Number.isFinite) || !(Number.isInteger(ns) && ns >= 1 && ns <= 0x7fffffff) ||
+        !(Number.isInteger(seed) && seed >= 0 && seed <= 0xffffffff) || (args.probe !== undefined && args.irradiance !== undefined)) {
+        console.error('usage: pt-render.js <scene.ini> --irradiance x,y,z,nx,ny,nz | --probe x,y,z [--samples N] [--seed S]: ' + text);
+        process.exit(2);
+    }
+    const s = host.load_scene_from_ini(args._[0], { web_root: args.web_root, quiet: true });
+    const meta = host.make_meta(s.screenDimension, s.camera_data, s.scene_description, 0);
+    const pt = host.native();
+    const scene = pt.sceneCreate(s.primitive_data[0].triangle_data, s.primitive_data[0].bvh_data, parseInt(args.device || '0'));
+    try {
+        if (args.vertex_normals === '1') pt.sceneSetVertexNormals(scene, true);
+        const points = host.gatherPoints(v.slice(0, 3), probe ? [0, 0, 0] : v.slice(3, 6), [seed]);
+        const sums = host.gather(scene, points, { nsamples: ns, mode: probe ? 'sh9' : 'cosine', maxDepth: parseInt(args.max_depth || '16'),
+            rr: meta[45], directOnly: meta[46] > 0 });
+        const k = (probe ? 4 : 1) * Math.PI / ns;
+        const scaled = Array.from(sums, (x) => x * k);
+        console.log(JSON.stringify(probe ? { probe: v, samples: ns, seed, sh9: scaled }
+                                         : { irradiance: scaled, point: v.slice(0, 3), normal: v.slice(3, 6), samples: ns, seed }));
     } finally {
         pt.sceneDestroy(scene);
     }

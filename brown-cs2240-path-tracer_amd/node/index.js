@@ -50,6 +50,36 @@ const unitRays = (o, d) => {
     }
     return rays;
 };
+// Irradiance gathers: the directions are drawn on the device (include/pt_hip.h pt_gather).
+//   gatherPoints(p, n, seeds) -> Float32Array[8k]: pt_gather_point records from 3k coordinates, 3k normal
+//       components (any admitted length; ignored by 'sh9') and k uint32 seeds
+//   gather(scene, points, { nsamples, sample0 = 0, mode = 'cosine' | 'sh9', maxDepth = 8, rr = 0.9, directOnly = false,
+//       accum }) -> Float32Array[3k | 27k]: per point the clamped radiance of samples sample0 .. sample0 + nsamples - 1,
+//       summed ('cosine': irradiance = pi / N times it) or weighted by the nine SH basis values of the direction
+//       ('sh9': coefficient j of channel c at 9 c + j, scale by 4 pi / N), onto a copy of accum if given
+//   gatherRays(scene, points, sample, mode = 'cosine') -> { rays, seeds }: that sample of every point as the
+//       inputs of queryRadiance({ nsamples: 1 })
+const GATHER_MODES = ['cosine', 'sh9'];
+const gatherMode = (mode) => {
+    const m = typeof mode === 'string' ? GATHER_MODES.indexOf(mode) : mode;
+    if (m !== 0 && m !== 1) throw new TypeError(`gather mode must be 'cosine' or 'sh9', not ${mode}`);
+    return m;
+};
+const gatherPoints = (p, n, seeds) => {
+    const k = seeds.length, out = new Float32Array(8 * k), bits = new Uint32Array(out.buffer);
+    if (p.length !== 3 * k || n.length !== 3 * k) throw new TypeError('gatherPoints(p[3k], n[3k], seeds[k])');
+    for (let i = 0; i < k; ++i) {
+        out.set([p[3 * i], p[3 * i + 1], p[3 * i + 2]], 8 * i);
+        out.set([n[3 * i], n[3 * i + 1], n[3 * i + 2]], 8 * i + 4);
+        bits[8 * i + 3] = seeds[i];
+    }
+    return out;
+};
+const gather = (scene, points, params = {}) => {
+    const { nsamples = 1, sample0 = 0, mode = 'cosine', maxDepth = 8, rr = 0.9, directOnly = false, accum = null } = params;
+    return addon.load().gather(scene, points, nsamples, sample0, gatherMode(mode), maxDepth, rr, !!directOnly, accum);
+};
+const gatherRays = (scene, points, sample = 0, mode = 'cosine') => addon.load().gatherRays(scene, points, sample, gatherMode(mode));
 
 module.exports = {
     parse_ini_file, ini_file_to_ini_scene, parse_obj, BVH, pack_scene_object_group, pack_bvh,
@@ -60,4 +90,5 @@ module.exports = {
     load_scene_xml_file: scene.load_scene_xml_file,
     programEntry, make_meta, check_window, check_rects, MODE, encode_png, native: addon.load,
     queryHits, queryOccluded, cameraRays, queryRadiance, cameraSeeds, unitRays,
+    gather, gatherRays, gatherPoints,
 };

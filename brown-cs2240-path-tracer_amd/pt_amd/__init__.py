@@ -55,5 +55,9 @@ from ._lib import (  # noqa: F401
     tile_rects,
     tonemap,
     unit_rays,
+    gather_points,
+    sh9_basis,
+    sh9_irradiance,
+    GATHER_MODES,
 )
 from .host import PackedScene, load_scene, program_entry  # noqa: F401

@@ -13,7 +13,7 @@ ABI_VERSION = 3  # include/pt_hip.h PT_ABI_VERSION
 _CSRC = os.path.join(_PKG_ROOT, "csrc")
 # csrc/Makefile BUILD_SRCS: the sources whose SHA-256 the library carries as pt_build_id()
 _BUILD_SRCS = ["pt_kernels.hip", "pt_wavefront.hip", "pt_leafpass.hip", "pt_image.hip", "pt_features.hip", "pt_denoise.hip", "pt_query.hip", "pt_capi.hip", "pt_capi_render.hip",
-               "pt_capi_adaptive.hip", "pt_capi_denoise.hip", "pt_capi_query.hip", "pt_capi_radiance.hip", "pt_capi_selftest.hip",
+               "pt_capi_adaptive.hip", "pt_capi_denoise.hip", "pt_capi_query.hip", "pt_capi_radiance.hip", "pt_capi_gather.hip", "pt_capi_selftest.hip",
                "pt_capi_multi.hip", "pt_capi_camera.hip", "pt_capi_internal.h", "pt_math.h", "pt_flavour.h", "pt_layout.h",
                "pt_device.h", "pt_path.h", "pt_kernels.h", "../../include/pt_hip.h", "pt_bvh.cpp", "pt_leafbvh.h",
                "pt_leafbvh.cpp", "pt_leafskip.cpp", "pt_scene_layout.h", "pt_scene_layout.cpp", "pt_rect_plan.h",
@@ -53,6 +53,15 @@ class RadianceParams(ctypes.Structure):
     """pt_radiance_params."""
     _fields_ = [("rr_prob", ctypes.c_float), ("direct_only", ctypes.c_int32), ("max_depth", ctypes.c_int32),
                 ("nsamples", ctypes.c_uint32)]
+
+
+class GatherParams(ctypes.Structure):
+    """pt_gather_params."""
+    _fields_ = [("rr_prob", ctypes.c_float), ("direct_only", ctypes.c_int32), ("max_depth", ctypes.c_int32),
+                ("sample0", ctypes.c_uint32), ("nsamples", ctypes.c_uint32), ("mode", ctypes.c_uint32)]
+
+
+GATHER_MODES = ("cosine", "sh9")  # PT_GATHER_COSINE, PT_GATHER_SH9, by value
 
 
 CAMERA_MODELS = ("pinhole", "thin_lens", "ortho", "equirect")  # pt_camera_model, by value
@@ -250,6 +259,65 @@ def _fma32(a, b, c):
     return np.where(tie, other, r).astype(np.float32)
 
 
+def _gather_mode(mode) -> int:
+    if isinstance(mode, str):
+        if mode not in GATHER_MODES:
+            raise PtError(-1, f"mode must be one of {GATHER_MODES}, not {mode!r}")
+        return GATHER_MODES.index(mode)
+    return _uint(mode, "mode")
+
+
+def gather_points(points, normals, seeds) -> np.ndarray:
+    """[n, 8] f32 pt_gather_point records from points and normals ([n, 3]; normals None: zeros, for
+    sh9) and seeds ([n] uint32, stored by their bits in column 3); column 7 (reserved) is 0."""
+    p32 = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+    n = p32.shape[0]
+    n32 = np.zeros((n, 3), np.float32) if normals is None else np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+    sd = np.ascontiguousarray(seeds, np.uint32).reshape(-1)
+    if n32.shape[0] != n or sd.shape[0] != n:
+        raise PtError(-1, f"points, normals and seeds must hold as many entries ({n}, {n32.shape[0]}, {sd.shape[0]})")
+    out = np.zeros((n, 8), np.float32)
+    out[:, 0:3] = p32
+    out[:, 4:7] = n32
+    out.view(np.uint32)[:, 3] = sd
+    return out
+
+
+def sh9_basis(d) -> np.ndarray:
+    """[n, 9] f32: the nine real SH basis values of the directions d ([n, 3] f32) as pt_gather's SH9 mode
+    weights a sample, operation by operation in f32 (include/pt_hip.h)."""
+    v = np.ascontiguousarray(d, np.float32).reshape(-1, 3)
+    x, y, z = v[:, 0], v[:, 1], v[:, 2]
+    f = np.float32
+    with np.errstate(all="ignore"):
+        out = np.empty((v.shape[0], 9), np.float32)
+        out[:, 0] = f(0.282095)
+        out[:, 1] = f(0.488603) * y
+        out[:, 2] = f(0.488603) * z
+        out[:, 3] = f(0.488603) * x
+        out[:, 4] = f(1.092548) * (x * y)
+        out[:, 5] = f(1.092548) * (y * z)
+        out[:, 6] = f(0.315392) * _fma32(f(3.0) * z, z, np.full_like(z, -1.0))
+        out[:, 7] = f(1.092548) * (x * z)
+        out[:, 8] = f(0.546274) * _fma32(x, x, -(y * y))
+    return out
+
+
+def sh9_irradiance(coeffs, normals) -> np.ndarray:
+    """Irradiance [n, 3] (f64) at unit normals ([n, 3]) from SH9 radiance coefficients ([n, 27] or
+    [n, 3, 9], already scaled by 4 pi / N): the cosine-lobe convolution of Ramamoorthi and Hanrahan
+    (2001) — band l scaled by A_l = pi, 2 pi / 3, pi / 4 — evaluated with the basis of sh9_basis."""
+    c = np.asarray(coeffs, np.float64).reshape(-1, 3, 9)
+    nrm = np.asarray(normals, np.float64).reshape(-1, 3)
+    if nrm.shape[0] != c.shape[0]:
+        raise PtError(-1, f"coeffs and normals must hold as many entries ({c.shape[0]} and {nrm.shape[0]})")
+    x, y, z = nrm[:, 0], nrm[:, 1], nrm[:, 2]
+    Y = np.stack([np.full_like(x, 0.282095), 0.488603 * y, 0.488603 * z, 0.488603 * x, 1.092548 * x * y, 1.092548 * y * z,
+                  0.315392 * (3.0 * z * z - 1.0), 1.092548 * x * z, 0.546274 * (x * x - y * y)], axis=1)
+    A = np.array([np.pi] + [2.0 * np.pi / 3.0] * 3 + [np.pi / 4.0] * 5)
+    return np.einsum("nck,nk->nc", c, Y * A)
+
+
 def unit_rays(o, d) -> np.ndarray:
     """[n, 8] f32 rays for query_radiance from origins o and directions d (both [n, 3], any length):
     tmax = +inf, reserved = 0, and d normalised in f32 with the reference's operations — d / sqrt(fma(dz,
@@ -379,6 +447,12 @@ def load_library():
     L.pt_camera_seeds.argtypes = [p, p, wp, u32, p]
     L.pt_camera_seeds_async.argtypes = [p, p, wp, u32, p, p]
     for fn in ("pt_query_radiance", "pt_query_radiance_async", "pt_camera_seeds", "pt_camera_seeds_async"):
+        getattr(L, fn).restype = i
+    L.pt_gather.argtypes = [p, p, sz, ctypes.POINTER(GatherParams), p, p]
+    L.pt_gather_async.argtypes = [p, p, sz, ctypes.POINTER(GatherParams), p, p, p]
+    L.pt_gather_rays.argtypes = [p, p, sz, u32, u32, p, p]
+    L.pt_gather_rays_async.argtypes = [p, p, sz, u32, u32, p, p, p]
+    for fn in ("pt_gather", "pt_gather_async", "pt_gather_rays", "pt_gather_rays_async"):
         getattr(L, fn).restype = i
     L.pt_denoise_defaults.argtypes = [dpp]
     L.pt_denoise_defaults.restype = None
@@ -929,6 +1003,56 @@ class Scene:
                                                  ctypes.c_void_p(d_seeds_ptr or None), n, ctypes.byref(prm),
                                                  ctypes.c_void_p(d_accum_ptr or None),
                                                  ctypes.c_void_p(d_counters_ptr or None), ctypes.c_void_p(stream_ptr or None)))
+
+    def gather(self, points, normals, seeds, nsamples: int, sample0: int = 0, mode="cosine", max_depth: int = 8,
+               rr: float = 0.9, direct_only: bool = False, out=None, counters: bool = False):
+        """pt_gather: samples sample0 .. sample0 + nsamples - 1 of every point (points, normals [n, 3] f32,
+        seeds [n] uint32; normals may be None for "sh9"), their directions drawn on the device.  Returns
+        the sums — [n, 3] f32 for "cosine" (irradiance = pi / N times it), [n, 27] for "sh9" (coefficient
+        k of channel c at 9 c + k; scale by 4 pi / N) — added to `out` (left untouched) if given; and the
+        counters if requested.  A point or sample that is not admitted adds nothing."""
+        m = _gather_mode(mode)
+        pts = gather_points(points, normals, seeds)
+        n, w = pts.shape[0], 27 if m == 1 else 3
+        if out is None:
+            acc = np.zeros((n, w), np.float32)
+        else:
+            acc = np.array(out, np.float32, copy=True, order="C")
+            if acc.shape != (n, w):
+                raise PtError(-1, f"out must be [n, {w}] f32 with n = {n}, not {acc.shape}")
+        prm = GatherParams(float(rr), 1 if direct_only else 0, int(max_depth), _uint(sample0, "sample0"),
+                           _uint(nsamples, "nsamples"), m)
+        c = Counters()
+        _check(self._lib.pt_gather(self._h, _ptr(pts), n, ctypes.byref(prm), _ptr(acc), ctypes.byref(c) if counters else None))
+        return (acc, c.as_dict()) if counters else acc
+
+    def gather_async(self, d_points_ptr: int, n: int, d_accum_ptr: int, nsamples: int, sample0: int = 0, mode="cosine",
+                     max_depth: int = 8, rr: float = 0.9, direct_only: bool = False, stream_ptr: int = 0,
+                     d_counters_ptr: int = 0):
+        """pt_gather_async: n pt_gather_point records (gather_points; 16-byte aligned) and the [n, 3] or
+        [n, 27] f32 accumulator (in/out) in device memory, asynchronous on the stream."""
+        prm = GatherParams(float(rr), 1 if direct_only else 0, int(max_depth), _uint(sample0, "sample0"),
+                           _uint(nsamples, "nsamples"), _gather_mode(mode))
+        _check(self._lib.pt_gather_async(self._h, ctypes.c_void_p(d_points_ptr or None), n, ctypes.byref(prm),
+                                         ctypes.c_void_p(d_accum_ptr or None), ctypes.c_void_p(d_counters_ptr or None),
+                                         ctypes.c_void_p(stream_ptr or None)))
+
+    def gather_rays(self, points, normals, seeds, sample: int = 0, mode="cosine"):
+        """pt_gather_rays: (rays [n, 8] f32, seeds [n] uint32) of sample `sample` of every point — the inputs
+        with which query_radiance(nsamples=1) repeats that sample of a "cosine" gather.  A point or sample
+        that is not admitted gets a zero direction and seed 0."""
+        pts = gather_points(points, normals, seeds)
+        n = pts.shape[0]
+        rays, sd = np.zeros((n, 8), np.float32), np.zeros(n, np.uint32)
+        _check(self._lib.pt_gather_rays(self._h, _ptr(pts), n, _gather_mode(mode), _uint(sample, "sample"), _ptr(rays), _ptr(sd)))
+        return rays, sd
+
+    def gather_rays_async(self, d_points_ptr: int, n: int, sample: int, d_rays_ptr: int, d_seeds_ptr: int, mode="cosine",
+                          stream_ptr: int = 0):
+        """pt_gather_rays_async: device pointers (points and rays 16-byte, seeds 4-byte aligned)."""
+        _check(self._lib.pt_gather_rays_async(self._h, ctypes.c_void_p(d_points_ptr or None), n, _gather_mode(mode),
+                                              _uint(sample, "sample"), ctypes.c_void_p(d_rays_ptr or None),
+                                              ctypes.c_void_p(d_seeds_ptr or None), ctypes.c_void_p(stream_ptr or None)))
 
     def camera_seeds(self, meta, window=None, frame: int = 0) -> np.ndarray:
         """pt_camera_seeds: [h, w] uint32, the seed the render hands to radiance() for the window's pixels

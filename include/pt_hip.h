@@ -470,6 +470,62 @@ int pt_camera_seeds(pt_scene* scene, const float meta[48], const pt_window* win,
 int pt_camera_seeds_async(pt_scene* scene, const float meta[48], const pt_window* win, uint32_t frame, uint32_t* d_seeds,
                           void* stream);
 
+/* Irradiance gathers: lightmap texels and spherical-harmonic probes sampled on the device.  A radiance
+ * query needs one direction per (point, sample) from the caller; a gather draws them itself, with the
+ * reference's own samplers, and reduces the paths' radiance per point.  Every float operation below is
+ * f32 and as written; an FMA appears only where fmaf is written.
+ * Seeds.  For point i and sample s = sample0 .. sample0 + nsamples - 1:
+ *   sd = s == 0 ? seed : hash1u(seed + s * 16787u)   (u32 wrap; the radiance queries' rule);
+ *   the direction is drawn with sd; the path gets seed_in = (int32)hash1u(sd + 7u), the reference's own
+ *   idiom for "the next decision".
+ * PT_GATHER_COSINE.  nn = fmaf(n.z, n.z, fmaf(n.y, n.y, n.x * n.x)); the point is ADMITTED iff
+ *   2^-80 <= nn <= 2^80 (a NaN fails).  nh = n / sqrt(nn) per component by IEEE division (the reference's
+ *   normalize: the call normalises itself, since a normal off unit length by 2^-21 already pushes the
+ *   generated direction to the admission band's edge).  The ray is the reference's
+ *   sample_hemisphere((p, 1), (nh, 0), sd) (samplers.wgsl:15-46), origin fma(0.001, d, p) included: the
+ *   reference's diffuse bounce from that point.  Its pdf is not used: the estimator's weight is pi.
+ * PT_GATHER_SH9.  The normal is ignored and every point is admitted.  xi = hash2(sd * 7u + 11u);
+ *   phi = (2 * 3.14159f) * xi[0]; z = fmaf(-2, xi[1], 1); r = sqrt(max(fmaf(-z, z, 1), 0)); (s, c) = the
+ *   pinned sincos of phi; d = (r * c, r * s, z); the origin is p itself.
+ * Sample admission.  Each generated direction takes pt_query_radiance's test (|q - 1| <= 2^-18).  A sample
+ * or point that is not admitted is never traced, adds to no counter, and leaves every accumulator word it
+ * would have touched with its bits unchanged (-0, NaN and infinities included).
+ * The path.  L = the reference's radiance(ray, seed_in) with the params' rr_prob, direct_only != 0 and
+ * max_depth, bit for bit; pt_scene_set_vertex_normals is honoured.  Lc = (L_c >= 0 ? L_c : 0).
+ *   COSINE: accum[3 i + c] += Lc, in sample order; the irradiance is pi / N times the sum.
+ *   SH9:    accum[27 i + 9 c + k] = fmaf(Lc, Y_k, accum[..]), in sample order, with
+ *           Y0 = 0.282095f            Y1 = 0.488603f * y        Y2 = 0.488603f * z
+ *           Y3 = 0.488603f * x        Y4 = 1.092548f * (x * y)  Y5 = 1.092548f * (y * z)
+ *           Y6 = 0.315392f * fmaf(3 * z, z, -1)                 Y7 = 1.092548f * (x * z)
+ *           Y8 = 0.546274f * fmaf(x, x, -(y * y));              the caller scales by 4 pi / N.
+ * Composition.  Two calls over samples [0, a) and [a, b) equal one call over [0, b), bit for bit.
+ * pt_gather_rays hands out sample `sample` of every point as pt_ray {o, +inf, d, 0} and seeds[i] =
+ * hash1u(sd + 7u); a point or sample that is not admitted gets d = 0 (o = p) and seed 0, which
+ * pt_query_radiance also rejects.  So pt_gather_rays + pt_query_radiance(nsamples = 1) over the samples
+ * in order repeats a COSINE gather, bit for bit.
+ * Counters (nullable, added to): as pt_query_radiance; samples += admitted samples.
+ * n = 0 or nsamples = 0: PT_OK, nothing is touched.  PT_ERR_INVALID: params NULL; an unknown mode;
+ * n > 2^26; sample0 + nsamples > 2^31 (pt_gather_rays: sample >= 2^31); max_depth < 0 or > 1024; a null
+ * pointer with n > 0; and, in the _async forms, points or rays not 16-byte aligned, or accum / seeds not
+ * 4-byte aligned.  rr_prob is unchecked, as in pt_query_radiance.
+ * Batching, options, watchdog and the blocking form's scratch are pt_query_radiance's: always the
+ * wavefront pipeline, whole samples of all n points per batch, leaf_pre off unless set to 1;
+ * kernel=mega|literal, regen and fuse_gen do not apply. */
+typedef struct { float p[3]; uint32_t seed; float n[3]; uint32_t reserved; } pt_gather_point; /* 32 B */
+enum { PT_GATHER_COSINE = 0, PT_GATHER_SH9 = 1 };
+typedef struct {
+    float rr_prob; int32_t direct_only; int32_t max_depth;
+    uint32_t sample0; uint32_t nsamples; uint32_t mode;
+} pt_gather_params;
+int pt_gather(pt_scene* scene, const pt_gather_point* pts, size_t n, const pt_gather_params* params, float* accum,
+              pt_counters* counters);
+int pt_gather_async(pt_scene* scene, const pt_gather_point* d_pts, size_t n, const pt_gather_params* params, float* d_accum,
+                    pt_counters* d_counters, void* stream);
+int pt_gather_rays(pt_scene* scene, const pt_gather_point* pts, size_t n, uint32_t mode, uint32_t sample, pt_ray* rays,
+                   uint32_t* seeds);
+int pt_gather_rays_async(pt_scene* scene, const pt_gather_point* d_pts, size_t n, uint32_t mode, uint32_t sample,
+                         pt_ray* d_rays, uint32_t* d_seeds, void* stream);
+
 /* Completion check of the asynchronous calls: waits for every render of the scene to finish
  * (blocking) and reports a device-side failure of any of them — a wavefront traversal wave that
  * gave up after its watchdog limit leaves a flag instead of hanging, and the accumulators of
