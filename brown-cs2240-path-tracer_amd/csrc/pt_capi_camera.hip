@@ -4,6 +4,7 @@
 #include <cmath>
 
 #include "pt_capi_internal.h"
+#include "pt_view_plan.h"
 
 using namespace pt;
 
@@ -33,19 +34,7 @@ int pt_scene_set_camera(pt_scene* s, const pt_camera* cam) {
         s->cam = pt_camera{};
         return PT_OK;
     }
-    const bool focus_ok = std::isfinite(cam->focus_distance) && cam->focus_distance > 0.0f;
-    switch (cam->model) {
-        case PT_CAMERA_THIN_LENS:
-            if (!std::isfinite(cam->lens_radius) || cam->lens_radius < 0.0f)
-                return fail(PT_ERR_INVALID, "camera: thin lens needs a finite lens_radius >= 0");
-            if (!focus_ok) return fail(PT_ERR_INVALID, "camera: thin lens needs a finite focus_distance > 0");
-            break;
-        case PT_CAMERA_ORTHO:
-            if (!focus_ok) return fail(PT_ERR_INVALID, "camera: ortho needs a finite focus_distance > 0");
-            break;
-        case PT_CAMERA_EQUIRECT: break;
-        default: return fail(PT_ERR_INVALID, "camera: unknown model");
-    }
+    if (const char* why = camera_refusal(*cam)) return fail(PT_ERR_INVALID, why);  // pt_view_plan.h: a view's camera too
     s->cam = *cam;
     return PT_OK;
 }

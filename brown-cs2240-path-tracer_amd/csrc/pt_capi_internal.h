@@ -127,6 +127,8 @@ struct pt_scene {
     // a rectangle-list render's table (pt_render_rects): the rows, then the megakernel's blocks; written
     // on the call's stream before its first launch, so calls in stream order may share it
     pt::Scratch<char> d_rects;
+    // a view-list render's table (pt_render_views): its ViewRows, written like d_rects
+    pt::Scratch<char> d_views;
     // the denoiser's four w * h float4 planes (pt_denoise_async: two ping-pong (c, var), (N, Z), (A, 0);
     // counted in info.device_bytes while held), and the scratch of its blocking calls: the guide buffers
     // (geo, then alb) and the filtered variance

@@ -152,6 +152,27 @@ struct GatherList {
     uint32_t n;
     uint32_t mode;      // GATHER_COSINE / GATHER_SH9 (pt_path.h)
 };
+// A view list on the device (pt_render_views): the sixth slot map.  The rectangle list's
+// map — path id f * npix + q, q the pixel's position in the concatenation of the views' windows — with the
+// camera a per-slot quantity as well: a row holds its window, its place in the atlas, its first frame and
+// the fields path_begin and path_begin_model read from FrameParams and LensCam, as make_params made them
+// for the view's meta.  160 bytes, read as ten float4.
+struct alignas(16) ViewRow {
+    uint32_t first, x0, y0, w;           // the slot of the first pixel; the window in the view's IMAGE
+    uint32_t h, dst_x, dst_y, frame0;    // window pixel (0, 0) in the atlas; the view's first frame
+    float W, H, inv_w, inv_h;            // FrameParams' fields of the same names, from here on
+    float aspect, focal, view_half_h;
+    uint32_t model;                      // LensCam::model (CAM_PINHOLE: path_begin itself)
+    float cam[4];
+    float M[16];
+    uint32_t width, height;
+    float lens_radius, focus_distance;   // LensCam's
+};
+static_assert(sizeof(ViewRow) == 160, "ViewRow is ten 16-byte loads");
+struct ViewList {
+    const ViewRow* rows;  // n, list order
+    uint32_t n, npix;     // views, paths per frame
+};
 // rl (nullable, accumulating calls): the call renders the rectangles of the list instead of fp's
 // window — paths per frame rl->npix, camera paths by k_wf_generate's list instance (whatever
 // lo.fuse_gen and lo.regen say), k_wf_accum's list instance
@@ -162,11 +183,15 @@ struct GatherList {
 // k_wf_generate_cam's instance of the model, over the window's or the list's slot map (whatever
 // lo.fuse_gen and lo.regen say); everything after the generate kernel is the pinhole's
 // gl (nullable, accumulating calls, without m2, rl, ql and cam): as ql, for the points of the gather list
+// vl (nullable, accumulating calls, without m2, rl, ql, cam and gl): the call renders the views of the list —
+// paths per frame vl->npix, camera paths by k_wf_generate_views (whatever lo.fuse_gen and lo.regen say),
+// k_wf_accum_views into the atlas `out` with rows fp.row_pitch pixels apart; of fp only rr_prob,
+// direct_only, max_depth and row_pitch are read, and frame0 is not (the rows carry theirs)
 hipError_t launch_wavefront(const LaunchOpts& lo, const SceneView& sc, const FrameParams& fp, const WfBuffers& wb,
                             uint32_t frame0, uint32_t nframes, uint32_t stride, bool accum, bool count, float* out,
                             Counters* cnt, hipStream_t stream, const WfStreams& ws, float* m2 = nullptr,
                             const RectList* rl = nullptr, const RayList* ql = nullptr, const LensCam* cam = nullptr,
-                            const GatherList* gl = nullptr);
+                            const GatherList* gl = nullptr, const ViewList* vl = nullptr);
 // sample `sample` of every point of the list as pt_ray records and radiance seeds (pt_gather_rays)
 hipError_t launch_gather_rays(const GatherList& gl, uint32_t sample, void* rays, uint32_t* seeds, hipStream_t stream);
 

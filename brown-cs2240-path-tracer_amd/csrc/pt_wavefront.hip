@@ -379,6 +379,100 @@ __global__ __launch_bounds__(256) void k_wf_generate_cam(FrameParams fp, LensCam
     }
 }
 
+// The view of a list that holds pixel q of its frame (q < vl.npix): the last row whose first slot is <= q,
+// by bisection with the shape of rect_of (n <= 65536: at most 17 steps; neighbouring lanes nearly always
+// agree on every one).
+__device__ __forceinline__ const ViewRow* view_of(const ViewList& vl, uint32_t q) {
+    uint32_t lo = 0, hi = vl.n;
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (vl.rows[mid].first <= q) lo = mid;
+        else hi = mid;
+    }
+    return vl.rows + lo;
+}
+
+// k_wf_generate for a view list (pt_render_views; ViewList, pt_kernels.h): launch slot
+// p < P is pixel q = p - f npix of frame f = p / npix, path id p.  The slot finds its view (view_of), takes
+// the row's camera block into a FrameParams of its own — ten float4 loads; a wave inside one view loads one
+// address — and begins its path with path_begin (a pinhole row) or path_begin_model of the row's model, at
+// pixel (x0 + i, y0 + j) of the view's image and salt u32(f32(frame0_v + (fbase + f) * stride)).  Those
+// functions and camera_ray are the other generate kernels' own.  Samples that are not admitted, the
+// (-0, -0, -0) radiance slot and the compaction are k_wf_generate_cam's (the statements are repeated here so
+// that that kernel's code does not change); the host zeroes the counts before the launch.
+template <bool COUNT>
+__global__ __launch_bounds__(256) void k_wf_generate_views(ViewList vl, WfBuffers wb, uint32_t stride, uint32_t fbase,
+                                                           uint32_t P, Counters* cnt_out) {
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t R = wb.nreg;
+    bool adm = false;
+    Ray r;
+    PathState ps;
+    if (p < P) {  // p: the launch slot = the path id
+        const uint32_t f = p / vl.npix, q = p - f * vl.npix;
+        const float4* rw = reinterpret_cast<const float4*>(view_of(vl, q));
+        const float4 a = rw[0], b = rw[1], c = rw[2], d = rw[3], e = rw[4], g = rw[9];
+        const uint32_t k = q - __float_as_uint(a.x), w = __float_as_uint(a.w);
+        const uint32_t j = k / w, i = k - j * w;
+        const uint32_t x = __float_as_uint(a.y) + i, y = __float_as_uint(a.z) + j;
+        const uint32_t t = (uint32_t)(float)(__float_as_uint(b.w) + (fbase + f) * stride);
+        FrameParams fp = {};  // the camera fields alone: nothing else is read before the queue entry stands
+        fp.W = c.x; fp.H = c.y; fp.inv_w = c.z; fp.inv_h = c.w;
+        fp.aspect = d.x; fp.focal = d.y; fp.view_half_h = d.z;
+        fp.cam[0] = e.x; fp.cam[1] = e.y; fp.cam[2] = e.z; fp.cam[3] = e.w;
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+            const float4 col = rw[5 + m];
+            fp.M[4 * m] = col.x; fp.M[4 * m + 1] = col.y; fp.M[4 * m + 2] = col.z; fp.M[4 * m + 3] = col.w;
+        }
+        fp.width = __float_as_uint(g.x); fp.height = __float_as_uint(g.y);
+        LensCam lc;
+        lc.model = __float_as_uint(d.w);
+        lc.lens_radius = g.z;
+        lc.focus_distance = g.w;
+        switch (lc.model) {
+            case CAM_THIN_LENS: adm = path_begin_model<CAM_THIN_LENS>(fp, lc, x, y, t, r, ps); break;
+            case CAM_ORTHO: adm = path_begin_model<CAM_ORTHO>(fp, lc, x, y, t, r, ps); break;
+            case CAM_EQUIRECT: adm = path_begin_model<CAM_EQUIRECT>(fp, lc, x, y, t, r, ps); break;
+            default: r = path_begin(fp, x, y, t, ps); adm = true; break;  // the pinhole: every sample has a path
+        }
+        if (!adm) {
+            float* o = wb.rad + 3 * (size_t)p;
+            o[0] = -0.0f; o[1] = -0.0f; o[2] = -0.0f;
+        }
+    }
+    const uint64_t keep = __ballot(adm);
+    uint32_t slot = 0;
+    if (R) {  // the wave's slots are batch p / 64 of k_wf_generate's layout: its region's next entries
+        if (keep) {  // wave-uniform
+            const uint32_t j = __builtin_amdgcn_readfirstlane(p) / 64;
+            const uint32_t rg = (uint32_t)((uint64_t)(j % R) * wb.rqi % R);
+            uint32_t base = 0;
+            if (lane_id() == 0) base = atomicAdd(&wb.rcnt[rg], (uint32_t)__popcll(keep));
+            slot = rg * wb.rstride + __shfl(base, 0, 64) + rank_below(keep);
+        }
+    } else {  // wave counts -> one atomicAdd per block (four waves)
+        __shared__ uint32_t s_cnt[4];
+        __shared__ uint32_t s_base;
+        const uint32_t wv = threadIdx.x / 64;
+        if (lane_id() == 0) s_cnt[wv] = (uint32_t)__popcll(keep);
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const uint32_t total = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+            s_base = total ? atomicAdd(&wb.ctl[WF_COUNT0], total) : 0u;
+        }
+        __syncthreads();
+        slot = s_base + rank_below(keep);
+        for (uint32_t w = 0; w < wv; ++w) slot += s_cnt[w];
+    }
+    if (adm) store_entry(wb.ext, slot, r, p, ps);
+    if (COUNT) {
+        Counters c = {};
+        if (adm) { c.samples++; c.ext_queries++; }
+        flush_counters(c, cnt_out);
+    }
+}
+
 // k_wf_generate for a gather list (pt_gather; GatherList, pt_kernels.h): launch slot
 // p < P is sample f = p / n of point i = p - f n, so neighbouring lanes load neighbouring 32-byte points
 // (two float4 each).  Path id p.  The sample's direction is drawn on the spot (gather_ray<MODE>) with
@@ -1512,6 +1606,28 @@ __global__ __launch_bounds__(256) void k_wf_accum_gather(const float* __restrict
     for (int k = 0; k < W; ++k) o[k] = a[k];
 }
 
+// k_wf_accum for a view list: pixel pix of the list (its position in the concatenation of the views'
+// windows) is window pixel (i, j) of its view and lives at acc + 3 * ((dst_y + j) * row_pitch + dst_x + i);
+// acc += clamp(radiance) for the batch's F frames in order, k_wf_accum's accumulating statements (a sample
+// that is not admitted left -0 in its radiance slot, which changes no bit).  A sibling of k_wf_accum, so
+// that its instances' code stays as it is.
+__global__ __launch_bounds__(256) void k_wf_accum_views(const float* __restrict__ rad, float* __restrict__ acc, ViewList vl,
+                                                        uint32_t row_pitch, uint32_t F) {
+    const uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pix >= vl.npix) return;
+    const float4* rw = reinterpret_cast<const float4*>(view_of(vl, pix));
+    const float4 ra = rw[0], rb = rw[1];
+    const uint32_t k = pix - __float_as_uint(ra.x), w = __float_as_uint(ra.w);
+    const uint32_t j = k / w, i = k - j * w;
+    float* o = acc + 3 * ((size_t)(__float_as_uint(rb.z) + j) * row_pitch + (__float_as_uint(rb.y) + i));
+    f3 a = mk(o[0], o[1], o[2]);
+    for (uint32_t f = 0; f < F; ++f) {
+        const float* r = rad + 3 * ((size_t)f * vl.npix + pix);
+        a = add_clamped(a, mk(r[0], r[1], r[2]));
+    }
+    o[0] = a.x; o[1] = a.y; o[2] = a.z;
+}
+
 // ---------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------
@@ -1612,10 +1728,10 @@ template <bool LDS, int TRAV, bool COUNT>
 static hipError_t wf_render_t(const SceneView& sc_in, const FrameParams& fp, const WfBuffers& wb, uint32_t frame0,
                               uint32_t nframes, uint32_t stride, bool accum, float* out, Counters* cnt,
                               hipStream_t stream, const WfStreams& ws, const LaunchOpts& lo, float* m2, const RectList* rl,
-                              const RayList* ql, const LensCam* cam, const GatherList* gl) {
+                              const RayList* ql, const LensCam* cam, const GatherList* gl, const ViewList* vl) {
     SceneView sc = bf_view<TRAV, COUNT>(sc_in);
     // paths per frame: the list's, else the window's (a ray list: its rays, a "frame" being one sample of each)
-    const uint32_t npix = gl ? gl->n : ql ? ql->n : rl ? rl->npix : fp.win_w * fp.win_h;
+    const uint32_t npix = vl ? vl->npix : gl ? gl->n : ql ? ql->n : rl ? rl->npix : fp.win_w * fp.win_h;
     // the batch in lo.parts parts on as many streams when a part holds at least a frame: one
     // part's kernel fills the others' launch tails and boundaries (and, with separate trace and
     // shade kernels, a VALU-bound trace runs beside an HBM-bound shade)
@@ -1659,7 +1775,7 @@ static hipError_t wf_render_t(const SceneView& sc_in, const FrameParams& fp, con
     constexpr bool kNarrowOk = flv_fused(TRAV) && LDS && !COUNT;
     const bool narrow = kNarrowOk && sc.bfnode && sc.bfnarrow;
     if constexpr (flv_fused(TRAV)) {  // the camera batches' table (k_wf_camtab), before every part's GEN launch
-        if (lo.fuse_gen && !rl && !ql && !cam && !gl) {
+        if (lo.fuse_gen && !rl && !ql && !cam && !gl && !vl) {
             if (sc.n_tris - sc.mb_base > 64) return hipErrorInvalidValue;  // mailbox scenes: <= 64 entries
             hipLaunchKernelGGL(k_wf_camtab, dim3(1), dim3(64), 0, stream, sc, fp, wb.camtab);
         }
@@ -1709,11 +1825,12 @@ static hipError_t wf_render_t(const SceneView& sc_in, const FrameParams& fp, con
         // slots 0: zeroed here with slot 1, as k_wf_generate would have set them)
         // (and a lens camera's from k_wf_generate_cam, which compacts as k_wf_generate_rays does)
         // (and a gather list's from k_wf_generate_gather, likewise)
-        const bool fgen = flv_fused(TRAV) && lo.fuse_gen && !rl && !ql && !cam && !gl;
+        // (and a view list's from k_wf_generate_views, likewise)
+        const bool fgen = flv_fused(TRAV) && lo.fuse_gen && !rl && !ql && !cam && !gl && !vl;
         if (fgen)
             for (int h = 0; h < nh; ++h)
                 HIP_RETURN_IF(hipMemsetAsync(pv[h].w.rcnt + kRegions, 0, kRegions * sizeof(uint32_t), stream));
-        if (ql || cam || gl)
+        if (ql || cam || gl || vl)
             for (int h = 0; h < nh; ++h) {
                 HIP_RETURN_IF(hipMemsetAsync(pv[h].w.ctl + WF_COUNT0, 0, 2 * sizeof(uint32_t), stream));
                 if (flv_fused(TRAV)) HIP_RETURN_IF(hipMemsetAsync(pv[h].w.rcnt, 0, 2 * kRegions * sizeof(uint32_t), stream));
@@ -1739,7 +1856,10 @@ static hipError_t wf_render_t(const SceneView& sc_in, const FrameParams& fp, con
         }
         for (int h = 0; h < nh && !fgen; ++h) {
             const dim3 ggrid((std::max(pv[h].P, pv[h].w.nreg) + 255) / 256);
-            if (gl) {
+            if (vl) {
+                PT_LAUNCH(KID_WF_GENERATE, pv[h].st, (k_wf_generate_views<COUNT>), dim3((pv[h].P + 255) / 256), dim3(256), 0,
+                          pv[h].st, *vl, pv[h].w, stride, pv[h].fbase, pv[h].P, cnt);
+            } else if (gl) {
                 const dim3 qgrid((pv[h].P + 1023) / 1024);
                 if (gl->mode == GATHER_SH9)
                     PT_LAUNCH(KID_WF_GENERATE, pv[h].st, (k_wf_generate_gather<COUNT, GATHER_SH9>), qgrid, dim3(1024), 0,
@@ -1854,7 +1974,10 @@ static hipError_t wf_render_t(const SceneView& sc_in, const FrameParams& fp, con
                 HIP_RETURN_IF(hipStreamWaitEvent(stream, ws.join[h], 0));
             }
         }
-        if (gl && gl->mode == GATHER_SH9)
+        if (vl)
+            PT_LAUNCH(KID_WF_ACCUM, stream, k_wf_accum_views, dim3((npix + 255) / 256), dim3(256), 0, stream, wb.rad, out, *vl,
+                      fp.row_pitch, Fb);
+        else if (gl && gl->mode == GATHER_SH9)
             PT_LAUNCH(KID_WF_ACCUM, stream, (k_wf_accum_gather<GATHER_SH9>), dim3((npix + 255) / 256), dim3(256), 0, stream,
                       wb.rad, out, *gl, frame0 + fb, Fb);
         else if (gl)
@@ -1875,8 +1998,9 @@ static hipError_t wf_render_t(const SceneView& sc_in, const FrameParams& fp, con
 hipError_t launch_wavefront(const LaunchOpts& lo, const SceneView& sc, const FrameParams& fp, const WfBuffers& wb,
                             uint32_t frame0, uint32_t nframes, uint32_t stride, bool accum, bool count, float* out,
                             Counters* cnt, hipStream_t stream, const WfStreams& ws, float* m2, const RectList* rl,
-                            const RayList* ql, const LensCam* cam, const GatherList* gl) {
-    if ((m2 || rl || ql || gl) && !accum) return hipErrorInvalidValue;
+                            const RayList* ql, const LensCam* cam, const GatherList* gl, const ViewList* vl) {
+    if ((m2 || rl || ql || gl || vl) && !accum) return hipErrorInvalidValue;
+    if (vl && (m2 || rl || ql || cam || gl || vl->n == 0 || vl->npix == 0)) return hipErrorInvalidValue;
     if (gl && (m2 || rl || ql || cam || stride != 1 || gl->n == 0 || gl->mode > GATHER_SH9)) return hipErrorInvalidValue;
     if (cam && (ql || cam->model < CAM_THIN_LENS || cam->model > CAM_EQUIRECT)) return hipErrorInvalidValue;
     if (ql && (m2 || rl || stride != 1 || ql->n == 0)) return hipErrorInvalidValue;
@@ -1886,7 +2010,7 @@ hipError_t launch_wavefront(const LaunchOpts& lo, const SceneView& sc, const Fra
     // (pt_capi.hip shape_view: option leaf_pre, default on) and the buffers exist
     const int trav = select_wavefront(lo, sc.fast_rcp != 0, sc.mailbox != 0, sc.big_leaf > 0, sc.npre > 0 && sc.pre && wb.pres);
     // sc.node_bias <= 0: chosen per instance in wf_render_t
-#define WF_ARGS sc, fp, wb, frame0, nframes, stride, accum, out, cnt, stream, ws, lo, m2, rl, ql, cam, gl
+#define WF_ARGS sc, fp, wb, frame0, nframes, stride, accum, out, cnt, stream, ws, lo, m2, rl, ql, cam, gl, vl
 #define WF(T)                                                                                                        \
     case T:                                                                                                          \
         return lds ? (count ? wf_render_t<true, T, true>(WF_ARGS) : wf_render_t<true, T, false>(WF_ARGS))            \

@@ -955,22 +955,17 @@ static napi_value js_scene_set_vertex_normals(napi_env env, napi_callback_info i
     return NULL;
 }
 
-/* sceneSetCamera(scene, {model, lensRadius = 0, focusDistance = 1}): the camera model of later calls on the
- * scene (pt_scene_set_camera).  model: 'pinhole' | 'thin_lens' (or 'thinlens') | 'ortho' | 'equirect', or its
- * number; null or undefined instead of the object: the pinhole. */
-static napi_value js_scene_set_camera(napi_env env, napi_callback_info info) {
-    size_t argc = 2;
-    napi_value argv[2];
-    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-    pt_scene* s = argc ? get_scene(env, argv[0]) : NULL;
+/* {model, lensRadius = 0, focusDistance = 1} -> pt_camera.  model: 'pinhole' | 'thin_lens' (or 'thinlens') | 'ortho' |
+ * 'equirect', or its number; null or undefined instead of the object: the pinhole. */
+static bool parse_camera(napi_env env, napi_value obj, pt_camera* out) {
     pt_camera cam = {PT_CAMERA_PINHOLE, 0.0f, 1.0f, 0};
-    bool ok = s != NULL;
+    bool ok = true;
     napi_valuetype t = napi_undefined;
-    if (ok && argc > 1) napi_typeof(env, argv[1], &t);
-    if (ok && t == napi_object) {
+    if (napi_typeof(env, obj, &t) != napi_ok) return false;
+    if (t == napi_object) {
         napi_value v;
         napi_valuetype vt = napi_undefined;
-        ok = napi_get_named_property(env, argv[1], "model", &v) == napi_ok && napi_typeof(env, v, &vt) == napi_ok;
+        ok = napi_get_named_property(env, obj, "model", &v) == napi_ok && napi_typeof(env, v, &vt) == napi_ok;
         if (ok && vt == napi_string) {
             char name[16] = "";
             size_t len = 0;
@@ -989,13 +984,27 @@ static napi_value js_scene_set_camera(napi_env env, napi_callback_info info) {
         float* dst[2] = {&cam.lens_radius, &cam.focus_distance};
         for (int k = 0; k < 2 && ok; ++k) {
             double d;
-            if (napi_get_named_property(env, argv[1], keys[k], &v) != napi_ok || napi_typeof(env, v, &vt) != napi_ok) ok = false;
+            if (napi_get_named_property(env, obj, keys[k], &v) != napi_ok || napi_typeof(env, v, &vt) != napi_ok) ok = false;
             else if (vt == napi_number) { ok = napi_get_value_double(env, v, &d) == napi_ok; *dst[k] = (float)d; }
             else if (vt != napi_undefined) ok = false;
         }
-    } else if (ok && t != napi_undefined && t != napi_null) {
+    } else if (t != napi_undefined && t != napi_null) {
         ok = false;
     }
+    if (ok) *out = cam;
+    return ok;
+}
+
+/* sceneSetCamera(scene, {model, lensRadius = 0, focusDistance = 1}): the camera model of later calls on the
+ * scene (pt_scene_set_camera); the object as parse_camera takes it. */
+static napi_value js_scene_set_camera(napi_env env, napi_callback_info info) {
+    size_t argc = 2;
+    napi_value argv[2];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    pt_scene* s = argc ? get_scene(env, argv[0]) : NULL;
+    pt_camera cam = {PT_CAMERA_PINHOLE, 0.0f, 1.0f, 0};
+    bool ok = s != NULL;
+    if (ok && argc > 1) ok = parse_camera(env, argv[1], &cam);
     if (!ok) {
         if (!pending_exception(env))
             napi_throw_type_error(env, NULL, "sceneSetCamera(scene, {model: 'pinhole'|'thin_lens'|'ortho'|'equirect', lensRadius, focusDistance})");
@@ -1004,6 +1013,155 @@ static napi_value js_scene_set_camera(napi_env env, napi_callback_info info) {
     int rc = pt_scene_set_camera(s, &cam);
     if (rc) return throw_pt(env, rc);
     return NULL;
+}
+
+/* renderViews(scene, [{meta: Float32Array[48], window: [x0, y0, w, h] | undefined, camera: {model, lensRadius,
+ * focusDistance} | undefined, dst: [x, y], frame0 = 0}, ...], atlasW, atlasH, nframes, stride, maxDepth, mode,
+ * accum[atlasH*atlasW*3][, counters=true]) -> Promise<counters|null>: the views of the list in one pass, each at
+ * its place of the atlas accumulator (pt_render_views).  The library checks the list. */
+#define PT_NODE_MAX_VIEWS 65536u
+typedef struct {
+    napi_async_work work;
+    napi_deferred deferred;
+    napi_ref refs[2]; /* scene, accum kept alive while the worker runs */
+    scene_box* box;
+    pt_scene* scene;
+    pt_view* views; /* malloc'd */
+    size_t n;
+    uint32_t atlas_w, atlas_h, nframes, stride;
+    int32_t max_depth, mode;
+    float* accum;
+    pt_counters counters;
+    int want_counters;
+    int rc;
+    char err[512];
+} views_job;
+
+static void views_execute(napi_env env, void* data) {
+    (void)env;
+    views_job* j = (views_job*)data;
+    j->rc = pt_render_views(j->scene, j->views, j->n, j->atlas_w, j->atlas_h, j->nframes, j->stride, j->max_depth, j->mode,
+                            j->accum, j->want_counters ? &j->counters : NULL);
+    if (j->rc) snprintf(j->err, sizeof j->err, "pt_hip error %d: %s", j->rc, pt_last_error());
+}
+
+static void views_complete(napi_env env, napi_status status, void* data) {
+    views_job* j = (views_job*)data;
+    if (j->box) j->box->busy = 0;
+    if (status == napi_ok && j->rc == 0) {
+        napi_value none;
+        napi_get_null(env, &none);
+        napi_resolve_deferred(env, j->deferred, j->want_counters ? counters_obj(env, &j->counters) : none);
+    } else {
+        napi_value msg, e;
+        napi_create_string_utf8(env, j->rc ? j->err : "render cancelled", NAPI_AUTO_LENGTH, &msg);
+        napi_create_error(env, NULL, msg, &e);
+        napi_reject_deferred(env, j->deferred, e);
+    }
+    for (int i = 0; i < 2; ++i) napi_delete_reference(env, j->refs[i]);
+    napi_delete_async_work(env, j->work);
+    free(j->views);
+    free(j);
+}
+
+/* one view object into *v; the window defaults to the whole image of meta[0..1] */
+static int parse_view(napi_env env, napi_value obj, pt_view* v) {
+    napi_valuetype t;
+    napi_value e;
+    float* meta;
+    size_t ml;
+    memset(v, 0, sizeof *v);
+    if (napi_typeof(env, obj, &t) != napi_ok || t != napi_object) return 0;
+    if (napi_get_named_property(env, obj, "meta", &e) != napi_ok || !get_f32(env, e, &meta, &ml) || ml < 48) return 0;
+    memcpy(v->meta, meta, sizeof v->meta);
+    if (napi_get_named_property(env, obj, "window", &e) != napi_ok || napi_typeof(env, e, &t) != napi_ok) return 0;
+    if (t == napi_undefined || t == napi_null) {
+        if (!(v->meta[0] >= 1.0f && v->meta[0] <= 32768.0f && v->meta[1] >= 1.0f && v->meta[1] <= 32768.0f)) return 0;
+        v->win.w = (uint32_t)v->meta[0];
+        v->win.h = (uint32_t)v->meta[1];
+    } else if (!parse_window(env, e, &v->win)) {
+        return 0;
+    }
+    if (napi_get_named_property(env, obj, "camera", &e) != napi_ok || !parse_camera(env, e, &v->cam)) return 0;
+    if (v->cam.model == PT_CAMERA_PINHOLE) v->cam.lens_radius = v->cam.focus_distance = 0.0f;
+    bool is_arr = false;
+    uint32_t n = 0;
+    napi_value c;
+    if (napi_get_named_property(env, obj, "dst", &e) != napi_ok || napi_is_array(env, e, &is_arr) != napi_ok || !is_arr ||
+        napi_get_array_length(env, e, &n) != napi_ok || n != 2)
+        return 0;
+    uint32_t* out[2] = {&v->dst_x, &v->dst_y};
+    for (uint32_t i = 0; i < 2; ++i) {
+        double d;
+        if (napi_get_element(env, e, i, &c) != napi_ok || napi_get_value_double(env, c, &d) != napi_ok) return 0;
+        if (!(d >= 0.0 && d <= 4294967295.0) || d != (double)(uint32_t)d) return 0;
+        *out[i] = (uint32_t)d;
+    }
+    if (napi_get_named_property(env, obj, "frame0", &e) != napi_ok || napi_typeof(env, e, &t) != napi_ok) return 0;
+    if (t != napi_undefined) {
+        double d;
+        if (napi_get_value_double(env, e, &d) != napi_ok || !(d >= 0.0 && d <= 4294967295.0) || d != (double)(uint32_t)d) return 0;
+        v->frame0 = (uint32_t)d;
+    }
+    return 1;
+}
+
+static int parse_views_args(napi_env env, napi_callback_info info, views_job* j, napi_value argv[10]) {
+    size_t argc = 10;
+    if (napi_get_cb_info(env, info, &argc, argv, NULL, NULL) != napi_ok || argc < 9 || argc > 10) return 0;
+    bool want = true;
+    napi_valuetype t;
+    if (argc > 9) {
+        if (napi_typeof(env, argv[9], &t) != napi_ok) return 0;
+        if (t != napi_undefined && napi_get_value_bool(env, argv[9], &want) != napi_ok) return 0;
+    }
+    j->want_counters = want ? 1 : 0;
+    j->box = get_box(env, argv[0]);
+    j->scene = get_scene(env, argv[0]);
+    if (!j->scene) return 0;
+    bool is_arr = false;
+    uint32_t n = 0;
+    if (napi_is_array(env, argv[1], &is_arr) != napi_ok || !is_arr || napi_get_array_length(env, argv[1], &n) != napi_ok ||
+        n < 1 || n > PT_NODE_MAX_VIEWS)
+        return 0;
+    j->views = (pt_view*)malloc((size_t)n * sizeof(pt_view));
+    if (!j->views) return 0;
+    j->n = n;
+    for (uint32_t k = 0; k < n; ++k) {
+        napi_value e;
+        if (napi_get_element(env, argv[1], k, &e) != napi_ok || !parse_view(env, e, &j->views[k])) return 0;
+    }
+    size_t al;
+    if (!get_u32(env, argv[2], &j->atlas_w) || !get_u32(env, argv[3], &j->atlas_h) || !get_u32(env, argv[4], &j->nframes) ||
+        !get_u32(env, argv[5], &j->stride) || !get_i32(env, argv[6], &j->max_depth) || !get_i32(env, argv[7], &j->mode) ||
+        !get_f32(env, argv[8], &j->accum, &al))
+        return 0;
+    return al == (size_t)j->atlas_w * j->atlas_h * 3;
+}
+
+static napi_value js_render_views(napi_env env, napi_callback_info info) {
+    napi_value argv[10];
+    views_job* j = (views_job*)calloc(1, sizeof(views_job));
+    if (!j) { napi_throw_error(env, NULL, "out of memory"); return NULL; }
+    if (!parse_views_args(env, info, j, argv)) {
+        free(j->views);
+        free(j);
+        if (!pending_exception(env))
+            napi_throw_type_error(env, NULL,
+                                  "renderViews(scene, [{meta: Float32Array[48], window: [x0, y0, w, h]?, camera: {model, lensRadius, "
+                                  "focusDistance}?, dst: [x, y], frame0?}, ...], atlasW, atlasH, nframes, stride, maxDepth, mode, "
+                                  "Float32Array accum[atlasH*atlasW*3], counters?)");
+        return NULL;
+    }
+    j->box->busy = 1;
+    napi_value promise, name;
+    CHECK_NAPI(env, napi_create_promise(env, &j->deferred, &promise));
+    napi_create_reference(env, argv[0], 1, &j->refs[0]);
+    napi_create_reference(env, argv[8], 1, &j->refs[1]);
+    napi_create_string_utf8(env, "pt_render_views", NAPI_AUTO_LENGTH, &name);
+    CHECK_NAPI(env, napi_create_async_work(env, NULL, name, views_execute, views_complete, j, &j->work));
+    CHECK_NAPI(env, napi_queue_async_work(env, j->work));
+    return promise;
 }
 
 /* profileRead(scene) -> {kernel: {launches, totalMs, minMs, maxMs, busyMs}} */
@@ -1044,6 +1202,7 @@ static napi_value init(napi_env env, napi_value exports) {
          * which tests/test_host_node.py pins — still lists exactly the original set */
         {"renderWindow", NULL, js_render_window, NULL, NULL, NULL, napi_default, NULL},
         {"renderRects", NULL, js_render_rects, NULL, NULL, NULL, napi_default, NULL},
+        {"renderViews", NULL, js_render_views, NULL, NULL, NULL, napi_default, NULL},
         {"renderSync", NULL, js_render_sync, NULL, NULL, NULL, napi_enumerable, NULL},
         {"renderMulti", NULL, js_render_multi, NULL, NULL, NULL, napi_enumerable, NULL},
         {"renderImage", NULL, js_render_image, NULL, NULL, NULL, napi_enumerable, NULL},

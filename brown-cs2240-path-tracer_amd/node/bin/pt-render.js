@@ -31,6 +31,10 @@
 //  all in doubles, then unitRays' f32 normalisation.  Seeds: pixel index i = x + y W has seed hash1u(hash1u(i * 16787))
 //  for its sample 0 and, the library's rule, hash1u(seed + s * 16787) for sample s of --spp, frame after frame.)
 //  (--camera ortho|equirect renders these projections on the device, jittered, with every other option.)
+// [--turntable N[,cols]] (N cameras — the scene's own position rotated about the axis through its focus along its up,
+//  in N equal steps, step 0 the scene's camera — rendered in ONE renderViews call (pt_render_views) into a contact
+//  sheet of `cols` tiles per row (default ceil(sqrt(N))), which is the PNG; combines with --camera, --counters 1 and
+//  --dump-accum FILE (the sheet's accumulator); not with --window, --denoise or --projection)
 // [--dump-rays FILE] (with equirect or ortho: the rays, 8 f32 each, then the seeds, one u32 each, as made)
 // [--dump-accum FILE] (with equirect or ortho: the accumulator, 3 f32 per pixel, before the tone map)
 const fs = require('fs');
@@ -72,6 +76,17 @@ async function main(argv) {
         }
         denoise = { iters: +it, featureFrames: +ff };
     }
+    let turntable = null;
+    if (args.turntable !== undefined) {
+        const parts = String(args.turntable).split(',');
+        if (parts.length < 1 || parts.length > 2 || !parts.every((v) => /^\d+$/.test(v)) || !(+parts[0] >= 1 && +parts[0] <= 65536) ||
+            (parts.length > 1 && !(+parts[1] >= 1)) || window || rects || denoise || args.projection !== undefined) {
+            console.error('usage: pt-render.js <scene.ini> --turntable N[,cols] (N in 1..65536, cols at least 1; ' +
+                          `not with --window, --denoise or --projection): --turntable ${args.turntable}`);
+            process.exit(2);
+        }
+        turntable = { n: +parts[0], cols: parts.length > 1 ? +parts[1] : undefined };
+    }
     if (args.pick !== undefined) return pick(args);
     if (args.irradiance !== undefined || args.probe !== undefined) return gather(args);
     const projection = args.projection === undefined ? 'pinhole' : String(args.projection);
@@ -99,6 +114,7 @@ async function main(argv) {
         const dist = Math.hypot(focus[0] - pos[0], focus[1] - pos[1], focus[2] - pos[2]);
         camera = { model: models[args.camera], lensRadius: num(args.aperture) || 0, focusDistance: args.focus_distance === undefined ? dist : num(args.focus_distance) };
     }
+    if (turntable) return turn(args, s, turntable, camera, t0);
     const t1 = Date.now();
     const r = await host.programEntry(s.screenDimension, s.primitive_data, s.camera_data, s.scene_description, {
         device: parseInt(args.device || '0'), maxDepth: parseInt(args.max_depth || '16'), mode: args.mode || 'auto',
@@ -113,6 +129,34 @@ async function main(argv) {
     const samples = (rects ? rects.reduce((a, w) => a + w[2] * w[3], 0) : W * H) * r.sample_runs;
     console.log(JSON.stringify({ output: out, width: W, height: H, window, rects, camera, spp: r.sample_runs, scene_ms: t1 - t0,
         denoise, render_ms: t2 - t1, msamples_per_s: samples / ((t2 - t1) / 1000) / 1e6, counters: r.counters }));
+}
+// --turntable N[,cols]: N metas from make_meta, one renderViews call, the contact sheet as the PNG
+async function turn(args, s, turntable, camera, t0) {
+    const [W, H] = s.screenDimension;
+    const spp = s.scene_description.Settings.samplesPerPixel;
+    const cams = host.turntable_cameras(s.camera_data, turntable.n);
+    const { dsts, atlasW, atlasH } = host.view_atlas(cams.map(() => [W, H]), turntable.cols);
+    const views = cams.map((c, k) => ({ meta: host.make_meta(s.screenDimension, c, s.scene_description, 0), camera, dst: dsts[k], frame0: 0 }));
+    const t1 = Date.now();
+    const pt = host.native();
+    const scene = pt.sceneCreate(s.primitive_data[0].triangle_data, s.primitive_data[0].bvh_data, parseInt(args.device || '0'));
+    let r;
+    try {
+        if (args.vertex_normals === '1') pt.sceneSetVertexNormals(scene, true);
+        r = await host.renderViews(scene, views, { atlasW, atlasH, nframes: spp, stride: 1, maxDepth: parseInt(args.max_depth || '16'),
+            mode: args.mode || 'auto', counters: args.counters === '1' });
+    } finally {
+        pt.sceneDestroy(scene);
+    }
+    const t2 = Date.now();
+    const rgba = new Uint8ClampedArray(atlasW * atlasH * 4);
+    pt.tonemap(r.accum, spp, rgba);
+    const out = path.join(args.out_root || '.', s.scene_description.IO.output || 'out.png');
+    fs.mkdirSync(path.dirname(out), { recursive: true });
+    fs.writeFileSync(out, host.encode_png(rgba, atlasW, atlasH));
+    if (args.dump_accum) fs.writeFileSync(args.dump_accum, Buffer.from(r.accum.buffer, r.accum.byteOffset, r.accum.byteLength));
+    console.log(JSON.stringify({ output: out, width: atlasW, height: atlasH, turntable: turntable.n, tile: [W, H], dsts, camera, spp,
+        scene_ms: t1 - t0, render_ms: t2 - t1, msamples_per_s: W * H * turntable.n * spp / ((t2 - t1) / 1000) / 1e6, counters: r.counters }));
 }
 // hash.wgsl's hash1u in u32 arithmetic
 function hash1u(n) {

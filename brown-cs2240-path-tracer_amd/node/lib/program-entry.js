@@ -147,4 +147,73 @@ async function programEntryMulti(pt, meta, W, H, primitive_data, scene_descripti
     }
 }
 
-module.exports = { programEntry, make_meta, check_window, check_rects, MODE };
+/** A shelf packing of rectangles [[w, h], ...] in list order: rows of `cols` rectangles (default ceil(sqrt(n))), each
+ *  row as tall as its tallest -> { dsts: [[x, y], ...], atlasW, atlasH } (pt_amd.view_atlas's rule) */
+function view_atlas(sizes, cols) {
+    if (!Array.isArray(sizes) || sizes.length < 1) throw Error('views: the list is empty (n must be at least 1)');
+    const per = cols === undefined || cols === null ? Math.ceil(Math.sqrt(sizes.length)) : cols;
+    if (!Number.isInteger(per) || per < 1) throw Error(`cols must be a positive integer, not ${cols}`);
+    const dsts = [];
+    let x = 0, y = 0, rowH = 0, atlasW = 0;
+    sizes.forEach(([w, h], k) => {
+        if (k && k % per === 0) { x = 0; y += rowH; rowH = 0; }
+        dsts.push([x, y]);
+        x += w;
+        rowH = Math.max(rowH, h);
+        atlasW = Math.max(atlasW, x);
+    });
+    return { dsts, atlasW, atlasH: y + rowH };
+}
+
+/**
+ * renderViews(scene, views, {atlasW, atlasH, nframes, stride=1, maxDepth=16, mode='auto', accum, counters=false})
+ *   -> Promise<{accum: Float32Array(atlasH*atlasW*3), counters, atlasW, atlasH, dsts}>
+ * Many images of one native scene handle (native().sceneCreate) in ONE pass through the pipeline
+ * (pt_render_views): views = [{meta: Float32Array(48), window: [x0, y0, w, h] (default: the image), camera:
+ * {model, lensRadius, focusDistance} (default: the pinhole), dst: [x, y], frame0 = 0}, ...].  View v's window lands at
+ * dst in the atlas accumulator (given, in/out; default zeros) and holds the bits render / renderWindow give under
+ * sceneSetCamera(camera).  Without atlasW, atlasH and any dst the views are packed by view_atlas.
+ */
+async function renderViews(scene, views, options) {
+    const o = Object.assign({ stride: 1, maxDepth: 16, mode: 'auto', counters: false }, options || {});
+    if (!Array.isArray(views) || views.length < 1) throw Error('views must be a non-empty list of {meta, window, camera, dst, frame0}');
+    const mode = typeof o.mode === 'number' ? o.mode : MODE[o.mode];
+    if (mode === undefined) throw Error(`unknown mode ${o.mode}`);
+    const list = views.map((v, k) => {
+        if (!v || !(v.meta instanceof Float32Array) || v.meta.length < 48) throw Error(`views[${k}]: meta must be a Float32Array of 48`);
+        const window = check_window(v.window) || [0, 0, v.meta[0], v.meta[1]];
+        return { meta: v.meta, window, camera: v.camera || undefined, dst: v.dst, frame0: v.frame0 || 0 };
+    });
+    let { atlasW, atlasH } = o;
+    const packed = list.every((v) => v.dst === undefined || v.dst === null) && atlasW === undefined && atlasH === undefined;
+    if (packed) {
+        const a = view_atlas(list.map((v) => [v.window[2], v.window[3]]));
+        a.dsts.forEach((d, k) => { list[k].dst = d; });
+        ({ atlasW, atlasH } = a);
+    }
+    if (!Number.isInteger(atlasW) || !Number.isInteger(atlasH) || atlasW < 1 || atlasH < 1 || list.some((v) => !Array.isArray(v.dst)))
+        throw Error('views: give every view a dst and the call atlasW and atlasH, or none of them');
+    const accum = o.accum || new Float32Array(atlasW * atlasH * 3);
+    const counters = await load().renderViews(scene, list, atlasW, atlasH, o.nframes, o.stride, o.maxDepth, mode, accum, !!o.counters);
+    return { accum, counters, atlasW, atlasH, dsts: list.map((v) => v.dst.slice()) };
+}
+
+/** N cameras on a turntable: the camera's position rotated about the axis through `focus` along `up`, in N equal
+ *  steps of 2 pi / N (Rodrigues' formula in doubles); step 0 is camera_data itself */
+function turntable_cameras(camera_data, n) {
+    const P = camera_data.pos.toArray(), C = camera_data.focus.toArray(), U = camera_data.up.toArray();
+    const ul = Math.hypot(U[0], U[1], U[2]);
+    const k = U.map((v) => v / ul), r = P.map((v, c) => v - C[c]);
+    const Vertex = camera_data.pos.constructor;
+    const out = [camera_data];
+    for (let s = 1; s < n; ++s) {
+        const th = 2 * Math.PI * s / n, cs = Math.cos(th), sn = Math.sin(th);
+        const kr = k[0] * r[0] + k[1] * r[1] + k[2] * r[2];
+        const x = [k[1] * r[2] - k[2] * r[1], k[2] * r[0] - k[0] * r[2], k[0] * r[1] - k[1] * r[0]];
+        const p = r.map((v, c) => C[c] + v * cs + x[c] * sn + k[c] * kr * (1 - cs));
+        out.push({ focus: camera_data.focus, heightangle: camera_data.heightangle, up: camera_data.up, pos: new Vertex(p[0], p[1], p[2]) });
+    }
+    return out;
+}
+
+module.exports = { programEntry, make_meta, check_window, check_rects, MODE, renderViews, view_atlas, turntable_cameras };

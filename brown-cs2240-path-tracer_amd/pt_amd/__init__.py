@@ -30,6 +30,7 @@ from ._lib import (  # noqa: F401
     SceneInfo,
     TILE_NOISE_DTYPE,
     TileNoise,
+    View,
     Window,
     abi_version,
     build_id,
@@ -54,6 +55,8 @@ from ._lib import (  # noqa: F401
     source_hash,
     tile_rects,
     tonemap,
+    view_atlas,
+    view_plan,
     unit_rays,
     gather_points,
     sh9_basis,

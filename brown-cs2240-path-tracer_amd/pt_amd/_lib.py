@@ -14,10 +14,10 @@ _CSRC = os.path.join(_PKG_ROOT, "csrc")
 # csrc/Makefile BUILD_SRCS: the sources whose SHA-256 the library carries as pt_build_id()
 _BUILD_SRCS = ["pt_kernels.hip", "pt_wavefront.hip", "pt_leafpass.hip", "pt_image.hip", "pt_features.hip", "pt_denoise.hip", "pt_query.hip", "pt_capi.hip", "pt_capi_render.hip",
                "pt_capi_adaptive.hip", "pt_capi_denoise.hip", "pt_capi_query.hip", "pt_capi_radiance.hip", "pt_capi_gather.hip", "pt_capi_selftest.hip",
-               "pt_capi_multi.hip", "pt_capi_camera.hip", "pt_capi_internal.h", "pt_math.h", "pt_flavour.h", "pt_layout.h",
+               "pt_capi_multi.hip", "pt_capi_camera.hip", "pt_capi_views.hip", "pt_capi_internal.h", "pt_math.h", "pt_flavour.h", "pt_layout.h",
                "pt_device.h", "pt_path.h", "pt_kernels.h", "../../include/pt_hip.h", "pt_bvh.cpp", "pt_leafbvh.h",
                "pt_leafbvh.cpp", "pt_leafskip.cpp", "pt_scene_layout.h", "pt_scene_layout.cpp", "pt_rect_plan.h",
-               "pt_rect_plan.cpp", "pt_query_plan.h", "pt_step_addr.h", "Makefile"]
+               "pt_rect_plan.cpp", "pt_view_plan.h", "pt_view_plan.cpp", "pt_query_plan.h", "pt_step_addr.h", "Makefile"]
 MODE_AUTO, MODE_MEGAKERNEL, MODE_WAVEFRONT = 0, 1, 2
 MATH_FNS = ["sin", "cos", "tan", "acos", "log2", "exp2", "pow", "sqrt", "div", "hash1u", "hash1", "hash2x",
             "hash2y", "min", "max", "ray_inv"]
@@ -114,6 +114,85 @@ def _rects(rects):
             raise PtError(-1, f"rects[{k}] must have four values (x0, y0, w, h), not {len(t)}")
         arr[k] = Window(*[_uint(v, f"rects[{k}] {n}") for v, n in zip(t, ("x0", "y0", "w", "h"))])
     return arr, len(items)
+
+
+class View(ctypes.Structure):
+    """pt_view (240 B): one view of Scene.render_views — its meta, the window of its image, its camera model,
+    its place in the atlas, its first frame."""
+    _fields_ = [("meta", ctypes.c_float * 48), ("win", Window), ("cam", Camera), ("dst_x", ctypes.c_uint32),
+                ("dst_y", ctypes.c_uint32), ("frame0", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+def _camera(camera) -> Camera:
+    """None, a model's name, or (model, lens_radius, focus_distance) as Scene.set_camera takes them."""
+    if camera is None:
+        return Camera(0, 0.0, 0.0, 0)
+    model, lens_radius, focus_distance = (camera, 0.0, 1.0) if isinstance(camera, (str, int)) else tuple(camera)
+    m = CAMERA_MODELS.index(model) if isinstance(model, str) and model in CAMERA_MODELS else model
+    if isinstance(m, str):
+        raise ValueError(f"unknown camera model {model!r} (one of {CAMERA_MODELS})")
+    return Camera(int(m), float(lens_radius), float(focus_distance), 0)
+
+
+def view_atlas(sizes, cols=None):
+    """A shelf packing of rectangles of sizes [(w, h), ...] in list order: rows of `cols` rectangles (None:
+    ceil(sqrt(n))), each row as tall as its tallest.  Returns (dsts [(x, y), ...], (atlas_w, atlas_h))."""
+    sizes = [(_uint(w, "view width", 1), _uint(h, "view height", 1)) for w, h in sizes]
+    if not sizes:
+        raise PtError(-1, "views: the list is empty (n must be at least 1)")
+    n = len(sizes)
+    cols = int(np.ceil(np.sqrt(n))) if cols is None else _uint(cols, "cols", 1)
+    dsts, x, y, row_h, aw = [], 0, 0, 0, 0
+    for k, (w, h) in enumerate(sizes):
+        if k and k % cols == 0:
+            x, y, row_h = 0, y + row_h, 0
+        dsts.append((x, y))
+        x += w
+        row_h = max(row_h, h)
+        aw = max(aw, x)
+    return dsts, (aw, y + row_h)
+
+
+def _views(views, atlas=None):
+    """A list of {meta, window=None, camera=None, dst=None, frame0=0} dicts as a pt_view array, its length and
+    the atlas (atlas_w, atlas_h): views without a dst are packed by view_atlas when none has one and no
+    atlas is given."""
+    try:
+        items = [dict(v) for v in views]
+    except (TypeError, ValueError):
+        raise PtError(-1, f"views must be a sequence of dicts (meta, window, camera, dst, frame0), not {views!r}") from None
+    arr = (View * max(1, len(items)))()
+    wins = []
+    for k, v in enumerate(items):
+        unknown = set(v) - {"meta", "window", "camera", "dst", "frame0"}
+        if unknown or "meta" not in v:
+            raise PtError(-1, f"views[{k}] needs meta and may hold window, camera, dst, frame0; not {sorted(unknown)}")
+        meta = _f32(v["meta"])
+        if meta.size != 48:
+            raise PtError(-1, f"views[{k}] meta must hold 48 floats, not {meta.size}")
+        win = _window(v.get("window"))
+        if win is None:
+            W, H = float(meta[0]), float(meta[1])
+            if not (1 <= W <= 32768 and 1 <= H <= 32768):
+                raise PtError(-1, f"views[{k}]: meta[0..1] must be integral resolutions in [1, 32768]")
+            win = Window(0, 0, int(W), int(H))
+        ctypes.memmove(arr[k].meta, meta.ctypes.data, 192)  # the bits, NaN payloads included
+        arr[k].win = win
+        arr[k].cam = _camera(v.get("camera"))
+        arr[k].frame0 = _uint(v.get("frame0", 0), f"views[{k}] frame0")
+        wins.append((win.w, win.h))
+    dsts = [v.get("dst") for v in items]
+    if items and all(d is None for d in dsts) and atlas is None:
+        dsts, atlas = view_atlas(wins)
+    if atlas is None or any(d is None for d in dsts):
+        raise PtError(-1, "views: give every view a dst and the call an atlas=(w, h), or neither")
+    for k, d in enumerate(dsts):
+        t = tuple(d)
+        if len(t) != 2:
+            raise PtError(-1, f"views[{k}] dst must be (x, y), not {d!r}")
+        arr[k].dst_x, arr[k].dst_y = _uint(t[0], f"views[{k}] dst x"), _uint(t[1], f"views[{k}] dst y")
+    aw, ah = (_uint(a, "atlas " + n_, 1) for a, n_ in zip(tuple(atlas), ("w", "h")))
+    return arr, len(items), (aw, ah)
 
 
 class TileNoise(ctypes.Structure):
@@ -428,6 +507,12 @@ def load_library():
     L.pt_render_rects.argtypes = [p, p, wp, wp, sz, u32, u32, u32, i, i, p, p, p]
     L.pt_render_rects_async.argtypes = [p, p, wp, wp, sz, u32, u32, u32, i, i, p, p, sz, p, p]
     L.pt_selftest_rect_plan.argtypes = [wp, u32, u32, wp, sz, p, ctypes.POINTER(ctypes.c_uint64)]
+    vp = ctypes.POINTER(View)
+    L.pt_render_views.argtypes = [p, vp, sz, u32, u32, u32, u32, i, i, p, p]
+    L.pt_render_views_async.argtypes = [p, vp, sz, u32, u32, u32, u32, i, i, p, sz, p, p]
+    L.pt_selftest_view_plan.argtypes = [vp, sz, u32, u32, p, ctypes.POINTER(ctypes.c_uint64)]
+    for fn in ("pt_render_views", "pt_render_views_async", "pt_selftest_view_plan"):
+        getattr(L, fn).restype = i
     L.pt_noise_tiles_async.argtypes = [p, p, p, u32, u32, sz, u32, u32, p, dbl, dbl, p, p]
     L.pt_noise_tiles.argtypes = [p, p, p, u32, u32, u32, u32, p, dbl, dbl, p]
     L.pt_tile_mean_async.argtypes = [p, p, u32, u32, sz, u32, u32, p, p, p]
@@ -805,6 +890,37 @@ class Scene:
                                                frame0, nframes, stride, max_depth, mode, ctypes.c_void_p(d_accum_ptr),
                                                ctypes.c_void_p(d_m2_ptr or None), pitch,
                                                ctypes.c_void_p(d_counters_ptr or None), ctypes.c_void_p(stream_ptr or None)))
+
+    def render_views(self, views, nframes: int, stride: int = 1, max_depth: int = -1, mode: int = MODE_AUTO, atlas=None,
+                     accum: np.ndarray | None = None, counters: bool = False):
+        """pt_render_views: a list of views — dicts {meta, window=None, camera=None, dst=None, frame0=0}; camera
+        as set_camera's arguments (model, lens_radius, focus_distance) — of this scene in ONE pass through the
+        pipeline.  accum is the atlas [atlas_h, atlas_w, 3], in/out; view v's window lands at dst=(x, y) and
+        holds the bits Scene.render(meta, frame0, nframes, stride, max_depth, window=window) gives under
+        set_camera(*camera); nothing else of accum changes.  With atlas=None and no dst the views are packed
+        by view_atlas.  Returns accum (and the counters, summed over the views, if requested)."""
+        arr, n, (aw, ah) = _views(views, atlas)
+        if accum is None:
+            accum = np.zeros((ah, aw, 3), np.float32)
+        if not isinstance(accum, np.ndarray) or accum.dtype != np.float32 or not accum.flags.c_contiguous or \
+                accum.size != aw * ah * 3:
+            raise ValueError("accum must be a contiguous float32 array of atlas_h*atlas_w*3 elements")
+        c = Counters()
+        _check(self._lib.pt_render_views(self._h, arr, n, aw, ah, _uint(nframes, "nframes"), _uint(stride, "stride"),
+                                         max_depth, mode, _ptr(accum), ctypes.byref(c) if counters else None))
+        return (accum, c.as_dict()) if counters else accum
+
+    def render_views_async(self, views, nframes: int, stride: int, max_depth: int, mode: int, d_accum_ptr: int, atlas=None,
+                           row_pitch=None, stream_ptr: int = 0, d_counters_ptr: int = 0):
+        """pt_render_views_async: d_accum_ptr addresses the atlas's FIRST pixel in a device buffer whose rows
+        are row_pitch pixels apart (default: the atlas's width); nothing outside the views' destination
+        rectangles is read or written.  Returns the atlas's (w, h)."""
+        arr, n, (aw, ah) = _views(views, atlas)
+        pitch = aw if row_pitch is None else _uint(row_pitch, "row_pitch")
+        _check(self._lib.pt_render_views_async(self._h, arr, n, aw, ah, _uint(nframes, "nframes"), _uint(stride, "stride"),
+                                               max_depth, mode, ctypes.c_void_p(d_accum_ptr), pitch,
+                                               ctypes.c_void_p(d_counters_ptr or None), ctypes.c_void_p(stream_ptr or None)))
+        return aw, ah
 
     def noise_tiles(self, accum, m2, tile, frames, tol: float, floor: float) -> np.ndarray:
         """pt_noise_tiles: the noise verdict of every tile of tile=(tile_w, tile_h) pixels over the host
@@ -1259,6 +1375,16 @@ def rect_plan(rects, W: int, H: int, frame=None):
     _check(load_library().pt_selftest_rect_plan(ctypes.byref(fr) if fr is not None else None, _uint(W, "W"), _uint(H, "H"),
                                                 arr, n, _ptr(first), ctypes.byref(npix)))
     return first[:n], int(npix.value)
+
+
+def view_plan(views, atlas=None):
+    """pt_selftest_view_plan (host only): a view list checked as a one-frame pt_render_views checks it.
+    Returns (first, npix): every view's first slot (uint64, list order) and the paths per frame."""
+    arr, n, (aw, ah) = _views(views, atlas)
+    first = np.zeros(n, np.uint64)
+    npix = ctypes.c_uint64(0)
+    _check(load_library().pt_selftest_view_plan(arr, n, aw, ah, _ptr(first), ctypes.byref(npix)))
+    return first, int(npix.value)
 
 
 def tonemap(accum, sample_runs: int) -> np.ndarray:

@@ -230,6 +230,56 @@ int pt_render_rects(pt_scene* scene, const float meta[48], const pt_window* fram
 int pt_selftest_rect_plan(const pt_window* frame, uint32_t W, uint32_t H, const pt_window* rects, size_t n,
                           uint64_t* first_out, uint64_t* npix_out);
 
+/* A list of views: n images of one scene, each with its own meta, window, camera model,
+ * first frame and place in a shared atlas, rendered in ONE pass through the pipeline — the paths of all
+ * views share the call's batches and launches, as the rectangles of pt_render_rects do. */
+typedef struct {
+    float     meta[48];     /* the view's own image and camera, as pt_render takes it */
+    pt_window win;          /* the window of THAT image to render (w, h >= 1, inside meta[0..1]) */
+    pt_camera cam;          /* model of this view; PT_CAMERA_PINHOLE = the reference's camera */
+    uint32_t  dst_x, dst_y; /* where window pixel (0, 0) lands in the atlas */
+    uint32_t  frame0;       /* this view's first frame: frames frame0 + i * frame_stride */
+    uint32_t  reserved;     /* 0 */
+} pt_view; /* 240 B */
+/* Render frames frame0_v + i*frame_stride (i < nframes) of every view v of the list.  Destination: the
+ * atlas, atlas_w x atlas_h pixels (each in [1, 32768]) whose first pixel d_accum addresses, rows row_pitch
+ * pixels apart (>= atlas_w); window pixel (i, j) of view v lives at
+ * d_accum + 3*((dst_y + j)*row_pitch + dst_x + i); in/out; nothing outside the views' destination
+ * rectangles (dst_x, dst_y, win.w, win.h) is read or written.
+ * Every such pixel gets exactly the bits pt_render_window[_async](meta_v, win_v, frame0_v, nframes,
+ * frame_stride, max_depth) would have put there on a scene whose pt_scene_set_camera is cam_v, started from
+ * the same values: for a pinhole view the reference's radiance(ray, seed) through the unchanged camera_ray,
+ * for a lens view pt_scene_set_camera's contract — a sample whose direction is not admitted leaves the
+ * accumulator's bits alone and counts nothing.  The counters are the sum over the views' paths.  The scene's
+ * own pt_scene_set_camera setting is not read (the views carry theirs); its other settings (vertex normals)
+ * apply as to any render.
+ * Shared by all views of a call, because the kernels after the generate kernel take them once per launch:
+ * max_depth, meta[45] (the continuation probability) and meta[46] > 0 (direct lighting only).  Views whose
+ * meta[45] differs bitwise from view 0's, or whose direct-only flag differs, are refused.
+ * A path's id is f * npix + q: npix the sum of the views' window areas ("paths per frame" for the batches
+ * and the counters), q the pixel's position in the concatenation of the views in list order, row-major
+ * inside each window; its salt is t = u32(f32(frame0_v + f * frame_stride)).  The route is always the
+ * wavefront pipeline with camera paths from the generate kernel: mode and the options kernel, fuse_gen and
+ * regen do not apply, as under a lens camera.
+ * views NULL, n = 0, n > 65536, npix >= 2^31, a meta[0..1] that pt_render refuses, a window of no area or
+ * outside its image, a destination rectangle outside the atlas, row_pitch < atlas_w, any two destination
+ * rectangles that share a pixel (two slots on one word would race), a view whose last frame index is
+ * >= 2^24, reserved != 0, a pt_camera that pt_scene_set_camera would refuse, and the shared-field
+ * mismatches above fail with PT_ERR_INVALID before anything is launched or copied; pt_last_error() names
+ * the offending view(s).  The view table lives in device memory of the scene and is written on `stream`
+ * before the first launch. */
+int pt_render_views_async(pt_scene* scene, const pt_view* views, size_t n, uint32_t atlas_w, uint32_t atlas_h,
+                          uint32_t nframes, uint32_t frame_stride, int max_depth, int mode, float* d_accum,
+                          size_t row_pitch, pt_counters* d_counters, void* stream);
+/* Blocking, host buffers: accum dense [atlas_h][atlas_w][3], in/out. */
+int pt_render_views(pt_scene* scene, const pt_view* views, size_t n, uint32_t atlas_w, uint32_t atlas_h,
+                    uint32_t nframes, uint32_t frame_stride, int max_depth, int mode, float* accum,
+                    pt_counters* counters);
+/* Host only, for tests: validates a list as a one-frame call does and writes each view's first slot (prefix
+ * sum of win.w * win.h in list order) and *npix_out = the paths per frame.  first_out, npix_out: nullable. */
+int pt_selftest_view_plan(const pt_view* views, size_t n, uint32_t atlas_w, uint32_t atlas_h, uint64_t* first_out,
+                          uint64_t* npix_out);
+
 /* A tile's noise verdict: its pixels, how many of them are noisy, and the largest error estimate. */
 typedef struct { uint32_t noisy, pixels; double max_err; } pt_tile_noise; /* 16 B */
 
