@@ -193,6 +193,30 @@ LaunchOpts launch_opts(const Opts& o, int mode, uint64_t paths, const SceneView&
 // radiance — the option wf_paths or the default target, at least two frames when the call has two, halved
 // down to one frame's paths when the device is short of memory, then PT_ERR_NOMEM — and the view's leaf keys
 int prepare_wavefront(pt_scene* s, const Opts& o, const SceneView& view, uint64_t npix, uint32_t nframes);
+// One call's way through the wavefront pipeline, for every kind of PathSource:
+//     WfCall c;
+//     c.open(s, o, fp, mode, npix, nframes)   shape_view (the leaf pass chosen for fp's camera), launch_opts,
+//                                             take_watchdog (an earlier asynchronous call failed)
+//     what is the call's own: c.lo forced, its table uploaded
+//     c.run(s, o, fp, src, ...)               prepare_wavefront, launch_wavefront, the control words' mirror copy
+// npix paths per frame; nframes frames or samples (a single-frame call: 1).  run's fp may be another than
+// open's (a view list launches with a reduced one).
+struct WfCall {
+    SceneView view;
+    LaunchOpts lo;
+    uint64_t npix = 0;
+    uint32_t nframes = 0;
+    int open(pt_scene* s, const Opts& o, const FrameParams& fp, int mode, uint64_t paths_per_frame, uint32_t frames);
+    int run(pt_scene* s, const Opts& o, const FrameParams& fp, const PathSource& src, uint32_t frame0, uint32_t stride,
+            bool accum, float* d_out, Counters* d_cnt, hipStream_t stream) const;
+};
+// A radiance query's or a gather's call (src: its n rays or points), samples sample0 .. sample0 + nsamples - 1
+// added to d_accum.  The render's options, except: the pipeline is the wavefront's whatever `kernel` says
+// (there is no megakernel for a list), and the leaf pass — chosen for a render by a probe from its camera —
+// is off unless option leaf_pre asks for it (1; 2 means off here).  FrameParams: a 1-row "image" of n paths
+// per sample with the call's rr_prob, direct_only and max_depth.
+int query_call(pt_scene* s, const PathSource& src, size_t n, uint32_t sample0, uint32_t nsamples, float rr_prob,
+               int32_t direct_only, int32_t max_depth, float* d_accum, Counters* d_cnt, hipStream_t stream);
 int render_impl(pt_scene* s, const float* meta, uint32_t frame0, uint32_t nframes, uint32_t stride, int max_depth,
                 int mode, bool accum, float* d_out, Counters* d_cnt, hipStream_t stream, const pt_window* win = nullptr,
                 const size_t* pitch = nullptr, float* d_m2 = nullptr, const pt_window* rects = nullptr, size_t nrects = 0);

@@ -31,31 +31,9 @@ static bool radiance_args(const void* s, const void* rays, const void* seeds, si
 // the arguments are checked (radiance_args)
 static int radiance_impl(pt_scene* s, const pt_ray* d_rays, const uint32_t* d_seeds, size_t n, const pt_radiance_params& prm,
                          float* d_accum, Counters* d_cnt, hipStream_t stream) {
-    HIP_TRY(hipSetDevice(s->device));
-    ProfScope prof_scope(s);
-    // the render's options, except: the pipeline is the wavefront's whatever `kernel` says (there is no
-    // megakernel for a ray list), and the leaf pass — chosen for a render by a probe from its camera — is
-    // off unless option leaf_pre asks for it (1; 2 means off here)
-    Opts o = opts_snapshot();
-    o.v[opt_index("kernel")] = "wavefront";
-    if (o.num("leaf_pre", 2) != 1) o.v[opt_index("leaf_pre")] = "0";
-    FrameParams fp{};
-    fp.rr_prob = prm.rr_prob;
-    fp.direct_only = prm.direct_only != 0 ? 1 : 0;
-    fp.max_depth = prm.max_depth;
-    fp.width = fp.win_w = fp.row_pitch = (uint32_t)n;  // a 1-row "image" of n paths per sample
-    fp.height = fp.win_h = 1;
-    const uint64_t paths = (uint64_t)n * prm.nsamples;
-    SceneView view;
-    PT_TRY(shape_view(s, o, fp, PT_MODE_WAVEFRONT, paths, view));
-    const LaunchOpts lo = launch_opts(o, PT_MODE_WAVEFRONT, paths, view);
-    PT_TRY(take_watchdog(s));  // an earlier asynchronous call failed
-    PT_TRY(prepare_wavefront(s, o, view, n, prm.nsamples));
     const RayList ql{reinterpret_cast<const float4*>(d_rays), d_seeds, (uint32_t)n};
-    HIP_TRY(launch_wavefront(lo, view, fp, s->wf, 0, prm.nsamples, 1, true, d_cnt != nullptr, d_accum, d_cnt, stream, s->ws,
-                             nullptr, nullptr, &ql));
-    HIP_TRY(hipMemcpyAsync(s->h_ctl.p, s->wf.ctl, 4 * kMaxParts * WF_CTL_WORDS, hipMemcpyDeviceToHost, stream));
-    return PT_OK;
+    return query_call(s, PathSource(ql), n, 0, prm.nsamples, prm.rr_prob, prm.direct_only, prm.max_depth, d_accum, d_cnt,
+                      stream);
 }
 
 extern "C" {

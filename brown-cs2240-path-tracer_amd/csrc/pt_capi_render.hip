@@ -431,33 +431,61 @@ int render_impl(pt_scene* s, const float* meta, uint32_t frame0, uint32_t nframe
     const uint64_t npix = list ? plan.npix : (uint64_t)fp.win_w * fp.win_h;  // paths per frame: the list's or the window's
     ProfScope prof_scope(s);
     const Opts o = opts_snapshot();
-    const uint64_t paths = npix * (accum ? nframes : 1);
     // a lens camera (pt_scene_set_camera): the wavefront pipeline with camera paths from the generate
     // kernel, whatever the mode and the options kernel, fuse_gen and regen say — as a ray list's
     // (pt_query_radiance); nothing else of the call changes
     LensCam lens;
     const LensCam* const cam = scene_camera(s, lens);
     if (cam) mode = PT_MODE_WAVEFRONT;
-    SceneView view;
-    if ((rc = shape_view(s, o, fp, mode, paths, view)) != PT_OK) return rc;
-    LaunchOpts lo = launch_opts(o, mode, paths, view);
+    WfCall c;
+    if ((rc = c.open(s, o, fp, mode, npix, accum ? nframes : 1)) != PT_OK) return rc;
     if (cam) {
-        lo.wavefront = true;
-        lo.literal = false;
+        c.lo.wavefront = true;
+        c.lo.literal = false;
     }
-    if ((rc = take_watchdog(s)) != PT_OK) return rc;  // an earlier asynchronous render failed
     RectList rl{};
-    if (list && (rc = upload_rects(s, plan, fp, !lo.wavefront, stream, rl)) != PT_OK) return rc;
-    const RectList* const prl = list ? &rl : nullptr;
-    if (lo.wavefront) {
-        PT_TRY(prepare_wavefront(s, o, view, npix, accum ? nframes : 1));
-        HIP_TRY(launch_wavefront(lo, view, fp, s->wf, frame0, nframes, stride, accum, d_cnt != nullptr, d_out, d_cnt,
-                                 stream, s->ws, d_m2, prl, nullptr, cam));
-        HIP_TRY(hipMemcpyAsync(s->h_ctl.p, s->wf.ctl, 4 * kMaxParts * WF_CTL_WORDS, hipMemcpyDeviceToHost, stream));
-        return PT_OK;
-    }
-    HIP_TRY(launch_megakernel(lo, view, fp, frame0, nframes, stride, accum, d_cnt != nullptr, d_out, d_cnt, stream, d_m2, prl));
+    if (list && (rc = upload_rects(s, plan, fp, !c.lo.wavefront, stream, rl)) != PT_OK) return rc;
+    if (c.lo.wavefront)
+        return c.run(s, o, fp, list ? PathSource(rl, cam, d_m2) : PathSource(cam, d_m2), frame0, stride, accum,
+                     d_out, d_cnt, stream);
+    HIP_TRY(launch_megakernel(c.lo, c.view, fp, frame0, nframes, stride, accum, d_cnt != nullptr, d_out, d_cnt, stream, d_m2,
+                              list ? &rl : nullptr));
     return PT_OK;
+}
+
+int WfCall::open(pt_scene* s, const Opts& o, const FrameParams& fp, int mode, uint64_t paths_per_frame, uint32_t frames) {
+    npix = paths_per_frame;
+    nframes = frames;
+    PT_TRY(shape_view(s, o, fp, mode, npix * nframes, view));
+    lo = launch_opts(o, mode, npix * nframes, view);
+    return take_watchdog(s);
+}
+
+int WfCall::run(pt_scene* s, const Opts& o, const FrameParams& fp, const PathSource& src, uint32_t frame0, uint32_t stride,
+                bool accum, float* d_out, Counters* d_cnt, hipStream_t stream) const {
+    PT_TRY(prepare_wavefront(s, o, view, npix, nframes));
+    HIP_TRY(launch_wavefront(lo, view, fp, s->wf, src, frame0, nframes, stride, accum, d_cnt != nullptr, d_out, d_cnt, stream,
+                             s->ws));
+    HIP_TRY(hipMemcpyAsync(s->h_ctl.p, s->wf.ctl, 4 * kMaxParts * WF_CTL_WORDS, hipMemcpyDeviceToHost, stream));
+    return PT_OK;
+}
+
+int query_call(pt_scene* s, const PathSource& src, size_t n, uint32_t sample0, uint32_t nsamples, float rr_prob,
+               int32_t direct_only, int32_t max_depth, float* d_accum, Counters* d_cnt, hipStream_t stream) {
+    HIP_TRY(hipSetDevice(s->device));
+    ProfScope prof_scope(s);
+    Opts o = opts_snapshot();
+    o.v[opt_index("kernel")] = "wavefront";
+    if (o.num("leaf_pre", 2) != 1) o.v[opt_index("leaf_pre")] = "0";
+    FrameParams fp{};
+    fp.rr_prob = rr_prob;
+    fp.direct_only = direct_only != 0 ? 1 : 0;
+    fp.max_depth = max_depth;
+    fp.width = fp.win_w = fp.row_pitch = (uint32_t)n;
+    fp.height = fp.win_h = 1;
+    WfCall c;
+    PT_TRY(c.open(s, o, fp, PT_MODE_WAVEFRONT, n, nsamples));
+    return c.run(s, o, fp, src, sample0, 1, true, d_accum, d_cnt, stream);
 }
 
 }  // namespace pt

@@ -60,17 +60,14 @@ static int render_views_impl(pt_scene* s, const pt_view* views, const ViewPlan& 
     if (nframes == 0) return PT_OK;
     ProfScope prof_scope(s);
     const Opts o = opts_snapshot();
-    const uint64_t paths = plan.npix * nframes;
     // the wavefront pipeline with camera paths from the generate kernel, whatever the mode and the options
     // kernel, fuse_gen and regen say — a lens camera's route.  The leaf pass is chosen through view 0's
     // camera, once (the choice changes kernels, never bits; a probe per view would hold the scene's mutex
     // n times)
-    SceneView view;
-    PT_TRY(shape_view(s, o, fp0, PT_MODE_WAVEFRONT, paths, view));
-    LaunchOpts lo = launch_opts(o, PT_MODE_WAVEFRONT, paths, view);
-    lo.wavefront = true;
-    lo.literal = false;
-    PT_TRY(take_watchdog(s));  // an earlier asynchronous render failed
+    WfCall c;
+    PT_TRY(c.open(s, o, fp0, PT_MODE_WAVEFRONT, plan.npix, nframes));
+    c.lo.wavefront = true;
+    c.lo.literal = false;
     // the table, on the call's stream before its first launch; the host rows are pageable, so the runtime
     // has read them when hipMemcpyAsync returns (as for a rectangle list)
     PT_TRY(s->d_views.ensure(rows.size() * sizeof(ViewRow), "view table"));
@@ -86,11 +83,7 @@ static int render_views_impl(pt_scene* s, const pt_view* views, const ViewPlan& 
     fp.direct_only = fp0.direct_only;
     fp.max_depth = fp0.max_depth;
     fp.row_pitch = (uint32_t)row_pitch;
-    PT_TRY(prepare_wavefront(s, o, view, plan.npix, nframes));
-    HIP_TRY(launch_wavefront(lo, view, fp, s->wf, 0, nframes, stride, true, d_cnt != nullptr, d_out, d_cnt, stream, s->ws,
-                             nullptr, nullptr, nullptr, nullptr, nullptr, &vl));
-    HIP_TRY(hipMemcpyAsync(s->h_ctl.p, s->wf.ctl, 4 * kMaxParts * WF_CTL_WORDS, hipMemcpyDeviceToHost, stream));
-    return PT_OK;
+    return c.run(s, o, fp, PathSource(vl), 0, stride, true, d_out, d_cnt, stream);
 }
 
 }  // namespace pt

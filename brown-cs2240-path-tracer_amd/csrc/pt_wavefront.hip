@@ -184,17 +184,23 @@ __device__ __forceinline__ uint32_t slot_path(uint32_t s, const FrameParams& fp,
     return s;
 }
 
-// The rectangle of a list that holds pixel q of its frame (q < rl.npix), and q's place inside it:
-// the last row whose first slot is <= q, by bisection (<= 17 steps; neighbouring lanes nearly always
-// agree on every one).
-__device__ __forceinline__ RectRow rect_of(const RectList& rl, uint32_t q, uint32_t& i, uint32_t& j) {
-    uint32_t lo = 0, hi = rl.n;
+// The last of n rows whose .first is <= q (rows ordered by .first, rows[0].first = 0), by bisection: the
+// rectangle or the view that holds pixel q of its list's frame (n <= 65536: at most 17 steps; neighbouring
+// lanes nearly always agree on every one)
+template <class Row>
+__device__ __forceinline__ uint32_t row_of(const Row* rows, uint32_t n, uint32_t q) {
+    uint32_t lo = 0, hi = n;
     while (hi - lo > 1) {
         const uint32_t mid = (lo + hi) >> 1;
-        if (rl.rows[mid].first <= q) lo = mid;
+        if (rows[mid].first <= q) lo = mid;
         else hi = mid;
     }
-    const RectRow r = rl.rows[lo];
+    return lo;
+}
+
+// The rectangle of a list that holds pixel q of its frame (q < rl.npix), and q's place inside it
+__device__ __forceinline__ RectRow rect_of(const RectList& rl, uint32_t q, uint32_t& i, uint32_t& j) {
+    const RectRow r = rl.rows[row_of(rl.rows, rl.n, q)];
     const uint32_t k = q - r.first;
     j = k / r.w;
     i = k - j * r.w;
@@ -251,20 +257,84 @@ __global__ __launch_bounds__(256) void k_wf_generate(FrameParams fp, WfBuffers w
     if (COUNT) flush_counters(c, cnt_out);
 }
 
+// What the generate kernels that can reject a sample share (k_wf_generate_rays, _cam, _views, _gather): a
+// sample that is not admitted makes no queue entry and counts nothing, and the admitted paths are compacted
+// into the queue.  The host zeroes the counts appended to before the launch.
+
+// No path for launch slot p: (-0, -0, -0) in its radiance slot, the one value k_wf_accum's
+// acc + (L >= 0 ? L : 0) adds without changing a bit of acc (x + -0 = x for every x, -0 included) and that
+// no traced path can leave there (a path's L starts at +0 and is only added to)
+__device__ __forceinline__ void mark_no_path(const WfBuffers& wb, uint32_t p) {
+    float* o = wb.rad + 3 * (size_t)p;
+    o[0] = -0.0f; o[1] = -0.0f; o[2] = -0.0f;
+}
+
+// The queue slot of launch slot p's path; every thread of the block calls it, adm: this lane has a path
+// (the slot of a lane without one means nothing).  NW: the block's waves.  With the fused kernel's regions
+// (wb.nreg > 0) the wave's slots are batch p / 64 of k_wf_generate's layout, so its paths take its region's
+// next entries, as k_wf_step_bf appends: one atomicAdd per wave on the region's count (a region receives at
+// most the batches k_wf_generate gives it, so it holds them).  Otherwise wave counts -> LDS -> prefix by
+// the first wave -> one atomicAdd per block on the queue's count (as k_wf_shade compacts).  No atomic when
+// nothing is kept; the order of the entries changes no path's result.
+template <uint32_t NW>
+__device__ __forceinline__ uint32_t compact_slot(const WfBuffers& wb, uint32_t p, bool adm) {
+    static_assert(NW <= 64 && (NW & (NW - 1)) == 0, "the first wave scans the wave counts");
+    const uint64_t keep = __ballot(adm);
+    const uint32_t R = wb.nreg;
+    uint32_t slot = 0;
+    if (R) {
+        if (keep) {  // wave-uniform
+            const uint32_t j = __builtin_amdgcn_readfirstlane(p) / 64;
+            const uint32_t rg = (uint32_t)((uint64_t)(j % R) * wb.rqi % R);
+            uint32_t base = 0;
+            if (lane_id() == 0) base = atomicAdd(&wb.rcnt[rg], (uint32_t)__popcll(keep));
+            slot = rg * wb.rstride + __shfl(base, 0, 64) + rank_below(keep);
+        }
+    } else {
+        __shared__ uint32_t s_cnt[NW];
+        const uint32_t wv = threadIdx.x / 64;
+        if (lane_id() == 0) s_cnt[wv] = (uint32_t)__popcll(keep);
+        __syncthreads();
+        if (threadIdx.x < 64) {
+            const uint32_t n = threadIdx.x < NW ? s_cnt[threadIdx.x] : 0u;
+            uint32_t incl = n;
+#pragma unroll
+            for (uint32_t off = 1; off < NW; off <<= 1) {
+                const uint32_t v = __shfl_up(incl, off, 64);
+                if (lane_id() >= off) incl += v;
+            }
+            const uint32_t total = __shfl(incl, NW - 1, 64);
+            uint32_t base = 0;
+            if (threadIdx.x == 0 && total) base = atomicAdd(&wb.ctl[WF_COUNT0], total);
+            base = __shfl(base, 0, 64);
+            if (threadIdx.x < NW) s_cnt[threadIdx.x] = base + incl - n;
+        }
+        __syncthreads();
+        slot = s_cnt[wv] + rank_below(keep);
+    }
+    return slot;
+}
+
+// the COUNT epilogue: an admitted path is one sample and one extension query
+template <bool COUNT>
+__device__ __forceinline__ void count_generated(bool adm, Counters* cnt_out) {
+    if (COUNT) {
+        Counters c = {};
+        if (adm) { c.samples++; c.ext_queries++; }
+        flush_counters(c, cnt_out);
+    }
+}
+
 // k_wf_generate for a ray list (pt_query_radiance; RayList, pt_kernels.h): launch slot p < P is sample
 // f = p / n of ray i = p - f n, so neighbouring lanes load neighbouring 32-byte rays (two float4 each)
 // and seeds.  Path id p — the radiance index k_wf_accum_rays reads.  The path's seed_in is the ray's seed
 // for sample 0 of the call and hash1u(seed + s * 16787) for its sample s = sample0 + fbase + f >= 1.
-// A ray that is not admitted (ray_admitted) makes no queue entry and counts nothing: the admitted paths
-// are compacted into the queue — one atomicAdd per block on the queue's count, or, with the fused
-// kernel's regions (wb.nreg > 0), one per wave on the count of the region its 64-slot batch goes to, as
-// k_wf_step_bf appends.  The host zeroes those counts before the launch.  A region receives at most the
-// batches k_wf_generate gives it, so it holds them; the order of the entries changes no path's result.
+// A ray that is not admitted (ray_admitted) has no path; its radiance slot is left alone (k_wf_accum_rays
+// takes the test again).
 template <bool COUNT>
 __global__ __launch_bounds__(1024) void k_wf_generate_rays(WfBuffers wb, RayList ql, uint32_t sample0, uint32_t fbase,
                                                            uint32_t P, Counters* cnt_out) {
     const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t R = wb.nreg;
     bool adm = false;
     Ray r;
     PathState ps;
@@ -280,59 +350,20 @@ __global__ __launch_bounds__(1024) void k_wf_generate_rays(WfBuffers wb, RayList
             path_begin_ray(r, s == 0 ? s0 : hash1u(s0 + s * 16787u), ps);
         }
     }
-    const uint64_t keep = __ballot(adm);
-    uint32_t slot = 0;
-    if (R) {  // the wave's slots are batch p / 64 of k_wf_generate's layout: its region's next entries
-        if (keep) {  // wave-uniform
-            const uint32_t j = __builtin_amdgcn_readfirstlane(p) / 64;
-            const uint32_t rg = (uint32_t)((uint64_t)(j % R) * wb.rqi % R);
-            uint32_t base = 0;
-            if (lane_id() == 0) base = atomicAdd(&wb.rcnt[rg], (uint32_t)__popcll(keep));
-            slot = rg * wb.rstride + __shfl(base, 0, 64) + rank_below(keep);
-        }
-    } else {  // wave counts -> LDS prefix -> one atomicAdd per block (as k_wf_shade compacts)
-        __shared__ uint32_t s_cnt[16];
-        const uint32_t wv = threadIdx.x / 64;
-        if (lane_id() == 0) s_cnt[wv] = (uint32_t)__popcll(keep);
-        __syncthreads();
-        if (threadIdx.x < 64) {
-            const uint32_t n = threadIdx.x < 16 ? s_cnt[threadIdx.x] : 0u;
-            uint32_t incl = n;
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) {
-                const uint32_t v = __shfl_up(incl, off, 64);
-                if (lane_id() >= (uint32_t)off) incl += v;
-            }
-            const uint32_t total = __shfl(incl, 63, 64);
-            uint32_t base = 0;
-            if (threadIdx.x == 0 && total) base = atomicAdd(&wb.ctl[WF_COUNT0], total);
-            base = __shfl(base, 0, 64);
-            if (threadIdx.x < 16) s_cnt[threadIdx.x] = base + incl - n;
-        }
-        __syncthreads();
-        slot = s_cnt[wv] + rank_below(keep);
-    }
+    const uint32_t slot = compact_slot<16>(wb, p, adm);
     if (adm) store_entry(wb.ext, slot, r, p, ps);
-    if (COUNT) {
-        Counters c = {};
-        if (adm) { c.samples++; c.ext_queries++; }
-        flush_counters(c, cnt_out);
-    }
+    count_generated<COUNT>(adm, cnt_out);
 }
 
 // k_wf_generate under a lens camera (LensCam): k_wf_generate's slot maps — the window,
-// the rectangle list, raw_salt — with path_begin_model<MODEL> for path_begin, and k_wf_generate_rays'
-// compaction for the samples whose direction is not admitted: such a sample makes no queue entry and
-// counts nothing, and its radiance slot gets (-0, -0, -0), the one value k_wf_accum's acc + (L >= 0 ? L : 0)
-// adds without changing a bit of acc (x + -0 = x for every x, -0 included).  The host zeroes the queue's
-// and the regions' counts before the launch, as for a ray list.
+// the rectangle list, raw_salt — with path_begin_model<MODEL> for path_begin; a sample whose direction is
+// not admitted has no path (mark_no_path).
 template <bool COUNT, uint32_t MODEL, class... RL>
 __global__ __launch_bounds__(256) void k_wf_generate_cam(FrameParams fp, LensCam lc, WfBuffers wb, uint32_t frame0,
                                                          uint32_t stride, uint32_t fbase, uint32_t P, bool raw_salt,
                                                          Counters* cnt_out, RL... rl) {
     static_assert(sizeof...(RL) <= 1, "at most the one rectangle list");
     const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t R = wb.nreg;
     bool adm = false;
     Ray r;
     PathState ps;
@@ -342,54 +373,16 @@ __global__ __launch_bounds__(256) void k_wf_generate_cam(FrameParams fp, LensCam
         else (void)slot_path(p, fp, x, y, f);
         const uint32_t t = raw_salt ? frame0 : (uint32_t)(float)(frame0 + (fbase + f) * stride);
         adm = path_begin_model<MODEL>(fp, lc, x, y, t, r, ps);
-        if (!adm) {
-            float* o = wb.rad + 3 * (size_t)p;
-            o[0] = -0.0f; o[1] = -0.0f; o[2] = -0.0f;
-        }
+        if (!adm) mark_no_path(wb, p);
     }
-    const uint64_t keep = __ballot(adm);
-    uint32_t slot = 0;
-    if (R) {  // the wave's slots are batch p / 64 of k_wf_generate's layout: its region's next entries
-        if (keep) {  // wave-uniform
-            const uint32_t j = __builtin_amdgcn_readfirstlane(p) / 64;
-            const uint32_t rg = (uint32_t)((uint64_t)(j % R) * wb.rqi % R);
-            uint32_t base = 0;
-            if (lane_id() == 0) base = atomicAdd(&wb.rcnt[rg], (uint32_t)__popcll(keep));
-            slot = rg * wb.rstride + __shfl(base, 0, 64) + rank_below(keep);
-        }
-    } else {  // wave counts -> one atomicAdd per block (four waves)
-        __shared__ uint32_t s_cnt[4];
-        __shared__ uint32_t s_base;
-        const uint32_t wv = threadIdx.x / 64;
-        if (lane_id() == 0) s_cnt[wv] = (uint32_t)__popcll(keep);
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const uint32_t total = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
-            s_base = total ? atomicAdd(&wb.ctl[WF_COUNT0], total) : 0u;
-        }
-        __syncthreads();
-        slot = s_base + rank_below(keep);
-        for (uint32_t w = 0; w < wv; ++w) slot += s_cnt[w];
-    }
+    const uint32_t slot = compact_slot<4>(wb, p, adm);
     if (adm) store_entry(wb.ext, slot, r, p, ps);
-    if (COUNT) {
-        Counters c = {};
-        if (adm) { c.samples++; c.ext_queries++; }
-        flush_counters(c, cnt_out);
-    }
+    count_generated<COUNT>(adm, cnt_out);
 }
 
-// The view of a list that holds pixel q of its frame (q < vl.npix): the last row whose first slot is <= q,
-// by bisection with the shape of rect_of (n <= 65536: at most 17 steps; neighbouring lanes nearly always
-// agree on every one).
+// The view of a list that holds pixel q of its frame (q < vl.npix)
 __device__ __forceinline__ const ViewRow* view_of(const ViewList& vl, uint32_t q) {
-    uint32_t lo = 0, hi = vl.n;
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (vl.rows[mid].first <= q) lo = mid;
-        else hi = mid;
-    }
-    return vl.rows + lo;
+    return vl.rows + row_of(vl.rows, vl.n, q);
 }
 
 // k_wf_generate for a view list (pt_render_views; ViewList, pt_kernels.h): launch slot
@@ -397,14 +390,12 @@ __device__ __forceinline__ const ViewRow* view_of(const ViewList& vl, uint32_t q
 // the row's camera block into a FrameParams of its own — ten float4 loads; a wave inside one view loads one
 // address — and begins its path with path_begin (a pinhole row) or path_begin_model of the row's model, at
 // pixel (x0 + i, y0 + j) of the view's image and salt u32(f32(frame0_v + (fbase + f) * stride)).  Those
-// functions and camera_ray are the other generate kernels' own.  Samples that are not admitted, the
-// (-0, -0, -0) radiance slot and the compaction are k_wf_generate_cam's (the statements are repeated here so
-// that that kernel's code does not change); the host zeroes the counts before the launch.
+// functions and camera_ray are the other generate kernels' own; a lens row's sample that is not admitted
+// has no path (mark_no_path).
 template <bool COUNT>
 __global__ __launch_bounds__(256) void k_wf_generate_views(ViewList vl, WfBuffers wb, uint32_t stride, uint32_t fbase,
                                                            uint32_t P, Counters* cnt_out) {
     const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t R = wb.nreg;
     bool adm = false;
     Ray r;
     PathState ps;
@@ -436,57 +427,22 @@ __global__ __launch_bounds__(256) void k_wf_generate_views(ViewList vl, WfBuffer
             case CAM_EQUIRECT: adm = path_begin_model<CAM_EQUIRECT>(fp, lc, x, y, t, r, ps); break;
             default: r = path_begin(fp, x, y, t, ps); adm = true; break;  // the pinhole: every sample has a path
         }
-        if (!adm) {
-            float* o = wb.rad + 3 * (size_t)p;
-            o[0] = -0.0f; o[1] = -0.0f; o[2] = -0.0f;
-        }
+        if (!adm) mark_no_path(wb, p);
     }
-    const uint64_t keep = __ballot(adm);
-    uint32_t slot = 0;
-    if (R) {  // the wave's slots are batch p / 64 of k_wf_generate's layout: its region's next entries
-        if (keep) {  // wave-uniform
-            const uint32_t j = __builtin_amdgcn_readfirstlane(p) / 64;
-            const uint32_t rg = (uint32_t)((uint64_t)(j % R) * wb.rqi % R);
-            uint32_t base = 0;
-            if (lane_id() == 0) base = atomicAdd(&wb.rcnt[rg], (uint32_t)__popcll(keep));
-            slot = rg * wb.rstride + __shfl(base, 0, 64) + rank_below(keep);
-        }
-    } else {  // wave counts -> one atomicAdd per block (four waves)
-        __shared__ uint32_t s_cnt[4];
-        __shared__ uint32_t s_base;
-        const uint32_t wv = threadIdx.x / 64;
-        if (lane_id() == 0) s_cnt[wv] = (uint32_t)__popcll(keep);
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const uint32_t total = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
-            s_base = total ? atomicAdd(&wb.ctl[WF_COUNT0], total) : 0u;
-        }
-        __syncthreads();
-        slot = s_base + rank_below(keep);
-        for (uint32_t w = 0; w < wv; ++w) slot += s_cnt[w];
-    }
+    const uint32_t slot = compact_slot<4>(wb, p, adm);
     if (adm) store_entry(wb.ext, slot, r, p, ps);
-    if (COUNT) {
-        Counters c = {};
-        if (adm) { c.samples++; c.ext_queries++; }
-        flush_counters(c, cnt_out);
-    }
+    count_generated<COUNT>(adm, cnt_out);
 }
 
 // k_wf_generate for a gather list (pt_gather; GatherList, pt_kernels.h): launch slot
 // p < P is sample f = p / n of point i = p - f n, so neighbouring lanes load neighbouring 32-byte points
 // (two float4 each).  Path id p.  The sample's direction is drawn on the spot (gather_ray<MODE>) with
 // sd = gather_seed(seed, sample0 + fbase + f) and its path enters with seed_in = hash1u(sd + 7).  A point
-// or a sample that is not admitted makes no queue entry and counts nothing; its radiance slot gets the
-// lens cameras' (-0, -0, -0), which no traced path can leave there (a path's L starts at +0 and is only
-// added to), so k_wf_accum_gather skips it.  The admitted paths are compacted exactly as
-// k_wf_generate_rays compacts them (the statements are repeated here so that that kernel's code does not
-// change); the host zeroes the counts before the launch.
+// or a sample that is not admitted has no path (mark_no_path), and k_wf_accum_gather skips its slot.
 template <bool COUNT, uint32_t MODE>
 __global__ __launch_bounds__(1024) void k_wf_generate_gather(WfBuffers wb, GatherList gl, uint32_t sample0, uint32_t fbase,
                                                              uint32_t P, Counters* cnt_out) {
     const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t R = wb.nreg;
     bool adm = false;
     Ray r;
     PathState ps;
@@ -499,48 +455,12 @@ __global__ __launch_bounds__(1024) void k_wf_generate_gather(WfBuffers wb, Gathe
             r.inv = r.d;  // not stored: the trace kernels take 1 / d when they unpack the entry
             path_begin_ray(r, hash1u(sd + 7u), ps);
         } else {
-            float* o = wb.rad + 3 * (size_t)p;
-            o[0] = -0.0f; o[1] = -0.0f; o[2] = -0.0f;
+            mark_no_path(wb, p);
         }
     }
-    const uint64_t keep = __ballot(adm);
-    uint32_t slot = 0;
-    if (R) {  // the wave's slots are batch p / 64 of k_wf_generate's layout: its region's next entries
-        if (keep) {  // wave-uniform
-            const uint32_t j = __builtin_amdgcn_readfirstlane(p) / 64;
-            const uint32_t rg = (uint32_t)((uint64_t)(j % R) * wb.rqi % R);
-            uint32_t base = 0;
-            if (lane_id() == 0) base = atomicAdd(&wb.rcnt[rg], (uint32_t)__popcll(keep));
-            slot = rg * wb.rstride + __shfl(base, 0, 64) + rank_below(keep);
-        }
-    } else {  // wave counts -> LDS prefix -> one atomicAdd per block (as k_wf_generate_rays)
-        __shared__ uint32_t s_cnt[16];
-        const uint32_t wv = threadIdx.x / 64;
-        if (lane_id() == 0) s_cnt[wv] = (uint32_t)__popcll(keep);
-        __syncthreads();
-        if (threadIdx.x < 64) {
-            const uint32_t n = threadIdx.x < 16 ? s_cnt[threadIdx.x] : 0u;
-            uint32_t incl = n;
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) {
-                const uint32_t v = __shfl_up(incl, off, 64);
-                if (lane_id() >= (uint32_t)off) incl += v;
-            }
-            const uint32_t total = __shfl(incl, 63, 64);
-            uint32_t base = 0;
-            if (threadIdx.x == 0 && total) base = atomicAdd(&wb.ctl[WF_COUNT0], total);
-            base = __shfl(base, 0, 64);
-            if (threadIdx.x < 16) s_cnt[threadIdx.x] = base + incl - n;
-        }
-        __syncthreads();
-        slot = s_cnt[wv] + rank_below(keep);
-    }
+    const uint32_t slot = compact_slot<16>(wb, p, adm);
     if (adm) store_entry(wb.ext, slot, r, p, ps);
-    if (COUNT) {
-        Counters c = {};
-        if (adm) { c.samples++; c.ext_queries++; }
-        flush_counters(c, cnt_out);
-    }
+    count_generated<COUNT>(adm, cnt_out);
 }
 
 // One sample of every point as the ray and seed a radiance query takes (pt_gather_rays): pt_ray
@@ -1724,14 +1644,88 @@ static SceneView bf_view(const SceneView& sc) {
     return v;
 }
 
+// one part of a batch: its buffers, first frame, paths and stream
+struct WfPart { WfBuffers w; uint32_t fbase, P; hipStream_t st; };
+
+// A part's camera paths over the window's or a rectangle list's slot map (RL: nothing, or the list):
+// k_wf_generate, or under a lens camera k_wf_generate_cam's instance of the model
+template <bool COUNT, class... RL>
+static void launch_generate_pixels(const PathSource& src, const FrameParams& fp, const WfPart& pt, uint32_t frame0,
+                                   uint32_t stride, bool accum, Counters* cnt, const RL&... rl) {
+    if (!src.cam) {
+        const dim3 ggrid((std::max(pt.P, pt.w.nreg) + 255) / 256);  // a thread per region sets its count
+        PT_LAUNCH(KID_WF_GENERATE, pt.st, (k_wf_generate<COUNT, RL...>), ggrid, dim3(256), 0, pt.st, fp, pt.w, frame0, stride,
+                  pt.fbase, pt.P, !accum, cnt, rl...);
+        return;
+    }
+    auto kern = k_wf_generate_cam<COUNT, CAM_EQUIRECT, RL...>;
+    if (src.cam->model == CAM_THIN_LENS) kern = k_wf_generate_cam<COUNT, CAM_THIN_LENS, RL...>;
+    else if (src.cam->model == CAM_ORTHO) kern = k_wf_generate_cam<COUNT, CAM_ORTHO, RL...>;
+    PT_LAUNCH(KID_WF_GENERATE, pt.st, kern, dim3((pt.P + 255) / 256), dim3(256), 0, pt.st, fp, *src.cam, pt.w, frame0, stride,
+              pt.fbase, pt.P, !accum, cnt, rl...);
+}
+
+// A part's first-vertex paths, by the source's kind (the table in pt_kernels.h)
+template <bool COUNT>
+static void launch_generate(const PathSource& src, const FrameParams& fp, const WfPart& pt, uint32_t frame0, uint32_t stride,
+                            bool accum, Counters* cnt) {
+    const dim3 qgrid((pt.P + 1023) / 1024);
+    switch (src.kind) {
+        case PathSource::WINDOW: launch_generate_pixels<COUNT>(src, fp, pt, frame0, stride, accum, cnt); break;
+        case PathSource::RECTS: launch_generate_pixels<COUNT>(src, fp, pt, frame0, stride, accum, cnt, src.rects); break;
+        case PathSource::RAYS:
+            PT_LAUNCH(KID_WF_GENERATE, pt.st, (k_wf_generate_rays<COUNT>), qgrid, dim3(1024), 0, pt.st, pt.w, src.rays, frame0,
+                      pt.fbase, pt.P, cnt);
+            break;
+        case PathSource::GATHER: {
+            const auto kern = src.gather.mode == GATHER_SH9 ? k_wf_generate_gather<COUNT, GATHER_SH9>
+                                                            : k_wf_generate_gather<COUNT, GATHER_COSINE>;
+            PT_LAUNCH(KID_WF_GENERATE, pt.st, kern, qgrid, dim3(1024), 0, pt.st, pt.w, src.gather, frame0, pt.fbase, pt.P, cnt);
+            break;
+        }
+        case PathSource::VIEWS:
+            PT_LAUNCH(KID_WF_GENERATE, pt.st, (k_wf_generate_views<COUNT>), dim3((pt.P + 255) / 256), dim3(256), 0, pt.st,
+                      src.views, pt.w, stride, pt.fbase, pt.P, cnt);
+            break;
+    }
+}
+
+// A batch's radiance (Fb frames of npix paths; sbase: the call's sample index of the first) added to `out`,
+// by the source's kind
+static void launch_accum(const PathSource& src, const FrameParams& fp, const float* rad, uint32_t npix, uint32_t sbase,
+                         uint32_t Fb, bool accum, float* out, hipStream_t stream) {
+    const dim3 grid((npix + 255) / 256), block(256);
+    switch (src.kind) {
+        case PathSource::WINDOW:
+            PT_LAUNCH(KID_WF_ACCUM, stream, (k_wf_accum<>), grid, block, 0, stream, rad, out, npix, fp.win_w, fp.row_pitch, Fb,
+                      accum, src.m2);
+            break;
+        case PathSource::RECTS:
+            PT_LAUNCH(KID_WF_ACCUM, stream, (k_wf_accum<RectList>), grid, block, 0, stream, rad, out, npix, fp.win_w,
+                      fp.row_pitch, Fb, accum, src.m2, src.rects);
+            break;
+        case PathSource::RAYS:
+            PT_LAUNCH(KID_WF_ACCUM, stream, k_wf_accum_rays, grid, block, 0, stream, rad, out, src.rays, Fb);
+            break;
+        case PathSource::GATHER: {
+            const auto kern = src.gather.mode == GATHER_SH9 ? k_wf_accum_gather<GATHER_SH9> : k_wf_accum_gather<GATHER_COSINE>;
+            PT_LAUNCH(KID_WF_ACCUM, stream, kern, grid, block, 0, stream, rad, out, src.gather, sbase, Fb);
+            break;
+        }
+        case PathSource::VIEWS:
+            PT_LAUNCH(KID_WF_ACCUM, stream, k_wf_accum_views, grid, block, 0, stream, rad, out, src.views, fp.row_pitch, Fb);
+            break;
+    }
+}
+
 template <bool LDS, int TRAV, bool COUNT>
-static hipError_t wf_render_t(const SceneView& sc_in, const FrameParams& fp, const WfBuffers& wb, uint32_t frame0,
-                              uint32_t nframes, uint32_t stride, bool accum, float* out, Counters* cnt,
-                              hipStream_t stream, const WfStreams& ws, const LaunchOpts& lo, float* m2, const RectList* rl,
-                              const RayList* ql, const LensCam* cam, const GatherList* gl, const ViewList* vl) {
+static hipError_t wf_render_t(const SceneView& sc_in, const FrameParams& fp, const WfBuffers& wb, const PathSource& src,
+                              uint32_t frame0, uint32_t nframes, uint32_t stride, bool accum, float* out, Counters* cnt,
+                              hipStream_t stream, const WfStreams& ws, const LaunchOpts& lo) {
     SceneView sc = bf_view<TRAV, COUNT>(sc_in);
-    // paths per frame: the list's, else the window's (a ray list: its rays, a "frame" being one sample of each)
-    const uint32_t npix = vl ? vl->npix : gl ? gl->n : ql ? ql->n : rl ? rl->npix : fp.win_w * fp.win_h;
+    const uint32_t npix = src.paths_per_frame(fp);
+    // the fused kernel's first launch makes the camera paths itself (GEN)
+    const bool fgen = flv_fused(TRAV) && src.fused_gen(lo);
     // the batch in lo.parts parts on as many streams when a part holds at least a frame: one
     // part's kernel fills the others' launch tails and boundaries (and, with separate trace and
     // shade kernels, a VALU-bound trace runs beside an HBM-bound shade)
@@ -1774,17 +1768,14 @@ static hipError_t wf_render_t(const SceneView& sc_in, const FrameParams& fp, con
     // narrow payload (pt_capi.hip: <= 32 entries and nodes, stackless replay and bf_narrow on)
     constexpr bool kNarrowOk = flv_fused(TRAV) && LDS && !COUNT;
     const bool narrow = kNarrowOk && sc.bfnode && sc.bfnarrow;
-    if constexpr (flv_fused(TRAV)) {  // the camera batches' table (k_wf_camtab), before every part's GEN launch
-        if (lo.fuse_gen && !rl && !ql && !cam && !gl && !vl) {
-            if (sc.n_tris - sc.mb_base > 64) return hipErrorInvalidValue;  // mailbox scenes: <= 64 entries
-            hipLaunchKernelGGL(k_wf_camtab, dim3(1), dim3(64), 0, stream, sc, fp, wb.camtab);
-        }
+    if (fgen) {  // the camera batches' table (k_wf_camtab), before every part's GEN launch
+        if (sc.n_tris - sc.mb_base > 64) return hipErrorInvalidValue;  // mailbox scenes: <= 64 entries
+        hipLaunchKernelGGL(k_wf_camtab, dim3(1), dim3(64), 0, stream, sc, fp, wb.camtab);
     }
     for (uint32_t fb = 0; fb < nframes; fb += F) {
         const uint32_t Fb = std::min(F, nframes - fb);
         // frames of the batch dealt to the parts in contiguous runs (part h: frames fb + f0[h] ..)
-        struct Part { WfBuffers w; uint32_t fbase, P; hipStream_t st; };
-        Part pv[kMaxParts];
+        WfPart pv[kMaxParts];
         int nh = 0;
         uint32_t f0 = 0;
         for (int h = 0; h < np && f0 < Fb; ++h) {
@@ -1815,22 +1806,16 @@ static hipError_t wf_render_t(const SceneView& sc_in, const FrameParams& fp, con
                 pv[h].w.rqi = qi;
             }
         }
-        // the fused kernel's first launch makes the camera paths itself (GEN); it appends into
-        // count slot 1, zeroed here (k_wf_generate zeroes it otherwise) — on the caller's stream
+        // the fused kernel's GEN launch appends into count slot 1, zeroed here (k_wf_generate zeroes it
+        // otherwise), and a compacting generate kernel into the queue's count or the regions' count slots 0,
+        // zeroed here with slot 1 (as k_wf_generate would have set them) — on the caller's stream
         // before the fork: on a part's stream the second part's memset waited ~0.5 ms for a CU slot
         // behind the first part's first launch, and the parts ran that far apart (a kernel trace of
         // the bench, r06m)
-        // (a rectangle list's camera paths come from k_wf_generate's list instance: the fuse_gen = 0 route)
-        // (and a ray list's from k_wf_generate_rays, which appends to the queue's count or its regions' count
-        // slots 0: zeroed here with slot 1, as k_wf_generate would have set them)
-        // (and a lens camera's from k_wf_generate_cam, which compacts as k_wf_generate_rays does)
-        // (and a gather list's from k_wf_generate_gather, likewise)
-        // (and a view list's from k_wf_generate_views, likewise)
-        const bool fgen = flv_fused(TRAV) && lo.fuse_gen && !rl && !ql && !cam && !gl && !vl;
         if (fgen)
             for (int h = 0; h < nh; ++h)
                 HIP_RETURN_IF(hipMemsetAsync(pv[h].w.rcnt + kRegions, 0, kRegions * sizeof(uint32_t), stream));
-        if (ql || cam || gl || vl)
+        if (src.compacts())
             for (int h = 0; h < nh; ++h) {
                 HIP_RETURN_IF(hipMemsetAsync(pv[h].w.ctl + WF_COUNT0, 0, 2 * sizeof(uint32_t), stream));
                 if (flv_fused(TRAV)) HIP_RETURN_IF(hipMemsetAsync(pv[h].w.rcnt, 0, 2 * kRegions * sizeof(uint32_t), stream));
@@ -1854,45 +1839,7 @@ static hipError_t wf_render_t(const SceneView& sc_in, const FrameParams& fp, con
             else
                 regen_q = 0;  // one launch admits them all: the plain first launch
         }
-        for (int h = 0; h < nh && !fgen; ++h) {
-            const dim3 ggrid((std::max(pv[h].P, pv[h].w.nreg) + 255) / 256);
-            if (vl) {
-                PT_LAUNCH(KID_WF_GENERATE, pv[h].st, (k_wf_generate_views<COUNT>), dim3((pv[h].P + 255) / 256), dim3(256), 0,
-                          pv[h].st, *vl, pv[h].w, stride, pv[h].fbase, pv[h].P, cnt);
-            } else if (gl) {
-                const dim3 qgrid((pv[h].P + 1023) / 1024);
-                if (gl->mode == GATHER_SH9)
-                    PT_LAUNCH(KID_WF_GENERATE, pv[h].st, (k_wf_generate_gather<COUNT, GATHER_SH9>), qgrid, dim3(1024), 0,
-                              pv[h].st, pv[h].w, *gl, frame0, pv[h].fbase, pv[h].P, cnt);
-                else
-                    PT_LAUNCH(KID_WF_GENERATE, pv[h].st, (k_wf_generate_gather<COUNT, GATHER_COSINE>), qgrid, dim3(1024), 0,
-                              pv[h].st, pv[h].w, *gl, frame0, pv[h].fbase, pv[h].P, cnt);
-            } else if (ql) {
-                PT_LAUNCH(KID_WF_GENERATE, pv[h].st, (k_wf_generate_rays<COUNT>), dim3((pv[h].P + 1023) / 1024), dim3(1024), 0,
-                          pv[h].st, pv[h].w, *ql, frame0, pv[h].fbase, pv[h].P, cnt);
-            } else if (cam) {
-                const dim3 cgrid((pv[h].P + 255) / 256);
-#define PT_GEN_CAM(M)                                                                                                   \
-    do {                                                                                                                \
-        if (rl)                                                                                                         \
-            PT_LAUNCH(KID_WF_GENERATE, pv[h].st, (k_wf_generate_cam<COUNT, M, RectList>), cgrid, dim3(256), 0, pv[h].st, \
-                      fp, *cam, pv[h].w, frame0, stride, pv[h].fbase, pv[h].P, !accum, cnt, *rl);                       \
-        else                                                                                                            \
-            PT_LAUNCH(KID_WF_GENERATE, pv[h].st, (k_wf_generate_cam<COUNT, M>), cgrid, dim3(256), 0, pv[h].st, fp,      \
-                      *cam, pv[h].w, frame0, stride, pv[h].fbase, pv[h].P, !accum, cnt);                                \
-    } while (0)
-                if (cam->model == CAM_THIN_LENS) PT_GEN_CAM(CAM_THIN_LENS);
-                else if (cam->model == CAM_ORTHO) PT_GEN_CAM(CAM_ORTHO);
-                else PT_GEN_CAM(CAM_EQUIRECT);
-#undef PT_GEN_CAM
-            } else if (rl) {
-                PT_LAUNCH(KID_WF_GENERATE, pv[h].st, (k_wf_generate<COUNT, RectList>), ggrid, dim3(256), 0, pv[h].st,
-                          fp, pv[h].w, frame0, stride, pv[h].fbase, pv[h].P, !accum, cnt, *rl);
-            } else {
-                PT_LAUNCH(KID_WF_GENERATE, pv[h].st, (k_wf_generate<COUNT>), ggrid, dim3(256), 0, pv[h].st,
-                          fp, pv[h].w, frame0, stride, pv[h].fbase, pv[h].P, !accum, cnt);
-            }
-        }
+        for (int h = 0; h < nh && !fgen; ++h) launch_generate<COUNT>(src, fp, pv[h], frame0, stride, accum, cnt);
         // launch `it` of part h (in_q: the queue the trace kernels read, it & 1)
         auto step = [&](int h, int it) -> hipError_t {
             const int in_q = it & 1;
@@ -1974,43 +1921,36 @@ static hipError_t wf_render_t(const SceneView& sc_in, const FrameParams& fp, con
                 HIP_RETURN_IF(hipStreamWaitEvent(stream, ws.join[h], 0));
             }
         }
-        if (vl)
-            PT_LAUNCH(KID_WF_ACCUM, stream, k_wf_accum_views, dim3((npix + 255) / 256), dim3(256), 0, stream, wb.rad, out, *vl,
-                      fp.row_pitch, Fb);
-        else if (gl && gl->mode == GATHER_SH9)
-            PT_LAUNCH(KID_WF_ACCUM, stream, (k_wf_accum_gather<GATHER_SH9>), dim3((npix + 255) / 256), dim3(256), 0, stream,
-                      wb.rad, out, *gl, frame0 + fb, Fb);
-        else if (gl)
-            PT_LAUNCH(KID_WF_ACCUM, stream, (k_wf_accum_gather<GATHER_COSINE>), dim3((npix + 255) / 256), dim3(256), 0, stream,
-                      wb.rad, out, *gl, frame0 + fb, Fb);
-        else if (ql)
-            PT_LAUNCH(KID_WF_ACCUM, stream, k_wf_accum_rays, dim3((npix + 255) / 256), dim3(256), 0, stream, wb.rad, out, *ql, Fb);
-        else if (rl)
-            PT_LAUNCH(KID_WF_ACCUM, stream, (k_wf_accum<RectList>), dim3((npix + 255) / 256), dim3(256), 0, stream, wb.rad, out,
-                      npix, fp.win_w, fp.row_pitch, Fb, accum, m2, *rl);
-        else
-            PT_LAUNCH(KID_WF_ACCUM, stream, (k_wf_accum<>), dim3((npix + 255) / 256), dim3(256), 0, stream, wb.rad, out, npix,
-                      fp.win_w, fp.row_pitch, Fb, accum, m2);
+        launch_accum(src, fp, wb.rad, npix, frame0 + fb, Fb, accum, out, stream);
     }
     return hipGetLastError();
 }
 
+// what a PathSource's making cannot rule out (pt_kernels.h)
+static bool source_ok(const PathSource& src, bool accum, uint32_t stride) {
+    if ((src.kind != PathSource::WINDOW || src.m2) && !accum) return false;
+    if (src.cam && (src.cam->model < CAM_THIN_LENS || src.cam->model > CAM_EQUIRECT)) return false;
+    switch (src.kind) {
+        case PathSource::WINDOW: return true;
+        case PathSource::RECTS: return src.rects.n != 0 && src.rects.npix != 0;
+        case PathSource::RAYS: return stride == 1 && src.rays.n != 0;
+        case PathSource::GATHER: return stride == 1 && src.gather.n != 0 && src.gather.mode <= GATHER_SH9;
+        case PathSource::VIEWS: return src.views.n != 0 && src.views.npix != 0;
+    }
+    return false;
+}
+
 hipError_t launch_wavefront(const LaunchOpts& lo, const SceneView& sc, const FrameParams& fp, const WfBuffers& wb,
-                            uint32_t frame0, uint32_t nframes, uint32_t stride, bool accum, bool count, float* out,
-                            Counters* cnt, hipStream_t stream, const WfStreams& ws, float* m2, const RectList* rl,
-                            const RayList* ql, const LensCam* cam, const GatherList* gl, const ViewList* vl) {
-    if ((m2 || rl || ql || gl || vl) && !accum) return hipErrorInvalidValue;
-    if (vl && (m2 || rl || ql || cam || gl || vl->n == 0 || vl->npix == 0)) return hipErrorInvalidValue;
-    if (gl && (m2 || rl || ql || cam || stride != 1 || gl->n == 0 || gl->mode > GATHER_SH9)) return hipErrorInvalidValue;
-    if (cam && (ql || cam->model < CAM_THIN_LENS || cam->model > CAM_EQUIRECT)) return hipErrorInvalidValue;
-    if (ql && (m2 || rl || stride != 1 || ql->n == 0)) return hipErrorInvalidValue;
+                            const PathSource& src, uint32_t frame0, uint32_t nframes, uint32_t stride, bool accum,
+                            bool count, float* out, Counters* cnt, hipStream_t stream, const WfStreams& ws) {
+    if (!source_ok(src, accum, stride)) return hipErrorInvalidValue;
     if (!accum) { nframes = 1; stride = 1; }
     const bool lds = lo.lds && scene_fits_lds(sc);
     // the leaf pass (FLV_PRE) when the scene's table of pre-resolved leaves holds its big leaves
     // (pt_capi.hip shape_view: option leaf_pre, default on) and the buffers exist
     const int trav = select_wavefront(lo, sc.fast_rcp != 0, sc.mailbox != 0, sc.big_leaf > 0, sc.npre > 0 && sc.pre && wb.pres);
     // sc.node_bias <= 0: chosen per instance in wf_render_t
-#define WF_ARGS sc, fp, wb, frame0, nframes, stride, accum, out, cnt, stream, ws, lo, m2, rl, ql, cam, gl, vl
+#define WF_ARGS sc, fp, wb, src, frame0, nframes, stride, accum, out, cnt, stream, ws, lo
 #define WF(T)                                                                                                        \
     case T:                                                                                                          \
         return lds ? (count ? wf_render_t<true, T, true>(WF_ARGS) : wf_render_t<true, T, false>(WF_ARGS))            \
