@@ -1,5 +1,5 @@
 // pt_capi_gather.hip — C ABI (include/pt_hip.h): irradiance gathers — lightmap texels and SH probes
-// sampled on the device (pt_wavefront.hip k_wf_generate_gather / k_wf_accum_gather / k_gather_rays;
+// sampled on the device (pt_wf_source.hip k_wf_generate_gather / k_wf_accum_gather / k_gather_rays;
 // DESIGN.md §5.13).  Host code only.
 #include "pt_capi_internal.h"
 

@@ -1,5 +1,5 @@
 // pt_capi_radiance.hip — C ABI (include/pt_hip.h): radiance queries for caller-supplied rays and the
-// camera's seeds (pt_wavefront.hip k_wf_generate_rays / k_wf_accum_rays, pt_query.hip k_camera_seeds;
+// camera's seeds (pt_wf_source.hip k_wf_generate_rays / k_wf_accum_rays, pt_query.hip k_camera_seeds;
 // DESIGN.md §5.11).  Host code only.
 #include <cmath>
 

@@ -110,12 +110,7 @@ LaunchOpts launch_opts(const Opts& o, int mode, uint64_t paths, const SceneView&
     return lo;
 }
 
-// paths in flight per wavefront batch (kWfBytesPerPath = 188 B of queue state per path: 64 M
-// paths ~ 12 GB of the 288 GB, plus the queue slack of the region layout).  Every batch ends in
-// launch tails that carry few paths at low occupancy (the last depths); a larger batch pays them
-// for more samples: CornellBox 1024^2 x 256 +6 % at 64 M over 8 M, CornellBox-Glossy +28 %
-// (probe of option wf_paths)
-constexpr uint64_t kWfTargetPaths = 64ull << 20;
+// kWfTargetPaths, the paths in flight per wavefront batch: pt_wf_plan.h
 constexpr int kBigLeafDefault = 128;
 constexpr long kPreRatioDefault = 50;  // shape_view: the leaf pass when >= 50 % of its work is visited
 
@@ -140,9 +135,7 @@ static int ensure_wavefront(pt_scene* s, uint64_t paths) {
     if (paths > 0x7fffffffull) return fail(PT_ERR_INVALID, "image too large for one wavefront batch");
     s->wf.capacity = 0;  // until the buffers below stand
     const size_t n = paths;
-    // queue arrays carry slack so that each part can be cut into up to kRegions regions of a whole
-    // number of 64-entry batches holding all its paths (k_wf_step_bf)
-    const size_t qn = n + 2 * (size_t)kQueueSlackRegions * 64;
+    const size_t qn = wf_queue_entries(n);  // with the region layout's slack (pt_wf_plan.h)
     size_t off = 0;
     auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
     size_t oq[6];
@@ -377,25 +370,14 @@ static int upload_rects(pt_scene* s, const RectPlan& plan, const FrameParams& fp
 // The wavefront's buffers for a call of nframes frames of npix paths each (a single-frame call: 1): the
 // queues and the radiance of one batch, and the keys of the view's pre-resolved leaves
 int prepare_wavefront(pt_scene* s, const Opts& o, const SceneView& view, uint64_t npix, uint32_t nframes) {
-    // the target in whole pairs of frames (a batch's two parts take whole frames each): 4096^2
-    // holds 4 frames (67 M paths), not 2 of the 3.8 that 64 M would hold
-    const uint64_t target0 = (uint64_t)std::max(1L, o.num("wf_paths", (long)kWfTargetPaths));  // A/B
-    const uint64_t pairs = (target0 + 2 * npix - 1) / (2 * npix) * (2 * npix);
-    const uint64_t target = o.has("wf_paths") || pairs > 0x7fffffffull ? target0 : pairs;
-    // at least two frames per batch when the call has two (images above the target, e.g.
-    // 4096^2): the batch's parts run on their own streams and overlap (+29 % at 4096^2)
-    const uint64_t all = npix * nframes;
-    const uint64_t two = 2 * npix <= 0x7fffffffull ? 2 * npix : npix;
-    // a call that fits the target runs as one batch: its two parts take whole frames each, so
-    // an odd frame count gets one frame of room more (5 frames: 3 + 2, not batches of 4 and 1)
-    const uint64_t all_even = nframes > 1 && (nframes & 1) ? all + npix : all;
-    const uint64_t want = std::max<uint64_t>(std::min<uint64_t>(all, two), std::min<uint64_t>(all_even, target));
-    int rc2 = ensure_wavefront(s, want);
+    // the batch: option wf_paths or the default target in whole pairs of frames, at least two frames,
+    // one frame of room more for an odd count (wf_batch_size, pt_wf_plan.h)
+    const WfBatchSize bs = wf_batch_size(npix, nframes, o.num("wf_paths", (long)kWfTargetPaths), o.has("wf_paths"));
+    int rc2 = ensure_wavefront(s, bs.want);
     // the batch's state (~188 B/path: 12 GB at the 64 M-path target) may not fit beside other
     // allocations: halve it down to one frame per batch before giving up
-    const uint64_t floor_paths = std::min<uint64_t>(all, npix);
-    for (uint64_t w = want; rc2 == PT_ERR_NOMEM && w > floor_paths;)
-        rc2 = ensure_wavefront(s, w = std::max<uint64_t>(w / 2, floor_paths));
+    for (uint64_t w = bs.want; rc2 == PT_ERR_NOMEM && w > bs.floor;)
+        rc2 = ensure_wavefront(s, w = std::max<uint64_t>(w / 2, bs.floor));
     if (rc2 != PT_OK) return rc2;
     rc2 = ensure_rad(s, s->wf.capacity);
     if (rc2 != PT_OK) return rc2;

@@ -29,6 +29,12 @@ struct Ray {
     f3 o, d, inv;
 };
 
+// number of set bits of m below this lane (the rank of a lane in a ballot: the wavefront's, the leaf
+// pass's and the queries' compactions)
+__device__ __forceinline__ uint32_t rank_below(uint64_t m) {
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+}
+
 // Diagnostic build only (make EXTRA=-DPT_TRACE_STATS=1 OUT_DIR=...; scripts/trace_stats.py): the lean
 // traversal's turns, timed with s_memtime and counted with their participating lanes, per kind
 // (TS_*), summed per wave in Counters::ts and flushed into g_trace_stats by k_wf_trace.

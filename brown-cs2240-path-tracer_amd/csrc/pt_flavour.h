@@ -79,13 +79,13 @@ constexpr bool mega_instantiated(int t) { return false PT_MEGA_FLAVOURS(PT_FLV_I
 constexpr bool wf_instantiated(int t) { return false PT_WF_FLAVOURS(PT_FLV_IS); }
 #undef PT_FLV_IS
 
-// hit slots per lane of the brute-force kernels (pt_wavefront.hip: a ray with more hits recomputes the rest)
+// hit slots per lane of the brute-force kernels (pt_wf_bf.hip: a ray with more hits recomputes the rest)
 constexpr int kBfSlots = 8;
 
 // Kernel selection, with every default resolved (pt_capi.hip launch_opts fills it from the option
 // table; pt_set_option overrides are for tests and A/B runs).
 struct LaunchOpts {
-    bool wavefront = false;  // wavefront pipeline (pt_wavefront.hip)
+    bool wavefront = false;  // wavefront pipeline (pt_wavefront.hip: the driver; the kernels in pt_wf_*.hip)
     bool literal = false;    // k_mega: the reference's control flow
     bool lds = true;         // stage the scene in LDS when it fits
     // traversal base flavour.  Wavefront: lean16 (measured best on gfx950, scripts/perf_variants.py);

@@ -10,6 +10,7 @@
 #include "pt_query_plan.h"
 #include "pt_rect_plan.h"
 #include "pt_step_addr.h"
+#include "pt_wf_plan.h"
 
 // ids for k_selftest_math (also used by pt_selftest_math in the C-ABI)
 enum {
@@ -64,7 +65,8 @@ constexpr size_t kLdsSceneBudget = 64 * 1024;
 // LaunchOpts (the per-call options, with their defaults): pt_flavour.h
 bool scene_fits_lds(const SceneView& sc);
 
-// Wavefront path state (HBM), `capacity` entries per queue; see pt_wavefront.hip.  Every
+// Wavefront path state (HBM), `capacity` entries per queue; see pt_wavefront.hip
+// (the pipeline) and pt_wf_queue.h (the entries' words).  Every
 // path's state travels with its ray: queue entry i holds the ray AND the path state, and
 // a shade kernel writes the surviving path to its compacted slot of the other queue, so no
 // kernel gathers by path index.  Iterations alternate extension / shadow queues.
@@ -110,16 +112,12 @@ struct WfBuffers {
     // per distinct entry, the camera-origin parts of the triangle test (k_wf_camtab; 2 x 64 float4)
     float4* camtab;
 };
-constexpr uint32_t kRegions = 512;
-// queue slack (entries per part = 64 * this): regions of R <= kRegions hold ceil(batches / R)
-// 64-entry batches each
-constexpr uint32_t kQueueSlackRegions = 4096;
+// kRegions, kQueueSlackRegions and kMaxParts: pt_wf_plan.h
 constexpr size_t kWfBytesPerPath = 64 + 64 + 40 + 8 + 12;
 
 // The wavefront's parts: streams owned by the scene, created back to back so that HIP's
 // round-robin stream -> hardware-queue mapping puts them on different queues (a shared queue
 // serialises the parts), plus fork/join events with the caller's stream.  Null = one stream.
-constexpr int kMaxParts = 4;  // parts of a wavefront batch on their own streams (LaunchOpts::parts)
 struct WfStreams {
     hipStream_t aux[kMaxParts] = {};
     hipEvent_t fork = nullptr, join[kMaxParts] = {};

@@ -37,7 +37,7 @@ static_assert(sizeof(Node) == 64, "node is 4 x 16 B");
 // numbered in the reference's visiting order (pre-order, right subtree first), each child's
 // payload in one 64-bit word — a leaf child's uid set (bit 63 clear; 0 for an empty leaf) or, for
 // an internal child, bit 63 | its pre-order number.  The brute-force replay walks this tree with a
-// 64-bit set of pending nodes instead of a stack (pt_wavefront.hip bf_closest).
+// 64-bit set of pending nodes instead of a stack (pt_wf_bf.hip bf_closest).
 struct alignas(16) BfNode {
     float lmin[3];
     float lmax[3];
@@ -51,7 +51,7 @@ static_assert(sizeof(BfNode) == 64, "bf node is 4 x 16 B");
 //   low   the set of uids beneath that child: a leaf's own set, an internal child's union over its
 //         whole subtree (what the replay's pruning asks: does this child hold a hit not yet resolved?)
 //   high  0x80000000 | pre-order number for an internal child, else 0
-// read by the 32-bit instance of the replay (pt_wavefront.hip bf_replay_stackless<.., true>).
+// read by the 32-bit instance of the replay (pt_wf_bf.hip bf_replay_stackless<.., true>).
 constexpr uint32_t kBfNarrowInner = 0x80000000u;
 constexpr int kBfNarrowMax = 32;  // entries, and internal nodes
 

@@ -17,19 +17,13 @@
 // lanes, no divergence, no per-lane memory traffic in the loop.  The rays that pass a leaf's
 // filter are gathered per wave and leaf in an LDS ring until 64 are waiting.
 #include "pt_kernels.h"
-
-#include <map>
-#include <mutex>
+#include "pt_occupancy.h"
 
 namespace pt {
 namespace {
 
 constexpr uint32_t kLeafPassBlock = 256;  // 4 waves
 constexpr uint32_t kLeafRing = 128;       // per wave and leaf: entries passed the filter, not resolved yet
-
-__device__ __forceinline__ uint32_t lp_rank_below(uint64_t m) {
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-}
 
 // uniform loads through the scalar cache (constant address space: s_load, no VGPRs)
 typedef const __attribute__((address_space(4))) float* cfloat_p;
@@ -277,7 +271,7 @@ __device__ __forceinline__ uint64_t resolve_leaf_pairs(const SceneView& sc, int 
         const float qbound = qk != ~0ull ? __builtin_bit_cast(float, (uint32_t)(qk >> 32)) : __builtin_inff();
         const bool keep = has && !pass_box_skip(na, nb, ne, nc.w, q, qbound, fmaf(cmin, qidl, -1e-5f));
         const uint64_t m = __builtin_amdgcn_ballot_w64(keep);
-        if (keep) qb[(hb + lp_rank_below(m)) & (kLeafRing - 1)] = item;
+        if (keep) qb[(hb + rank_below(m)) & (kLeafRing - 1)] = item;
         hb += (uint32_t)__popcll(m);
         ta += avail;
         if (hb - tb >= 64) pass(64);  // uniform (never more than 127 queued)
@@ -295,11 +289,11 @@ __device__ __forceinline__ uint64_t resolve_leaf_pairs(const SceneView& sc, int 
         if (!m) continue;  // uniform
         const uint32_t item = ((uint32_t)c << 6) | lane;
         if (refine) {  // uniform
-            if (open) qa[(ha + lp_rank_below(m)) & (kLeafRing - 1)] = item;
+            if (open) qa[(ha + rank_below(m)) & (kLeafRing - 1)] = item;
             ha += (uint32_t)__popcll(m);
             if (ha - ta >= 64) check(64);  // uniform (never more than 127 queued: kLeafRing)
         } else {
-            if (open) qb[(hb + lp_rank_below(m)) & (kLeafRing - 1)] = item;
+            if (open) qb[(hb + rank_below(m)) & (kLeafRing - 1)] = item;
             hb += (uint32_t)__popcll(m);
             if (hb - tb >= 64) pass(64);
         }
@@ -391,7 +385,7 @@ __global__ __launch_bounds__(kLeafPassBlock) void k_wf_leafpass(SceneView sc, Wf
             if (!m) continue;
             const uint32_t head = __builtin_amdgcn_readfirstlane(pos[wv][b][0]);
             const uint32_t tail = __builtin_amdgcn_readfirstlane(pos[wv][b][1]);
-            if (pass) ring[wv][b][(head + lp_rank_below(m)) & (kLeafRing - 1)] = i;
+            if (pass) ring[wv][b][(head + rank_below(m)) & (kLeafRing - 1)] = i;
             const uint32_t nh = head + (uint32_t)__popcll(m);
             uint32_t nt = tail;
             if (nh - tail >= 64) {  // uniform: 64 waiting (never more than 127: kLeafRing holds them)
@@ -457,21 +451,6 @@ __global__ __launch_bounds__(kLeafPassBlock) void k_selftest_leafpass(SceneView 
     o[5] = 0;
 }
 
-int leafpass_blocks(const void* kernel) {
-    static std::mutex mu;
-    static std::map<const void*, int> cache;
-    std::lock_guard<std::mutex> lk(mu);
-    auto it = cache.find(kernel);
-    if (it != cache.end()) return it->second;
-    int per_cu = 0, dev = 0, cus = 0;
-    hipGetDevice(&dev);
-    hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kLeafPassBlock, 0);
-    const int b = std::max(1, per_cu) * std::max(1, cus);
-    cache.emplace(kernel, b);
-    return b;
-}
-
 }  // namespace
 
 hipError_t launch_selftest_leafpass(const SceneView& sc, int b, int mode, uint32_t seed, uint32_t nrays, int32_t* out,
@@ -489,7 +468,7 @@ hipError_t launch_leafpass(const SceneView& sc, const WfBuffers& wb, int in_q, b
                            hipStream_t stream) {
     if (sc.npre <= 0 || !sc.pre || !wb.pres) return hipErrorInvalidValue;
     const void* k = fast_rcp ? (const void*)k_wf_leafpass<true> : (const void*)k_wf_leafpass<false>;
-    const int nb = blocks > 0 ? blocks : leafpass_blocks(k);
+    const int nb = blocks > 0 ? blocks : occupancy_blocks(k, kLeafPassBlock, 0);
     if (fast_rcp)
         PT_LAUNCH(KID_WF_LEAF, stream, k_wf_leafpass<true>, dim3(nb), dim3(kLeafPassBlock), 0, stream, sc, wb, in_q, pairs);
     else

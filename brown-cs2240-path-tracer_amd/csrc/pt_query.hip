@@ -13,11 +13,8 @@
 //       wave's slowest ray is traced (refill = 0 keeps them idle until all 64 are done: the A/B).
 //   k_camera_rays   one lane per pixel of the window: the ray camera_ray gives that pixel and salt.
 //   k_camera_seeds  one lane per pixel of the window: the seed camera_ray hands to radiance() there.
-#include <map>
-#include <mutex>
-#include <utility>
-
 #include "pt_kernels.h"
+#include "pt_occupancy.h"
 #include "pt_path.h"
 #include "pt_query_plan.h"
 
@@ -25,15 +22,11 @@ namespace pt {
 
 namespace {
 
-__device__ __forceinline__ uint32_t q_rank_below(uint64_t m) {
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-}
-
 // Per wave in LDS: the current window's rays, kQueryWin x 32 B.  The results are NOT staged: a lane
 // stores its own result when its ray ends, from inside the loop (on gfx9 a store shares the wave's
 // in-order vmcnt with the loads, so the next use of a loaded register also waits for it; k_wf_trace
 // stages its hit records in an LDS ring for that reason, see the comment above kWinRays in
-// pt_wavefront.hip).  Here a store happens once per ray, not per step, and the ring would cost the
+// pt_wf_trace.hip).  Here a store happens once per ray, not per step, and the ring would cost the
 // occupancy the stacks leave; DESIGN.md §5.10 keeps staging as a lead.
 constexpr uint32_t kQueryStageBytes = kQueryWin * 32;
 
@@ -108,7 +101,7 @@ __global__ __launch_bounds__(kMegaBlock) void k_query(SceneView sc, const float4
                 if (q.wnx != kQueryNone) load(q.wnx, q.nv, na, nb);
             }
             wave_lds_sync();  // the window's rays were written by other lanes
-            const uint32_t k = has ? kQueryNone : query_position(q, q_rank_below(need));
+            const uint32_t k = has ? kQueryNone : query_position(q, rank_below(need));
             if (k != kQueryNone) {
                 const float4 a = wray[2 * k], b = wray[2 * k + 1];
                 r.o = mk(a.x, a.y, a.z);
@@ -155,25 +148,6 @@ __global__ __launch_bounds__(kMegaBlock) void k_query(SceneView sc, const float4
     if (COUNT) flush_counters(c, cnt_out);
 }
 
-// resident blocks of `kernel` per CU at `lds` bytes of dynamic LDS, times the CUs (cached per kernel
-// instance and LDS size, as pt_wavefront.hip's: a pick of one ray should not pay three runtime calls)
-static hipError_t query_occupancy_blocks(const void* kernel, size_t lds, int& blocks) {
-    static std::mutex mu;
-    static std::map<std::pair<const void*, size_t>, int> cache;
-    std::lock_guard<std::mutex> lk(mu);
-    const auto key = std::make_pair(kernel, lds);
-    const auto it = cache.find(key);
-    if (it != cache.end()) { blocks = it->second; return hipSuccess; }
-    int per_cu = 0, dev = 0, cus = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kMegaBlock, lds);
-    if (e != hipSuccess) return e;
-    blocks = std::max(1, per_cu) * std::max(1, cus);
-    cache.emplace(key, blocks);
-    return hipSuccess;
-}
-
 // The batch goes out in launches of at most kQueryLaunchRays rays, in order on the stream: a wave lives
 // as long as its launch and its wall-clock guard counts from its start, so the guard must bound a
 // launch's work, not the caller's batch (as wf_paths bounds a k_wf_trace launch).  Every ray's result
@@ -187,7 +161,7 @@ static hipError_t launch_query_t(const SceneView& sc, const float4* rays, uint32
                                      : reinterpret_cast<const void*>(&k_query<TRAV, OCCL, false>);
     int full = blocks;
     if (full <= 0) {  // auto: what the device holds at once
-        const hipError_t e = query_occupancy_blocks(kernel, lds, full);
+        const hipError_t e = occupancy_blocks(kernel, kMegaBlock, lds, full);  // a pick of one ray pays no runtime call: cached
         if (e != hipSuccess) return e;
     }
     const int kid = OCCL ? KID_QUERY_OCCLUDED : KID_QUERY_HITS;

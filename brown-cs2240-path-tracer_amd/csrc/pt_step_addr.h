@@ -1,4 +1,4 @@
-// pt_step_addr.h — when the fused step kernel (k_wf_step_bf, pt_wavefront.hip) may address a part's
+// pt_step_addr.h — when the fused step kernel (k_wf_step_bf, pt_wf_bf.hip) may address a part's
 // queues with 32-bit byte offsets.  A rule for the host, in standard C++ (constexpr only, so it also
 // compiles into the device units that include pt_kernels.h; scripts/step_addr_harness.cpp checks the
 // boundary on the CPU).

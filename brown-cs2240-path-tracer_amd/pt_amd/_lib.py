@@ -12,12 +12,13 @@ _LIB_FILE = os.path.join(_PKG_ROOT, "lib", "libpt_hip.so")
 ABI_VERSION = 3  # include/pt_hip.h PT_ABI_VERSION
 _CSRC = os.path.join(_PKG_ROOT, "csrc")
 # csrc/Makefile BUILD_SRCS: the sources whose SHA-256 the library carries as pt_build_id()
-_BUILD_SRCS = ["pt_kernels.hip", "pt_wavefront.hip", "pt_leafpass.hip", "pt_image.hip", "pt_features.hip", "pt_denoise.hip", "pt_query.hip", "pt_capi.hip", "pt_capi_render.hip",
+_BUILD_SRCS = ["pt_kernels.hip", "pt_wavefront.hip", "pt_wf_source.hip", "pt_wf_trace.hip", "pt_wf_bf.hip", "pt_wf_shade.hip", "pt_leafpass.hip", "pt_image.hip", "pt_features.hip", "pt_denoise.hip", "pt_query.hip", "pt_capi.hip", "pt_capi_render.hip",
                "pt_capi_adaptive.hip", "pt_capi_denoise.hip", "pt_capi_query.hip", "pt_capi_radiance.hip", "pt_capi_gather.hip", "pt_capi_selftest.hip",
                "pt_capi_multi.hip", "pt_capi_camera.hip", "pt_capi_views.hip", "pt_capi_internal.h", "pt_math.h", "pt_flavour.h", "pt_layout.h",
                "pt_device.h", "pt_path.h", "pt_kernels.h", "../../include/pt_hip.h", "pt_bvh.cpp", "pt_leafbvh.h",
                "pt_leafbvh.cpp", "pt_leafskip.cpp", "pt_scene_layout.h", "pt_scene_layout.cpp", "pt_rect_plan.h",
-               "pt_rect_plan.cpp", "pt_view_plan.h", "pt_view_plan.cpp", "pt_query_plan.h", "pt_step_addr.h", "Makefile"]
+               "pt_rect_plan.cpp", "pt_view_plan.h", "pt_view_plan.cpp", "pt_query_plan.h", "pt_step_addr.h", "pt_wf_plan.h",
+               "pt_wf_queue.h", "pt_wf_stage.h", "pt_occupancy.h", "Makefile"]
 MODE_AUTO, MODE_MEGAKERNEL, MODE_WAVEFRONT = 0, 1, 2
 MATH_FNS = ["sin", "cos", "tan", "acos", "log2", "exp2", "pow", "sqrt", "div", "hash1u", "hash1", "hash2x",
             "hash2y", "min", "max", "ray_inv"]

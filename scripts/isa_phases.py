@@ -4,7 +4,7 @@ of DESIGN.md §5.3, with scripts/phase_stats.py's iteration counts).  The diagno
 marks (PT_PHASE_STATS) delimit the phases; backward branches delimit the loops.
 Make the assembly first:
   hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-slp-vectorize \\
-        -DPT_PHASE_STATS=1 --cuda-device-only -S -o diag.s brown-cs2240-path-tracer_amd/csrc/pt_wavefront.hip
+        -DPT_PHASE_STATS=1 --cuda-device-only -S -o diag.s brown-cs2240-path-tracer_amd/csrc/pt_wf_bf.hip
 usage: isa_phases.py diag.s [EXT=1|0]"""
 import re
 import sys

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Per-phase statistics of the fused kernel k_wf_step_bf (verdict r05 item 2): a diagnostic build
 (make -C brown-cs2240-path-tracer_amd/csrc EXTRA=-DPT_PHASE_STATS=1 OUT_DIR=<dir>) times each wave's
-phases with s_memtime and counts, per phase, loop iterations and active lanes (pt_wavefront.hip
+phases with s_memtime and counts, per phase, loop iterations and active lanes (pt_wf_queue.h
 PhaseAcc).  This script renders the bench workload through that library (same sources, so the same
 build id) and prints per instance (extension / shadow) and phase: the share of the waves' wall
 cycles, iterations per 64-path batch and the lane use (active lanes / 64 per iteration).

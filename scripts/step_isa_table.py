@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Static table of the fused step kernel's instances in a hipcc -S listing of pt_wavefront.hip (with
+"""Static table of the fused step kernel's instances in a hipcc -S listing of pt_wf_bf.hip (with
 -Rpass-analysis=kernel-resource-usage remarks in a second file): per k_wf_step_bf instance the VALU
 count, lane moves (v_readlane / v_writelane), 64-bit address VALU, 32-bit literal moves, division
 pieces, registers, scratch and occupancy; then, for the instances named by --loop (default: the two

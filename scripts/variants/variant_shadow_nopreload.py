@@ -10,7 +10,7 @@ dst = sys.argv[1]
 if os.path.exists(dst):
     shutil.rmtree(dst)
 shutil.copytree(os.path.join(ROOT, "brown-cs2240-path-tracer_amd", "csrc"), dst)
-p = os.path.join(dst, "pt_wavefront.hip")
+p = os.path.join(dst, "pt_wf_bf.hip")
 s = open(p).read()
 old = """        else { a1 = in.ray[2 * e + 1]; c2 = in.q2[e]; }
     }"""

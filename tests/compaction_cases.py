@@ -1,5 +1,5 @@
 """Inputs and references of the generate kernels' compaction under rejection (compact_slot in
-csrc/pt_wavefront.hip), shared by test_compaction_cpu.py and test_gpu_compaction.py.
+csrc/pt_wf_source.hip), shared by test_compaction_cpu.py and test_gpu_compaction.py.
 
 A path's result does not depend on its queue slot, so the reference of every case is the oracle's radiance()
 per path (radiance_ref.py, gather_ref.py, lens_ref.py, views_ref.py), bit for bit.  What this module adds:

@@ -1,6 +1,6 @@
-"""CPU model of the region-partitioned queues of the fused kernel (pt_wavefront.hip: k_wf_generate's
-region layout and closed-form counts, k_wf_step_bf's regions; the host's rstride
-and queue slack in pt_capi_render.hip / pt_kernels.h), step for step.
+"""CPU model of the region-partitioned queues of the fused kernel (k_wf_generate's region
+layout and closed-form counts in pt_wf_source.hip, k_wf_step_bf's regions in pt_wf_bf.hip; the host's
+rstride and queue slack in pt_wf_plan.h, pinned on the real code by test_wf_plan_cpu.py), step for step.
 
 64-path batch j of P paths goes to region j % R at offset (j // R) * 64 + p % 64 of that region;
 region r holds rstride = qcap // R // 64 * 64 entries, qcap = the queue entries of the half (the

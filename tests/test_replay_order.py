@@ -1,4 +1,4 @@
-"""The brute-force replay's stackless walk (pt_wavefront.hip bf_replay_stackless) visits the same
+"""The brute-force replay's stackless walk (pt_wf_bf.hip bf_replay_stackless) visits the same
 nodes in the same order as the reference's stack walk (program-raymarch.wgsl traversal, restated
 by lean_decide: right child first, the left one stacked when both are taken), for any
 decisions — the claim its comment makes.  Internal nodes are numbered in pre-order, right

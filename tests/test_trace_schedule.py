@@ -1,4 +1,4 @@
-"""CPU model of k_wf_trace's work split and write-back (pt_wavefront.hip), step for step.
+"""CPU model of k_wf_trace's work split and write-back (pt_wf_trace.hip), step for step.
 
 Wave w of N takes the queue windows w, w+N, ...; idle lanes take entries of the window in LDS
 (ballot rank order); a window is written back from the hit ring once all its entries were handed
