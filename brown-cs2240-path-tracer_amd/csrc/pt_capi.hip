@@ -354,6 +354,7 @@ void pt_scene_destroy(pt_scene* s) {
     if (!s) return;
     hipSetDevice(s->device);
     if (s->stream) { hipStreamSynchronize(s->stream); hipStreamDestroy(s->stream); }
+    orphan_histories(s);
     for (int h = 0; h < kMaxParts; ++h) {
         if (s->ws.aux[h]) { hipStreamSynchronize(s->ws.aux[h]); hipStreamDestroy(s->ws.aux[h]); }
         if (s->ws.join[h]) hipEventDestroy(s->ws.join[h]);

@@ -22,15 +22,17 @@ static int check_denoise(const pt_denoise_params& p, uint32_t feature_frames) {
     return PT_OK;
 }
 
+namespace pt {
+
 // the call's parameters: the defaults, the caller's over them (p nullable), checked
-static int denoise_params(const pt_denoise_params* p, uint32_t feature_frames, pt_denoise_params& out) {
+int denoise_params(const pt_denoise_params* p, uint32_t feature_frames, pt_denoise_params& out) {
     pt_denoise_defaults(&out);
     if (p) out = *p;
     return check_denoise(out, feature_frames);
 }
 
-static int features_impl(pt_scene* s, const float* meta, const pt_window* win, const size_t* pitch, uint32_t frame0,
-                         uint32_t nframes, uint32_t stride, float* d_geo, float* d_alb, Counters* d_cnt, hipStream_t stream) {
+int features_impl(pt_scene* s, const float* meta, const pt_window* win, const size_t* pitch, uint32_t frame0,
+                  uint32_t nframes, uint32_t stride, float* d_geo, float* d_alb, Counters* d_cnt, hipStream_t stream) {
     FrameParams fp{};
     int rc = make_params(meta, 0, fp, win, pitch);
     if (rc != PT_OK) return rc;
@@ -48,6 +50,36 @@ static int features_impl(pt_scene* s, const float* meta, const pt_window* win, c
                             scene_camera(s, lens)));
     return PT_OK;
 }
+
+// the scene's four planes for a w x h image: two ping-pong (c, var), (N, Z), (A, 0)
+int denoise_planes(pt_scene* s, size_t npix, float4* cv[2], float4*& nz, float4*& ab) {
+    PT_TRY(s->d_dn.ensure(4 * npix, "denoiser planes"));  // (counted in info.device_bytes)
+    cv[0] = s->d_dn.p; cv[1] = s->d_dn.p + npix;
+    nz = s->d_dn.p + 2 * npix;
+    ab = s->d_dn.p + 3 * npix;
+    return PT_OK;
+}
+
+// the passes over the prepared planes (cv[0] holds the first pass's input)
+int denoise_passes(const pt_denoise_params& prm, uint32_t w, uint32_t h, uint32_t row_pitch, float4* const cv[2],
+                   const float4* nz, const float4* ab, float* d_out, float* d_var_out, hipStream_t st) {
+    // host constants: double, rounded once
+    const float isn = (float)(1.0 / ((double)prm.sigma_n * (double)prm.sigma_n));
+    const float isa = (float)(1.0 / ((double)prm.sigma_a * (double)prm.sigma_a));
+    const float isz = (float)(1.0 / (double)prm.sigma_z);
+    // option denoise_lds = v: the first v passes (steps 1 .. 2^(v-1)) read their taps through LDS
+    const uint32_t staged = (uint32_t)opts_snapshot().num("denoise_lds", kDenoiseLdsDefault);
+    for (uint32_t i = 0; i < prm.iters; ++i) {
+        const uint32_t step = 1u << i;
+        const bool last = i + 1 == prm.iters;
+        HIP_TRY(launch_atrous(cv[i & 1], nz, ab, w, h, step, isn, isa, isz, prm.sigma_l, i < staged && atrous_can_stage(step),
+                              last ? nullptr : cv[(i & 1) ^ 1], last ? d_out : nullptr, last ? d_var_out : nullptr,
+                              row_pitch, st));
+    }
+    return PT_OK;
+}
+
+}  // namespace pt
 
 extern "C" {
 
@@ -94,27 +126,12 @@ int pt_denoise_async(pt_scene* s, const float* d_accum, const float* d_m2, uint3
     if (((uintptr_t)d_geo | (uintptr_t)d_alb) & 15u) return fail(PT_ERR_INVALID, "geo and alb must be 16-byte aligned");
     const size_t npix = (size_t)w * h;
     HIP_TRY(hipSetDevice(s->device));
-    PT_TRY(s->d_dn.ensure(4 * npix, "denoiser planes"));  // (counted in info.device_bytes)
-    float4* const cv[2] = {s->d_dn.p, s->d_dn.p + npix};
-    float4* const nz = s->d_dn.p + 2 * npix;
-    float4* const ab = s->d_dn.p + 3 * npix;
-    // host constants: double, rounded once
-    const float isn = (float)(1.0 / ((double)prm.sigma_n * (double)prm.sigma_n));
-    const float isa = (float)(1.0 / ((double)prm.sigma_a * (double)prm.sigma_a));
-    const float isz = (float)(1.0 / (double)prm.sigma_z);
-    // option denoise_lds = v: the first v passes (steps 1 .. 2^(v-1)) read their taps through LDS
-    const uint32_t staged = (uint32_t)opts_snapshot().num("denoise_lds", kDenoiseLdsDefault);
+    float4 *cv[2], *nz, *ab;
+    PT_TRY(denoise_planes(s, npix, cv, nz, ab));
     ProfScope prof_scope(s);
     hipStream_t st = static_cast<hipStream_t>(stream);
     HIP_TRY(launch_denoise_prepare(d_accum, d_m2, d_geo, d_alb, g, d_frames, feature_frames, cv[0], nz, ab, st));
-    for (uint32_t i = 0; i < prm.iters; ++i) {
-        const uint32_t step = 1u << i;
-        const bool last = i + 1 == prm.iters;
-        HIP_TRY(launch_atrous(cv[i & 1], nz, ab, w, h, step, isn, isa, isz, prm.sigma_l, i < staged && atrous_can_stage(step),
-                              last ? nullptr : cv[(i & 1) ^ 1], last ? d_out : nullptr, last ? d_var_out : nullptr,
-                              g.row_pitch, st));
-    }
-    return PT_OK;
+    return denoise_passes(prm, w, h, g.row_pitch, cv, nz, ab, d_out, d_var_out, st);
 }
 
 int pt_denoise(pt_scene* s, const float* accum, const float* m2, uint32_t w, uint32_t h, uint32_t tile_w, uint32_t tile_h,

@@ -105,6 +105,8 @@ struct PinnedWords {
 
 }  // namespace pt
 
+struct pt_history;
+
 // Members free themselves (~pt_scene, with the device set by pt_scene_destroy, which also destroys the
 // streams, the events and the profiler).
 struct pt_scene {
@@ -168,6 +170,11 @@ struct pt_scene {
     const pt::PreLeaf* d_pre = nullptr;
     pt::Scratch<uint64_t> d_pres;
     pt_camera cam{};  // pt_scene_set_camera, as given after validation (model 0: the pinhole)
+    // pt_reproject's scratch (the blocking call's inputs, both sets of planes and outputs; counted in
+    // info.device_bytes while held), and the scene's live histories (pt_history_create): pt_scene_destroy
+    // frees their buffers and orphans them, so a later call on one is an error, not a fault
+    pt::Scratch<float> d_temporal{&info.device_bytes};
+    std::vector<pt_history*> histories;
 };
 
 namespace pt {
@@ -220,6 +227,19 @@ int query_call(pt_scene* s, const PathSource& src, size_t n, uint32_t sample0, u
 int render_impl(pt_scene* s, const float* meta, uint32_t frame0, uint32_t nframes, uint32_t stride, int max_depth,
                 int mode, bool accum, float* d_out, Counters* d_cnt, hipStream_t stream, const pt_window* win = nullptr,
                 const size_t* pitch = nullptr, float* d_m2 = nullptr, const pt_window* rects = nullptr, size_t nrects = 0);
+// pt_capi_denoise.hip
+// the denoiser's parameters: the defaults, the caller's over them (p nullable), checked
+int denoise_params(const pt_denoise_params* p, uint32_t feature_frames, pt_denoise_params& out);
+// pt_render_features_async's body (pitch NULL: dense)
+int features_impl(pt_scene* s, const float* meta, const pt_window* win, const size_t* pitch, uint32_t frame0,
+                  uint32_t nframes, uint32_t stride, float* d_geo, float* d_alb, Counters* d_cnt, hipStream_t stream);
+// the scene's four denoiser planes for npix pixels, and the a-trous passes over them once prepared
+int denoise_planes(pt_scene* s, size_t npix, float4* cv[2], float4*& nz, float4*& ab);
+int denoise_passes(const pt_denoise_params& prm, uint32_t w, uint32_t h, uint32_t row_pitch, float4* const cv[2],
+                   const float4* nz, const float4* ab, float* d_out, float* d_var_out, hipStream_t stream);
+// pt_capi_temporal.hip
+// pt_scene_destroy: the scene's histories lose their buffers and their scene
+void orphan_histories(pt_scene* s);
 // pt_capi_camera.hip
 // the scene's camera as a call's launches take it, read once per call: lc filled and returned for a lens
 // model, nullptr for the pinhole (the call then launches the pinhole's own kernels)

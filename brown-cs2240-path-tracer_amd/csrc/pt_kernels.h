@@ -25,7 +25,8 @@ namespace pt {
 enum KernelId : int {
     KID_MEGA = 0, KID_REGEN, KID_WF_GENERATE, KID_WF_TRACE, KID_WF_SHADE_EXT, KID_WF_SHADE_SHADOW, KID_WF_ACCUM,
     KID_TONEMAP, KID_WF_STEP, KID_WF_LEAF, KID_NOISE_TILES, KID_TILE_MEAN, KID_FEATURES, KID_DENOISE_PREPARE, KID_ATROUS,
-    KID_QUERY_HITS, KID_QUERY_OCCLUDED, KID_CAMERA_RAYS, KID_CAMERA_SEEDS, KID_GATHER_RAYS,
+    KID_QUERY_HITS, KID_QUERY_OCCLUDED, KID_CAMERA_RAYS, KID_CAMERA_SEEDS, KID_GATHER_RAYS, KID_REPROJECT,
+    KID_DENOISE_PREPARE_MEAN,
     KID_COUNT
 };
 inline const char* kernel_name(int k) {
@@ -33,7 +34,8 @@ inline const char* kernel_name(int k) {
                                              "k_wf_shade_ext", "k_wf_shade_shadow", "k_wf_accum",    "k_tonemap",
                                              "k_wf_step",      "k_wf_leafpass",     "k_noise_tiles", "k_tile_mean",
                                              "k_features",     "k_denoise_prepare", "k_atrous",      "k_query_hits",
-                                             "k_query_occluded", "k_camera_rays", "k_camera_seeds", "k_gather_rays"};
+                                             "k_query_occluded", "k_camera_rays", "k_camera_seeds", "k_gather_rays",
+                                             "k_reproject",    "k_denoise_prepare_mean"};
     return (k >= 0 && k < KID_COUNT) ? n[k] : "?";
 }
 struct KernelProfiler {
@@ -270,6 +272,28 @@ bool atrous_can_stage(uint32_t s);
 hipError_t launch_atrous(const float4* cv, const float4* nz, const float4* ab, uint32_t w, uint32_t h, uint32_t s, float isn,
                          float isa, float isz, float sigma_l, bool staged, float4* cv_out, float* out, float* var_out,
                          uint32_t row_pitch, hipStream_t stream);
+// temporal accumulation (pt_temporal.hip; pt_hip.h pt_reproject_async).  The current camera as camera_ray reads
+// it, what the warp reads of the previous one (pV: its world_to_cam, meta[12..27], column-major), the
+// call's parameters.  hist_prev, mom_prev, gbuf_prev: all three or none (a first step); every buffer's rows
+// are P.row_pitch pixels apart; out, var nullable.
+struct ReprojectParams {
+    uint32_t w, h, row_pitch, n;  // n: the frames of the step's moments render
+    float W, H, inv_w, inv_h, aspect, focal, view_half_h;
+    float cam[4];
+    float M[16];
+    float paspect, pfocal, pview_half_h;
+    float pcam[3];
+    float pV[16];
+    float alpha, normal_min, depth_tol, max_history;
+};
+hipError_t launch_reproject(const float* acc, const float* m2, const float* geo, const float* alb, const ReprojectParams& P,
+                            const float4* hist_prev, const float4* mom_prev, const float4* gbuf_prev, float4* hist,
+                            float4* mom, float4* gbuf, float* out, float* var, hipStream_t stream);
+// launch_denoise_prepare for a caller that has the mean c [h][w][3] and the variance of the mean var [h][w]
+// (pt_denoise_mean_async): the same three planes, the guides divided as there
+hipError_t launch_denoise_prepare_mean(const float* c, const float* var, const float* geo, const float* alb, uint32_t w,
+                                       uint32_t h, uint32_t row_pitch, uint32_t feature_frames, float4* cv, float4* nz,
+                                       float4* ab, hipStream_t stream);
 // ray queries (pt_query.hip; pt_hip.h pt_query_hits_async, pt_query_occluded_async): n <= 2^30 rays of 32 B
 // (pt_ray) traced to hits (n pt_hit records) or, hits == nullptr, to occluded (n bytes); exactly one of the
 // two is given.  ctl: the scene's ten query control words (a wave that gave up sets ctl[0] and launches

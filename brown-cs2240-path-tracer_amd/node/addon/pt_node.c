@@ -651,6 +651,259 @@ static napi_value new_typedarray(napi_env env, napi_typedarray_type type, size_t
     return ta;
 }
 
+/* Temporal accumulation (include/pt_hip.h pt_reproject, pt_denoise_mean, pt_history_*): blocking calls, as
+ * renderDenoised.  params: null (pt_temporal_defaults) or a Float32Array [alpha, normal_min, depth_tol, max_history] */
+static int get_temporal(napi_env env, napi_value v, pt_temporal_params* p, const pt_temporal_params** out) {
+    napi_valuetype t = napi_undefined;
+    *out = NULL;
+    if (napi_typeof(env, v, &t) != napi_ok) return 0;
+    if (t == napi_null || t == napi_undefined) return 1;
+    float* f;
+    size_t n;
+    if (!get_f32(env, v, &f, &n) || n != 4) return 0;
+    p->alpha = f[0]; p->normal_min = f[1]; p->depth_tol = f[2]; p->max_history = f[3];
+    *out = p;
+    return 1;
+}
+
+static int is_nullish(napi_env env, napi_value v) {
+    napi_valuetype t = napi_undefined;
+    return napi_typeof(env, v, &t) == napi_ok && (t == napi_null || t == napi_undefined);
+}
+
+/* reproject(scene, accum[W*H*3], m2[W*H*3], n, geo[W*H*4], alb[W*H*4], meta[48], prevMeta | null, prevHist | null,
+ *           prevMom | null, prevGbuf | null, params | null) -> {hist, mom, gbuf, out, var}: pt_reproject */
+static napi_value js_reproject(napi_env env, napi_callback_info info) {
+    size_t argc = 12;
+    napi_value argv[12];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    float *acc, *m2, *geo, *alb, *meta, *prev[4] = {NULL, NULL, NULL, NULL};
+    size_t al, sl, gl, bl, ml, pl;
+    uint32_t n;
+    pt_temporal_params prm;
+    const pt_temporal_params* pp = NULL;
+    pt_scene* s = argc >= 12 ? get_scene(env, argv[0]) : NULL;
+    int ok = s && get_f32(env, argv[1], &acc, &al) && get_f32(env, argv[2], &m2, &sl) && get_u32(env, argv[3], &n) &&
+             get_f32(env, argv[4], &geo, &gl) && get_f32(env, argv[5], &alb, &bl) && get_f32(env, argv[6], &meta, &ml) &&
+             ml >= 48 && get_temporal(env, argv[11], &prm, &pp);
+    size_t npix = 0;
+    if (ok) {
+        npix = (size_t)meta[0] * (size_t)meta[1];
+        ok = npix > 0 && al == 3 * npix && sl == 3 * npix && gl == 4 * npix && bl == 4 * npix;
+    }
+    for (int k = 0; ok && k < 4; ++k)
+        if (!is_nullish(env, argv[7 + k])) ok = get_f32(env, argv[7 + k], &prev[k], &pl) && pl == (k ? 4 * npix : 48);
+    if (!ok) {
+        if (!pending_exception(env))
+            napi_throw_type_error(env, NULL,
+                                  "reproject(scene, Float32Array accum[W*H*3], m2[W*H*3], n, geo[W*H*4], alb[W*H*4], meta[48], "
+                                  "prevMeta[48] | null, prevHist[W*H*4] | null, prevMom | null, prevGbuf | null, "
+                                  "Float32Array params[4] | null)");
+        return NULL;
+    }
+    float *hist, *mom, *gbuf, *out, *var;
+    napi_value o, vh = new_typedarray(env, napi_float32_array, 4 * npix, (void**)&hist),
+                  vm = new_typedarray(env, napi_float32_array, 4 * npix, (void**)&mom),
+                  vg = new_typedarray(env, napi_float32_array, 4 * npix, (void**)&gbuf),
+                  vo = new_typedarray(env, napi_float32_array, 3 * npix, (void**)&out),
+                  vv = new_typedarray(env, napi_float32_array, npix, (void**)&var);
+    if (!vh || !vm || !vg || !vo || !vv) return NULL;
+    int rc = pt_reproject(s, acc, m2, n, geo, alb, meta, prev[0], prev[1], prev[2], prev[3], (uint32_t)meta[0], (uint32_t)meta[1],
+                          pp, hist, mom, gbuf, out, var);
+    if (rc) return throw_pt(env, rc);
+    CHECK_NAPI(env, napi_create_object(env, &o));
+    napi_set_named_property(env, o, "hist", vh);
+    napi_set_named_property(env, o, "mom", vm);
+    napi_set_named_property(env, o, "gbuf", vg);
+    napi_set_named_property(env, o, "out", vo);
+    napi_set_named_property(env, o, "var", vv);
+    return o;
+}
+
+/* denoiseMean(scene, c[w*h*3], var[w*h], w, h, geo[w*h*4], alb[w*h*4], featureFrames, iters) -> {out, var}:
+ * pt_denoise_mean; iters 0 = pt_denoise_defaults, else the defaults with that many passes */
+static napi_value js_denoise_mean(napi_env env, napi_callback_info info) {
+    size_t argc = 9;
+    napi_value argv[9];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    float *c, *var, *geo, *alb;
+    size_t cl, vl, gl, bl;
+    uint32_t w, h, ff, iters;
+    pt_scene* s = argc >= 9 ? get_scene(env, argv[0]) : NULL;
+    if (!s || !get_f32(env, argv[1], &c, &cl) || !get_f32(env, argv[2], &var, &vl) || !get_u32(env, argv[3], &w) ||
+        !get_u32(env, argv[4], &h) || !get_f32(env, argv[5], &geo, &gl) || !get_f32(env, argv[6], &alb, &bl) ||
+        !get_u32(env, argv[7], &ff) || !get_u32(env, argv[8], &iters) || !w || !h || vl != (size_t)w * h || cl != 3 * vl ||
+        gl != 4 * vl || bl != 4 * vl) {
+        if (!pending_exception(env))
+            napi_throw_type_error(env, NULL,
+                                  "denoiseMean(scene, Float32Array c[w*h*3], var[w*h], w, h, geo[w*h*4], alb[w*h*4], featureFrames, "
+                                  "iters)");
+        return NULL;
+    }
+    pt_denoise_params p;
+    pt_denoise_defaults(&p);
+    if (iters) p.iters = iters;
+    float *out, *vout;
+    napi_value o, vo = new_typedarray(env, napi_float32_array, cl, (void**)&out),
+                  vv = new_typedarray(env, napi_float32_array, vl, (void**)&vout);
+    if (!vo || !vv) return NULL;
+    int rc = pt_denoise_mean(s, c, var, w, h, geo, alb, ff, &p, out, vout);
+    if (rc) return throw_pt(env, rc);
+    CHECK_NAPI(env, napi_create_object(env, &o));
+    napi_set_named_property(env, o, "out", vo);
+    napi_set_named_property(env, o, "var", vv);
+    return o;
+}
+
+/* A JS history handle: the library's history, its size, and a reference that keeps its scene's handle alive (the
+ * scene's job guard covers the history's calls: they run on the scene's stream) */
+typedef struct {
+    pt_history* h;
+    uint32_t w, ht;
+    napi_ref scene;
+} history_box;
+
+static void history_release(napi_env env, history_box* b) {
+    if (b->h) {
+        pt_history_destroy(b->h);
+        b->h = NULL;
+        int64_t adj = 0;
+        napi_adjust_external_memory(env, -(int64_t)((size_t)b->w * b->ht * 188), &adj);
+    }
+    if (b->scene) { napi_delete_reference(env, b->scene); b->scene = NULL; }
+}
+
+static void history_finalize(napi_env env, void* data, void* hint) {
+    (void)hint;
+    history_release(env, (history_box*)data);
+    free(data);
+}
+
+/* the live history of a handle whose scene is neither destroyed nor busy: NULL (and a pending JS error) otherwise */
+static history_box* get_history(napi_env env, napi_value v) {
+    void* p = NULL;
+    if (napi_get_value_external(env, v, &p) != napi_ok || !p) return NULL;
+    history_box* b = (history_box*)p;
+    if (!b->h) { napi_throw_error(env, NULL, "history was destroyed (historyDestroy)"); return NULL; }
+    napi_value sv;
+    if (napi_get_reference_value(env, b->scene, &sv) != napi_ok || !sv) return NULL;
+    scene_box* sb = get_box(env, sv);
+    if (sb && !sb->s) { napi_throw_error(env, NULL, "scene was destroyed (sceneDestroy): the history is unusable"); return NULL; }
+    if (sb && sb->busy) { napi_throw_error(env, NULL, "scene is busy: a render job on it has not completed"); return NULL; }
+    return b;
+}
+
+/* historyCreate(scene, w, h) -> external */
+static napi_value js_history_create(napi_env env, napi_callback_info info) {
+    size_t argc = 3;
+    napi_value argv[3];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    uint32_t w, h;
+    pt_scene* s = argc >= 3 ? get_scene(env, argv[0]) : NULL;
+    if (!s || !get_u32(env, argv[1], &w) || !get_u32(env, argv[2], &h)) {
+        if (!pending_exception(env)) napi_throw_type_error(env, NULL, "historyCreate(scene, w, h)");
+        return NULL;
+    }
+    history_box* b = (history_box*)calloc(1, sizeof(history_box));
+    if (!b) { napi_throw_error(env, NULL, "out of memory"); return NULL; }
+    int rc = pt_history_create(s, w, h, &b->h);
+    if (rc) { free(b); return throw_pt(env, rc); }
+    b->w = w; b->ht = h;
+    napi_value ext;
+    if (napi_create_reference(env, argv[0], 1, &b->scene) != napi_ok ||
+        napi_create_external(env, b, history_finalize, NULL, &ext) != napi_ok) {
+        history_release(env, b);
+        free(b);
+        napi_throw_error(env, NULL, "napi_create_external failed");
+        return NULL;
+    }
+    int64_t adj = 0;
+    napi_adjust_external_memory(env, (int64_t)((size_t)w * h * 188), &adj);  /* 6 planes, 22 floats, 4 bytes per pixel */
+    return ext;
+}
+
+/* historyReset(history): the next step is a first step */
+static napi_value js_history_reset(napi_env env, napi_callback_info info) {
+    size_t argc = 1;
+    napi_value argv[1];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    history_box* b = argc ? get_history(env, argv[0]) : NULL;
+    if (!b) {
+        if (!pending_exception(env)) napi_throw_type_error(env, NULL, "historyReset(history)");
+        return NULL;
+    }
+    int rc = pt_history_reset(b->h);
+    if (rc) return throw_pt(env, rc);
+    return NULL;
+}
+
+/* historyDestroy(history): free its device memory now (the handle becomes unusable) */
+static napi_value js_history_destroy(napi_env env, napi_callback_info info) {
+    size_t argc = 1;
+    napi_value argv[1];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    void* p = NULL;
+    if (!argc || napi_get_value_external(env, argv[0], &p) != napi_ok || !p) {
+        napi_throw_type_error(env, NULL, "historyDestroy(history)");
+        return NULL;
+    }
+    history_box* b = (history_box*)p;
+    /* a history whose scene is gone has lost its buffers already: only the handle is released */
+    if (b->h) {
+        napi_value sv;
+        scene_box* sb = napi_get_reference_value(env, b->scene, &sv) == napi_ok && sv ? get_box(env, sv) : NULL;
+        if (sb && sb->busy) { napi_throw_error(env, NULL, "scene is busy: a render job on it has not completed"); return NULL; }
+    }
+    history_release(env, b);
+    return NULL;
+}
+
+/* historyStep(history, meta[48], frame0, nframes, stride, maxDepth, mode, featureFrames, params | null, denoiseIters)
+ * -> {mean[w*h*3], var[w*h], rgba[w*h*4], historyLen[w*h]}: pt_history_step; denoiseIters -1 = unfiltered,
+ * 0 = pt_denoise_defaults, else the defaults with that many passes */
+static napi_value js_history_step(napi_env env, napi_callback_info info) {
+    size_t argc = 10;
+    napi_value argv[10];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    float* meta;
+    size_t ml;
+    uint32_t frame0, nframes, stride, ff;
+    int32_t md, mode, iters;
+    pt_temporal_params prm;
+    const pt_temporal_params* pp = NULL;
+    history_box* b = argc >= 10 ? get_history(env, argv[0]) : NULL;
+    if (!b || !get_f32(env, argv[1], &meta, &ml) || ml < 48 || !get_u32(env, argv[2], &frame0) ||
+        !get_u32(env, argv[3], &nframes) || !get_u32(env, argv[4], &stride) || !get_i32(env, argv[5], &md) ||
+        !get_i32(env, argv[6], &mode) || !get_u32(env, argv[7], &ff) || !get_temporal(env, argv[8], &prm, &pp) ||
+        !get_i32(env, argv[9], &iters) || iters < -1) {
+        if (!pending_exception(env))
+            napi_throw_type_error(env, NULL,
+                                  "historyStep(history, Float32Array meta[48], frame0, nframes, stride, maxDepth, mode, "
+                                  "featureFrames, Float32Array params[4] | null, denoiseIters)");
+        return NULL;
+    }
+    pt_denoise_params dp;
+    pt_denoise_defaults(&dp);
+    if (iters > 0) dp.iters = (uint32_t)iters;
+    const size_t npix = (size_t)b->w * b->ht;
+    float *mean, *var, *len;
+    uint8_t* rgba;
+    napi_value o, vm = new_typedarray(env, napi_float32_array, 3 * npix, (void**)&mean),
+                  vv = new_typedarray(env, napi_float32_array, npix, (void**)&var),
+                  vr = new_typedarray(env, napi_uint8_array, 4 * npix, (void**)&rgba),
+                  vl = new_typedarray(env, napi_float32_array, npix, (void**)&len);
+    if (!vm || !vv || !vr || !vl) return NULL;
+    int rc = pt_history_step(b->h, meta, frame0, nframes, stride, md, mode, ff, pp, iters >= 0 ? &dp : NULL, mean, var, rgba, len,
+                             NULL);
+    if (rc) return throw_pt(env, rc);
+    CHECK_NAPI(env, napi_create_object(env, &o));
+    napi_set_named_property(env, o, "mean", vm);
+    napi_set_named_property(env, o, "var", vv);
+    napi_set_named_property(env, o, "rgba", vr);
+    napi_set_named_property(env, o, "historyLen", vl);
+    return o;
+}
+
 /* queryHits(scene, Float32Array rays[8n]) -> Float32Array[8n]: pt_query_hits — per ray (o.xyz, tmax, d.xyz,
  * reserved) the closest hit's (p.xyz, t, n.xyz, material as int32 bits; a miss: t = -1, material = -1).
  * queryOccluded(scene, rays) -> Uint8Array[n]: pt_query_occluded.  Blocking. */
@@ -1221,6 +1474,12 @@ static napi_value init(napi_env env, napi_value exports) {
         {"bvhBuild", NULL, js_bvh_build, NULL, NULL, NULL, napi_enumerable, NULL},
         {"sceneSetVertexNormals", NULL, js_scene_set_vertex_normals, NULL, NULL, NULL, napi_enumerable, NULL},
         {"sceneSetCamera", NULL, js_scene_set_camera, NULL, NULL, NULL, napi_default, NULL},
+        {"reproject", NULL, js_reproject, NULL, NULL, NULL, napi_default, NULL},
+        {"denoiseMean", NULL, js_denoise_mean, NULL, NULL, NULL, napi_default, NULL},
+        {"historyCreate", NULL, js_history_create, NULL, NULL, NULL, napi_default, NULL},
+        {"historyStep", NULL, js_history_step, NULL, NULL, NULL, napi_default, NULL},
+        {"historyReset", NULL, js_history_reset, NULL, NULL, NULL, napi_default, NULL},
+        {"historyDestroy", NULL, js_history_destroy, NULL, NULL, NULL, napi_default, NULL},
     };
     napi_define_properties(env, exports, sizeof props / sizeof props[0], props);
     return exports;

@@ -35,6 +35,11 @@
 //  in N equal steps, step 0 the scene's camera — rendered in ONE renderViews call (pt_render_views) into a contact
 //  sheet of `cols` tiles per row (default ceil(sqrt(N))), which is the PNG; combines with --camera, --counters 1 and
 //  --dump-accum FILE (the sheet's accumulator); not with --window, --denoise or --projection)
+// [--turntable N[,cols] --temporal [alpha]] (the N views rendered IN ORDER through one history, pt_history_step: view k
+//  takes the next --spp frames (frames k spp .. k spp + spp - 1) and starts from what the views before it accumulated,
+//  reprojected into its camera; alpha in (0, 1] is the blend's floor, default the library's 0.2.  The sheet holds the
+//  accumulated tiles, with --denoise [iters] [--feature-frames N] filtered by the a-trous denoiser on each view's guides;
+//  not with --window, --counters 1, --camera, --projection or --dump-accum)
 // [--dump-rays FILE] (with equirect or ortho: the rays, 8 f32 each, then the seeds, one u32 each, as made)
 // [--dump-accum FILE] (with equirect or ortho: the accumulator, 3 f32 per pixel, before the tone map)
 const fs = require('fs');
@@ -44,7 +49,7 @@ const host = require('..');
 async function main(argv) {
     const args = { _: [] };
     for (let i = 0; i < argv.length; i++) {
-        if (argv[i] === '--denoise' && (i + 1 >= argv.length || argv[i + 1].startsWith('--'))) args.denoise = '';
+        if ((argv[i] === '--denoise' || argv[i] === '--temporal') && (i + 1 >= argv.length || argv[i + 1].startsWith('--'))) args[argv[i].slice(2)] = '';
         else if (argv[i].startsWith('--')) args[argv[i].slice(2).replace(/-/g, '_')] = argv[++i];
         else args._.push(argv[i]);
     }
@@ -76,13 +81,24 @@ async function main(argv) {
         }
         denoise = { iters: +it, featureFrames: +ff };
     }
+    let temporal = null;
+    if (args.temporal !== undefined) {
+        const a = args.temporal === '' ? undefined : Number(args.temporal);
+        if (args.turntable === undefined || (a !== undefined && !(/^[0-9.eE+-]+$/.test(String(args.temporal)) && a > 0 && a <= 1)) ||
+            window || rects || args.counters === '1' || args.camera !== undefined || args.projection !== undefined || args.dump_accum !== undefined) {
+            console.error('usage: pt-render.js <scene.ini> --turntable N[,cols] --temporal [alpha] (alpha in (0, 1]; with --turntable only, ' +
+                          `not with --window, --counters 1, --camera, --projection or --dump-accum): --temporal ${args.temporal}`);
+            process.exit(2);
+        }
+        temporal = { alpha: a };
+    }
     let turntable = null;
     if (args.turntable !== undefined) {
         const parts = String(args.turntable).split(',');
         if (parts.length < 1 || parts.length > 2 || !parts.every((v) => /^\d+$/.test(v)) || !(+parts[0] >= 1 && +parts[0] <= 65536) ||
-            (parts.length > 1 && !(+parts[1] >= 1)) || window || rects || denoise || args.projection !== undefined) {
+            (parts.length > 1 && !(+parts[1] >= 1)) || window || rects || (denoise && !temporal) || args.projection !== undefined) {
             console.error('usage: pt-render.js <scene.ini> --turntable N[,cols] (N in 1..65536, cols at least 1; ' +
-                          `not with --window, --denoise or --projection): --turntable ${args.turntable}`);
+                          `not with --window or --projection, with --denoise only under --temporal): --turntable ${args.turntable}`);
             process.exit(2);
         }
         turntable = { n: +parts[0], cols: parts.length > 1 ? +parts[1] : undefined };
@@ -114,6 +130,7 @@ async function main(argv) {
         const dist = Math.hypot(focus[0] - pos[0], focus[1] - pos[1], focus[2] - pos[2]);
         camera = { model: models[args.camera], lensRadius: num(args.aperture) || 0, focusDistance: args.focus_distance === undefined ? dist : num(args.focus_distance) };
     }
+    if (turntable && temporal) return turnTemporal(args, s, turntable, temporal, denoise, t0);
     if (turntable) return turn(args, s, turntable, camera, t0);
     const t1 = Date.now();
     const r = await host.programEntry(s.screenDimension, s.primitive_data, s.camera_data, s.scene_description, {
@@ -157,6 +174,39 @@ async function turn(args, s, turntable, camera, t0) {
     if (args.dump_accum) fs.writeFileSync(args.dump_accum, Buffer.from(r.accum.buffer, r.accum.byteOffset, r.accum.byteLength));
     console.log(JSON.stringify({ output: out, width: atlasW, height: atlasH, turntable: turntable.n, tile: [W, H], dsts, camera, spp,
         scene_ms: t1 - t0, render_ms: t2 - t1, msamples_per_s: W * H * turntable.n * spp / ((t2 - t1) / 1000) / 1e6, counters: r.counters }));
+}
+// --turntable N[,cols] --temporal [alpha]: the N views in order through one history, the accumulated tiles as the sheet
+async function turnTemporal(args, s, turntable, temporal, denoise, t0) {
+    const [W, H] = s.screenDimension;
+    const spp = s.scene_description.Settings.samplesPerPixel;
+    const cams = host.turntable_cameras(s.camera_data, turntable.n);
+    const { dsts, atlasW, atlasH } = host.view_atlas(cams.map(() => [W, H]), turntable.cols);
+    const t1 = Date.now();
+    const pt = host.native();
+    const scene = pt.sceneCreate(s.primitive_data[0].triangle_data, s.primitive_data[0].bvh_data, parseInt(args.device || '0'));
+    const rgba = new Uint8ClampedArray(atlasW * atlasH * 4);
+    let history = null;
+    try {
+        if (args.vertex_normals === '1') pt.sceneSetVertexNormals(scene, true);
+        history = host.historyCreate(scene, W, H);
+        cams.forEach((c, k) => {
+            const r = host.historyStep(history, host.make_meta(s.screenDimension, c, s.scene_description, 0), {
+                frame0: k * spp, nframes: spp, maxDepth: parseInt(args.max_depth || '16'), mode: args.mode || 'auto',
+                featureFrames: denoise ? denoise.featureFrames : Math.min(4, spp),
+                params: temporal.alpha === undefined ? null : { alpha: temporal.alpha }, denoise });
+            const [dx, dy] = dsts[k];
+            for (let y = 0; y < H; ++y) rgba.set(r.rgba.subarray(4 * y * W, 4 * (y + 1) * W), 4 * ((dy + y) * atlasW + dx));
+        });
+    } finally {
+        if (history) host.historyDestroy(history);
+        pt.sceneDestroy(scene);
+    }
+    const t2 = Date.now();
+    const out = path.join(args.out_root || '.', s.scene_description.IO.output || 'out.png');
+    fs.mkdirSync(path.dirname(out), { recursive: true });
+    fs.writeFileSync(out, host.encode_png(rgba, atlasW, atlasH));
+    console.log(JSON.stringify({ output: out, width: atlasW, height: atlasH, turntable: turntable.n, tile: [W, H], dsts, temporal, denoise, spp,
+        scene_ms: t1 - t0, render_ms: t2 - t1, msamples_per_s: W * H * turntable.n * spp / ((t2 - t1) / 1000) / 1e6 }));
 }
 // hash.wgsl's hash1u in u32 arithmetic
 function hash1u(n) {

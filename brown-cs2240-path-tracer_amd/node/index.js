@@ -81,6 +81,48 @@ const gather = (scene, points, params = {}) => {
 };
 const gatherRays = (scene, points, sample = 0, mode = 'cosine') => addon.load().gatherRays(scene, points, sample, gatherMode(mode));
 
+// Temporal accumulation (include/pt_hip.h pt_reproject, pt_denoise_mean, pt_history_*): the history of a pixel's
+// surface point carried across a camera move.  params: null (the library's defaults) or any of { alpha, normalMin,
+// depthTol, maxHistory } over them (0.2, 0.9, 0.1, 64).
+//   reproject(scene, { accum, m2, n, geo, alb, meta }, prev = null, params = null) -> { meta, hist, mom, gbuf, out, var }:
+//       one step from an n-frame moments render and its guide sums; prev: null or an earlier step's result
+//   denoiseMean(scene, c, var, w, h, geo, alb, { featureFrames = 4, iters = 0 }) -> { out, var }: the a-trous filter on a
+//       given mean and variance of the mean (reproject's out and var)
+//   historyCreate(scene, w, h) -> history; historyReset(history); historyDestroy(history)
+//   historyStep(history, meta, { frame0 = 0, nframes, stride = 1, maxDepth = 16, mode = 'auto', featureFrames = 4,
+//       params = null, denoise = null | true | { iters } }) -> { mean, var, rgba, historyLen }: render, guides,
+//       reprojection against the previous step, optionally the filter, the tone map
+const temporalParams = (p) => {
+    if (p === null || p === undefined) return null;
+    const known = ['alpha', 'normalMin', 'depthTol', 'maxHistory'];
+    for (const k of Object.keys(p)) if (!known.includes(k)) throw new TypeError(`temporal params: unknown field ${k}`);
+    const { alpha = 0.2, normalMin = 0.9, depthTol = 0.1, maxHistory = 64 } = p;
+    const v = [alpha, normalMin, depthTol, maxHistory];
+    if (!v.every((x) => typeof x === 'number' && Number.isFinite(x)) || !(alpha > 0 && alpha <= 1) || !(depthTol > 0) || !(maxHistory >= 1))
+        throw new RangeError('temporal params: alpha in (0, 1], normalMin finite, depthTol > 0, maxHistory >= 1');
+    return Float32Array.from(v);
+};
+const reproject = (scene, step, prev = null, params = null) => {
+    const r = addon.load().reproject(scene, step.accum, step.m2, step.n, step.geo, step.alb, step.meta, prev ? prev.meta : null,
+        prev ? prev.hist : null, prev ? prev.mom : null, prev ? prev.gbuf : null, temporalParams(params));
+    r.meta = Float32Array.from(step.meta);
+    return r;
+};
+const denoiseMean = (scene, c, variance, w, h, geo, alb, params = {}) => {
+    const { featureFrames = 4, iters = 0 } = params;
+    return addon.load().denoiseMean(scene, c, variance, w, h, geo, alb, featureFrames, iters);
+};
+const historyCreate = (scene, w, h) => addon.load().historyCreate(scene, w, h);
+const historyReset = (history) => addon.load().historyReset(history);
+const historyDestroy = (history) => addon.load().historyDestroy(history);
+const historyStep = (history, meta, options = {}) => {
+    const { frame0 = 0, nframes, stride = 1, maxDepth = 16, mode = 'auto', featureFrames = 4, params = null, denoise = null } = options;
+    const m = typeof mode === 'number' ? mode : MODE[mode];
+    if (m === undefined) throw new TypeError(`historyStep: unknown mode ${mode}`);
+    const iters = denoise === null || denoise === undefined || denoise === false ? -1 : (denoise === true ? 0 : (denoise.iters || 0));
+    return addon.load().historyStep(history, meta, frame0, nframes, stride, maxDepth, m, featureFrames, temporalParams(params), iters);
+};
+
 module.exports = {
     parse_ini_file, ini_file_to_ini_scene, parse_obj, BVH, pack_scene_object_group, pack_bvh,
     mat4_rot_axis, bounds_of_vec3, chunk_into_3, bounds_bounds_intersection_3d, bounds_surface_area,
@@ -92,4 +134,5 @@ module.exports = {
     renderViews, view_atlas, turntable_cameras,
     queryHits, queryOccluded, cameraRays, queryRadiance, cameraSeeds, unitRays,
     gather, gatherRays, gatherPoints,
+    reproject, denoiseMean, historyCreate, historyStep, historyReset, historyDestroy,
 };

@@ -21,6 +21,7 @@ from ._lib import (  # noqa: F401
     Counters,
     DenoiseParams,
     HIT_DTYPE,
+    History,
     Hit,
     PtError,
     RAY_DTYPE,
@@ -29,6 +30,7 @@ from ._lib import (  # noqa: F401
     Scene,
     SceneInfo,
     TILE_NOISE_DTYPE,
+    TemporalParams,
     TileNoise,
     View,
     Window,
@@ -53,6 +55,7 @@ from ._lib import (  # noqa: F401
     set_hw_queues,
     set_option,
     source_hash,
+    temporal_defaults,
     tile_rects,
     tonemap,
     view_atlas,

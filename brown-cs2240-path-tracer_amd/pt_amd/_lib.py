@@ -12,9 +12,9 @@ _LIB_FILE = os.path.join(_PKG_ROOT, "lib", "libpt_hip.so")
 ABI_VERSION = 3  # include/pt_hip.h PT_ABI_VERSION
 _CSRC = os.path.join(_PKG_ROOT, "csrc")
 # csrc/Makefile BUILD_SRCS: the sources whose SHA-256 the library carries as pt_build_id()
-_BUILD_SRCS = ["pt_kernels.hip", "pt_wavefront.hip", "pt_wf_source.hip", "pt_wf_trace.hip", "pt_wf_bf.hip", "pt_wf_shade.hip", "pt_leafpass.hip", "pt_image.hip", "pt_features.hip", "pt_denoise.hip", "pt_query.hip", "pt_capi.hip", "pt_capi_render.hip",
+_BUILD_SRCS = ["pt_kernels.hip", "pt_wavefront.hip", "pt_wf_source.hip", "pt_wf_trace.hip", "pt_wf_bf.hip", "pt_wf_shade.hip", "pt_leafpass.hip", "pt_image.hip", "pt_features.hip", "pt_denoise.hip", "pt_temporal.hip", "pt_query.hip", "pt_capi.hip", "pt_capi_render.hip",
                "pt_capi_adaptive.hip", "pt_capi_denoise.hip", "pt_capi_query.hip", "pt_capi_radiance.hip", "pt_capi_gather.hip", "pt_capi_selftest.hip",
-               "pt_capi_multi.hip", "pt_capi_camera.hip", "pt_capi_views.hip", "pt_capi_internal.h", "pt_math.h", "pt_flavour.h", "pt_layout.h",
+               "pt_capi_multi.hip", "pt_capi_camera.hip", "pt_capi_views.hip", "pt_capi_temporal.hip", "pt_capi_internal.h", "pt_math.h", "pt_flavour.h", "pt_layout.h",
                "pt_device.h", "pt_path.h", "pt_kernels.h", "../../include/pt_hip.h", "pt_bvh.cpp", "pt_leafbvh.h",
                "pt_leafbvh.cpp", "pt_leafskip.cpp", "pt_scene_layout.h", "pt_scene_layout.cpp", "pt_rect_plan.h",
                "pt_rect_plan.cpp", "pt_view_plan.h", "pt_view_plan.cpp", "pt_query_plan.h", "pt_step_addr.h", "pt_wf_plan.h",
@@ -291,6 +291,51 @@ def _denoise_params(params):
     return p
 
 
+class TemporalParams(ctypes.Structure):
+    """pt_temporal_params (16 B): the blend's floor alpha in (0, 1], a tap's least normal dot product, its
+    largest relative depth difference (> 0) and the clamp of the history length (>= 1); all finite."""
+    _fields_ = [("alpha", ctypes.c_float), ("normal_min", ctypes.c_float), ("depth_tol", ctypes.c_float),
+                ("max_history", ctypes.c_float)]
+
+
+def temporal_defaults() -> TemporalParams:
+    """pt_temporal_defaults: alpha 0.2, normal_min 0.9, depth_tol 0.1, max_history 64."""
+    p = TemporalParams()
+    load_library().pt_temporal_defaults(ctypes.byref(p))
+    return p
+
+
+def _temporal_params(params):
+    """None (the library's defaults), a TemporalParams, or a mapping over the defaults' fields, checked on
+    the host (the library checks again)."""
+    if params is None:
+        return None
+    names = [n for n, _ in TemporalParams._fields_]
+    if isinstance(params, TemporalParams):
+        p = TemporalParams(*(getattr(params, n) for n in names))
+    else:
+        try:
+            kv = dict(params)
+        except (TypeError, ValueError):
+            raise PtError(-1, f"params must be a TemporalParams or a mapping of its fields, not {params!r}") from None
+        unknown = set(kv) - set(names)
+        if unknown:
+            raise PtError(-1, f"params: unknown field(s) {sorted(unknown)}")
+        p = temporal_defaults()
+        for n in names:
+            if n in kv:
+                setattr(p, n, _real(kv[n], n, positive=False))
+    for n in names:
+        _real(getattr(p, n), n, positive=False)
+    if not 0.0 < p.alpha <= 1.0:
+        raise PtError(-1, f"alpha must lie in (0, 1], not {p.alpha!r}")
+    if not p.depth_tol > 0.0:
+        raise PtError(-1, f"depth_tol must be > 0, not {p.depth_tol!r}")
+    if not p.max_history >= 1.0:
+        raise PtError(-1, f"max_history must be at least 1, not {p.max_history!r}")
+    return p
+
+
 class Ray(ctypes.Structure):
     """pt_ray (32 B): origin, tmax, direction (not normalised; t is in its units), reserved (ignored)."""
     _fields_ = [("o", ctypes.c_float * 3), ("tmax", ctypes.c_float), ("d", ctypes.c_float * 3),
@@ -546,6 +591,21 @@ def load_library():
     L.pt_denoise_async.argtypes = [p, p, p, u32, u32, sz, u32, u32, p, p, p, u32, dpp, p, p, p]
     L.pt_render_denoised_image.argtypes = [p, p, u32, u32, u32, i, i, u32, dpp, p, p]
     for fn in ("pt_render_features", "pt_render_features_async", "pt_denoise", "pt_denoise_async", "pt_render_denoised_image"):
+        getattr(L, fn).restype = i
+    tpp = ctypes.POINTER(TemporalParams)
+    L.pt_temporal_defaults.argtypes = [tpp]
+    L.pt_temporal_defaults.restype = None
+    L.pt_reproject_async.argtypes = [p, p, p, u32, p, p, p, p, p, p, p, u32, u32, sz, tpp, p, p, p, p, p, p]
+    L.pt_reproject.argtypes = [p, p, p, u32, p, p, p, p, p, p, p, u32, u32, tpp, p, p, p, p, p]
+    L.pt_denoise_mean_async.argtypes = [p, p, p, u32, u32, sz, p, p, u32, dpp, p, p, p]
+    L.pt_denoise_mean.argtypes = [p, p, p, u32, u32, p, p, u32, dpp, p, p]
+    L.pt_history_create.argtypes = [p, u32, u32, ctypes.POINTER(p)]
+    L.pt_history_reset.argtypes = [p]
+    L.pt_history_destroy.argtypes = [p]
+    L.pt_history_destroy.restype = None
+    L.pt_history_step.argtypes = [p, p, u32, u32, u32, i, i, u32, tpp, dpp, p, p, p, p, p]
+    for fn in ("pt_reproject_async", "pt_reproject", "pt_denoise_mean_async", "pt_denoise_mean", "pt_history_create",
+               "pt_history_reset", "pt_history_step"):
         getattr(L, fn).restype = i
     L.pt_tonemap.argtypes = [p, sz, u32, p]
     L.pt_selftest_math.argtypes = [i, i, p, p, p, sz]
@@ -1231,6 +1291,89 @@ class Scene:
                                           ctypes.byref(prm) if prm is not None else None, v(d_out_ptr or None),
                                           v(d_var_out_ptr or None), v(stream_ptr or None)))
 
+    def denoise_mean(self, c, var, geo, alb, feature_frames: int, params=None):
+        """pt_denoise_mean: the denoiser for a caller that has the mean c [h, w, 3] and the variance of the
+        mean var [h, w] (reproject's out and var); geo, alb, feature_frames and params as for denoise.
+        Returns (image [h, w, 3], variance [h, w])."""
+        cc, vv, ge, al = _f32(c), _f32(var), _f32(geo), _f32(alb)
+        if cc.ndim != 3 or cc.shape[2] != 3:
+            raise PtError(-1, f"c must be [h, w, 3], not {cc.shape}")
+        h, w = cc.shape[:2]
+        if vv.shape != (h, w):
+            raise PtError(-1, f"var must be [{h}, {w}], not {vv.shape}")
+        if ge.shape != (h, w, 4) or al.shape != (h, w, 4):
+            raise PtError(-1, f"geo and alb must both be [{h}, {w}, 4], not {ge.shape} and {al.shape}")
+        prm = _denoise_params(params)
+        out, vout = np.zeros((h, w, 3), np.float32), np.zeros((h, w), np.float32)
+        _check(self._lib.pt_denoise_mean(self._h, _ptr(cc), _ptr(vv), w, h, _ptr(ge), _ptr(al),
+                                         _uint(feature_frames, "feature_frames", 1),
+                                         ctypes.byref(prm) if prm is not None else None, _ptr(out), _ptr(vout)))
+        return out, vout
+
+    def denoise_mean_async(self, d_c_ptr: int, d_var_ptr: int, w: int, h: int, d_geo_ptr: int, d_alb_ptr: int,
+                           feature_frames: int, d_out_ptr: int, d_var_out_ptr: int = 0, params=None, row_pitch=None,
+                           stream_ptr: int = 0):
+        """pt_denoise_mean_async between caller-owned device buffers, all with rows row_pitch pixels apart
+        (default w): c [h, w, 3], var [h, w], guides [h, w, 4], out [h, w, 3] and (0: none) var_out [h, w]."""
+        w, h = _uint(w, "w", 1), _uint(h, "h", 1)
+        pitch = w if row_pitch is None else _uint(row_pitch, "row_pitch")
+        prm = _denoise_params(params)
+        v = ctypes.c_void_p
+        _check(self._lib.pt_denoise_mean_async(self._h, v(d_c_ptr or None), v(d_var_ptr or None), w, h, pitch,
+                                               v(d_geo_ptr or None), v(d_alb_ptr or None),
+                                               _uint(feature_frames, "feature_frames", 1),
+                                               ctypes.byref(prm) if prm is not None else None, v(d_out_ptr or None),
+                                               v(d_var_out_ptr or None), v(stream_ptr or None)))
+
+    def reproject(self, accum, m2, n: int, geo, alb, meta, prev=None, params=None):
+        """pt_reproject: one step of temporal accumulation on host buffers.  accum, m2 [h, w, 3]: the sums of
+        an n-frame moments render from zero; geo, alb [h, w, 4]: render_features' sums; meta: the step's
+        camera.  prev: None (a first step) or the previous step's result (its "meta", "hist", "mom",
+        "gbuf").  params: None (temporal_defaults()), a TemporalParams or a mapping of its fields.
+        Returns {"meta", "hist", "mom", "gbuf" [h, w, 4], "out" [h, w, 3], "var" [h, w]}."""
+        acc, sq, ge, al, meta = _f32(accum), _f32(m2), _f32(geo), _f32(alb), _f32(meta)
+        if acc.ndim != 3 or acc.shape[2] != 3 or sq.shape != acc.shape:
+            raise PtError(-1, f"accum and m2 must both be [h, w, 3], not {acc.shape} and {sq.shape}")
+        h, w = acc.shape[:2]
+        if ge.shape != (h, w, 4) or al.shape != (h, w, 4):
+            raise PtError(-1, f"geo and alb must both be [{h}, {w}, 4], not {ge.shape} and {al.shape}")
+        if meta.shape != (48,):
+            raise PtError(-1, "meta must hold 48 floats")
+        pm = ph = pq = pg = None
+        if prev is not None:
+            pm, ph, pq, pg = (_f32(prev[k]) for k in ("meta", "hist", "mom", "gbuf"))
+            if pm.shape != (48,) or any(a.shape != (h, w, 4) for a in (ph, pq, pg)):
+                raise PtError(-1, f"prev: meta must hold 48 floats and hist, mom, gbuf be [{h}, {w}, 4]")
+        prm = _temporal_params(params)
+        r = {"meta": meta.copy(), "hist": np.zeros((h, w, 4), np.float32), "mom": np.zeros((h, w, 4), np.float32),
+             "gbuf": np.zeros((h, w, 4), np.float32), "out": np.zeros((h, w, 3), np.float32),
+             "var": np.zeros((h, w), np.float32)}
+        q = lambda a: _ptr(a) if a is not None else None
+        _check(self._lib.pt_reproject(self._h, _ptr(acc), _ptr(sq), _uint(n, "n", 1), _ptr(ge), _ptr(al), _ptr(meta), q(pm),
+                                      q(ph), q(pq), q(pg), w, h, ctypes.byref(prm) if prm is not None else None,
+                                      _ptr(r["hist"]), _ptr(r["mom"]), _ptr(r["gbuf"]), _ptr(r["out"]), _ptr(r["var"])))
+        return r
+
+    def reproject_async(self, d_accum_ptr: int, d_m2_ptr: int, n: int, d_geo_ptr: int, d_alb_ptr: int, meta, w: int, h: int,
+                        d_hist_ptr: int, d_mom_ptr: int, d_gbuf_ptr: int, meta_prev=None, d_hist_prev_ptr: int = 0,
+                        d_mom_prev_ptr: int = 0, d_gbuf_prev_ptr: int = 0, d_out_ptr: int = 0, d_var_ptr: int = 0,
+                        params=None, row_pitch=None, stream_ptr: int = 0):
+        """pt_reproject_async between caller-owned device buffers, all with rows row_pitch pixels apart
+        (default w).  meta_prev None and the three previous planes 0: a first step."""
+        meta = _f32(meta)
+        mp = None if meta_prev is None else _f32(meta_prev)
+        w, h = _uint(w, "w", 1), _uint(h, "h", 1)
+        pitch = w if row_pitch is None else _uint(row_pitch, "row_pitch")
+        prm = _temporal_params(params)
+        v = ctypes.c_void_p
+        _check(self._lib.pt_reproject_async(self._h, v(d_accum_ptr or None), v(d_m2_ptr or None), _uint(n, "n", 1),
+                                            v(d_geo_ptr or None), v(d_alb_ptr or None), _ptr(meta),
+                                            _ptr(mp) if mp is not None else None, v(d_hist_prev_ptr or None),
+                                            v(d_mom_prev_ptr or None), v(d_gbuf_prev_ptr or None), w, h, pitch,
+                                            ctypes.byref(prm) if prm is not None else None, v(d_hist_ptr or None),
+                                            v(d_mom_ptr or None), v(d_gbuf_ptr or None), v(d_out_ptr or None),
+                                            v(d_var_ptr or None), v(stream_ptr or None)))
+
     def render_denoised(self, meta, frame0: int, nframes: int, stride: int = 1, max_depth: int = -1, mode: int = MODE_AUTO,
                         feature_frames: int = 4, params=None, counters: bool = False):
         """pt_render_denoised_image: an nframes (>= 2) moments render, the guides of the first
@@ -1386,6 +1529,65 @@ def view_plan(views, atlas=None):
     npix = ctypes.c_uint64(0)
     _check(load_library().pt_selftest_view_plan(arr, n, aw, ah, _ptr(first), ctypes.byref(npix)))
     return first, int(npix.value)
+
+
+class History:
+    """pt_history: the temporal state of one camera path on the device (two sets of the hist, mom and gbuf
+    planes of a w x h image and the previous step's camera), counted in the scene's device_bytes.  Close it
+    before its scene; a step after the scene is gone raises PtError."""
+
+    def __init__(self, scene: Scene, w: int, h: int):
+        self._lib = scene._lib
+        self.w, self.h = _uint(w, "w", 1), _uint(h, "h", 1)
+        hd = ctypes.c_void_p()
+        _check(self._lib.pt_history_create(scene._h, self.w, self.h, ctypes.byref(hd)))
+        self._h = hd
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.pt_history_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def reset(self):
+        """pt_history_reset: the next step is a first step."""
+        _check(self._lib.pt_history_reset(self._h))
+
+    def step(self, meta, frame0: int, nframes: int, stride: int = 1, max_depth: int = -1, mode: int = MODE_AUTO,
+             feature_frames: int = 4, params=None, denoise=None, counters: bool = False) -> dict:
+        """pt_history_step: an nframes moments render of meta's image, the guides of the first feature_frames
+        frames, the reprojection against the previous step (params: as for Scene.reproject), optionally the
+        denoiser (denoise: None = unfiltered, True = denoise_defaults(), or as Scene.denoise's params) and
+        the tone map.  Returns {"mean" [h, w, 3], "var" [h, w], "rgba" [h, w, 4] u8, "history_len" [h, w]}
+        (and "counters")."""
+        meta = _f32(meta)
+        if meta.shape != (48,):
+            raise PtError(-1, "meta must hold 48 floats")
+        tp = _temporal_params(params)
+        dp = denoise_defaults() if denoise is True else _denoise_params(denoise)
+        h, w = self.h, self.w
+        r = {"mean": np.zeros((h, w, 3), np.float32), "var": np.zeros((h, w), np.float32),
+             "rgba": np.zeros((h, w, 4), np.uint8), "history_len": np.zeros((h, w), np.float32)}
+        c = Counters()
+        _check(self._lib.pt_history_step(self._h, _ptr(meta), _uint(frame0, "frame0"), _uint(nframes, "nframes", 1),
+                                         _uint(stride, "stride"), max_depth, mode, _uint(feature_frames, "feature_frames", 1),
+                                         ctypes.byref(tp) if tp is not None else None,
+                                         ctypes.byref(dp) if dp is not None else None, _ptr(r["mean"]), _ptr(r["var"]),
+                                         _ptr(r["rgba"]), _ptr(r["history_len"]), ctypes.byref(c) if counters else None))
+        if counters:
+            r["counters"] = c.as_dict()
+        return r
 
 
 def tonemap(accum, sample_runs: int) -> np.ndarray:

@@ -411,6 +411,113 @@ int pt_render_denoised_image(pt_scene* scene, const float meta[48], uint32_t fra
                              uint32_t frame_stride, int max_depth, int mode, uint32_t feature_frames,
                              const pt_denoise_params* params, uint8_t* rgba_out, pt_counters* counters);
 
+/* The denoiser for a caller that already has the mean and the variance of the mean: d_c [h][w][3] and
+ * d_var [h][w] take the place of accum, m2, the tiles and their frame counts.  Prepare is c and var as given,
+ * N, Z, A as above; the constants and the passes are pt_denoise_async's, so with the c and var of its prepare
+ * the result has pt_denoise_async's bits.  Rows of ALL six buffers are row_pitch pixels apart; d_geo and
+ * d_alb 16-byte aligned; d_var_out nullable; the scratch is the scene's, as there. */
+int pt_denoise_mean_async(pt_scene* scene, const float* d_c, const float* d_var, uint32_t w, uint32_t h, size_t row_pitch,
+                          const float* d_geo, const float* d_alb, uint32_t feature_frames, const pt_denoise_params* p,
+                          float* d_out, float* d_var_out, void* stream);
+/* The same on dense host buffers (var_out nullable).  Blocking. */
+int pt_denoise_mean(pt_scene* scene, const float* c, const float* var, uint32_t w, uint32_t h, const float* geo,
+                    const float* alb, uint32_t feature_frames, const pt_denoise_params* p, float* out, float* var_out);
+
+/* Temporal accumulation: the temporal stage of SVGF (Schied et al. 2017) for a static
+ * scene.  What one image learned is carried to the next camera: the history of the pixel's surface point is
+ * looked up where the PREVIOUS camera saw it and blended with the current step.
+ *
+ * The state is three planes of [h][w][4] f32, 16-byte aligned:
+ *   hist = (c.r, c.g, c.b, N)   the accumulated mean radiance per sample; N: the history length in steps
+ *                               (a float; 0: none)
+ *   mom  = (q.r, q.g, q.b, 0)   the accumulated mean of the squared per-sample radiance
+ *   gbuf = (n.x, n.y, n.z, Z)   this step's mean shading normal (not renormalised) and mean hit distance;
+ *                               Z = 0: the pixel saw no hit
+ * A step reads the previous set and writes a new one; the two sets must not overlap. */
+typedef struct {
+    float alpha;       /* the blend's floor, in (0, 1] */
+    float normal_min;  /* a tap's least dot(N_cur, n_tap) */
+    float depth_tol;   /* a tap's largest |Z_tap - Ze| / Ze, > 0 */
+    float max_history; /* N is clamped to this, >= 1 */
+} pt_temporal_params;                               /* 16 B; all finite */
+void pt_temporal_defaults(pt_temporal_params* p); /* 0.2, 0.9, 0.1, 64 */
+
+/* One step over the whole w x h image of meta_cur (w = meta[0], h = meta[1] of both metas, else
+ * PT_ERR_INVALID).  d_accum, d_m2 [h][w][3]: the sums of an n-frame moments render from zero, n >= 1;
+ * d_geo, d_alb [h][w][4]: pt_render_features' sums (16-byte aligned).  meta_prev and the three d_*_prev
+ * planes: the previous step's camera and state, ALL NULL for a first step (a mixed set is PT_ERR_INVALID).
+ * Outputs: the three new planes and, both nullable, d_out [h][w][3] = c' and d_var [h][w], the variance of
+ * the accumulated mean.  Rows of ALL buffers are row_pitch pixels apart (>= w).  p NULL =
+ * pt_temporal_defaults.  The scene's camera model (pt_scene_set_camera) is not consulted: the warp is the
+ * pinhole's.  Asynchronous on `stream`; no scratch.
+ *
+ * Every operation is f32, rounded once, in the order written; fmaf where written and nowhere else; / and
+ * sqrtf correctly rounded.  Per pixel (x, y), fn = (float)n:
+ *  1. c_k = acc / fn, q_k = m2 / fn per channel; hits = alb.w;
+ *     hits > 0: Ncur = geo.xyz / hits, Z = geo.w / hits; else Ncur = 0, Z = 0.  gbuf' = (Ncur, Z).
+ *  2. With cur's W, H, inv_w, inv_h, aspect, focal, cam, M = cam_to_world (meta[28..43], column-major) and
+ *     vhh = its view_half_h (pt_selftest_view_half_h), camera_ray's chain at the pixel's centre:
+ *       norm_x = fmaf((float)x + 0.5f, inv_w, -0.5f);  norm_y = fmaf(((H - 1) - (float)y) + 0.5f, inv_h, -0.5f)
+ *       vx = (vhh * aspect) * norm_x;  vy = vhh * norm_y;  pz = -focal
+ *       p_k = fmaf(M[12+k], 1, fmaf(M[8+k], pz, fmaf(M[4+k], vy, M[k] * vx)))   k = 0..3
+ *       d_k = p_k - cam[k];  len = sqrtf(fmaf(d_3, d_3, fmaf(d_2, d_2, fmaf(d_1, d_1, d_0 * d_0))))
+ *       P_k = fmaf(Z, d_k / len, cam[k])   k = 0..2
+ *  3. With prev's V = world_to_cam (meta[12..27], column-major), focal', aspect', vhh', cam':
+ *       pc_k = fmaf(V[12+k], 1, fmaf(V[8+k], P_2, fmaf(V[4+k], P_1, V[k] * P_0)))   k = 0..2
+ *       zc = -pc_2;  vx' = (pc_0 * focal') / zc;  vy' = (pc_1 * focal') / zc
+ *       u = ((vx' / (vhh' * aspect')) + 0.5f) * W - 0.5f
+ *       v = (H - 1) - (((vy' / vhh') + 0.5f) * H - 0.5f)
+ *       e_k = P_k - cam'[k];  Ze = sqrtf(fmaf(e_2, e_2, fmaf(e_1, e_1, e_0 * e_0)))
+ *  4. fu = floorf(u), fx = u - fu, x0 = (int)fu; likewise fv, fy, y0.  Taps (x0 + i, y0 + j), j = 0, 1
+ *     outermost, i = 0, 1 inside, weight (i ? fx : 1 - fx) * (j ? fy : 1 - fy).  With (c_q, N_q) = hist_prev,
+ *     q_q = mom_prev, (n_q, Z_q) = gbuf_prev at the tap, it is valid iff it lies inside the image and
+ *       N_q > 0  &&  Z_q > 0  &&  |Z_q - Ze| <= depth_tol * Ze
+ *           &&  (Ncur.x * n_q.x + Ncur.y * n_q.y) + Ncur.z * n_q.z >= normal_min
+ *     For the valid taps in order: sw += wgt; sc += wgt * c_q; sq += wgt * q_q (per channel); sn += wgt * N_q.
+ *  5. No history — c' = c_k, q' = q_k, N' = 1, a = 1 — unless ALL of: the previous set is given; Z > 0;
+ *     zc > 0; u > -1 && u < W && v > -1 && v < H (tested in float before any conversion to an integer);
+ *     sw > 1e-6f.  Every comparison is written so that a NaN means no history, or an invalid tap.
+ *  6. Otherwise c_h = sc / sw, q_h = sq / sw, t = sn / sw + 1, N' = t < max_history ? t : max_history,
+ *     r = 1 / N', a = alpha > r ? alpha : r,  c' = c_h + a * (c_k - c_h),  q' = q_h + a * (q_k - q_h).
+ *     hist' = (c', N'), mom' = (q', 0).
+ *  7. out = c';  d_c = q'_c - c'_c * c'_c, v_c = d_c > 0 ? d_c : 0;  var = (((v_r + v_g) + v_b) * a) / fn, a
+ *     NaN stored as 0: the variance of the accumulated mean with 1 / a steps of n samples as the effective
+ *     count.
+ * Inputs are assumed finite; other inputs do not fault.  The result does not depend on the launch. */
+int pt_reproject_async(pt_scene* scene, const float* d_accum, const float* d_m2, uint32_t n, const float* d_geo,
+                       const float* d_alb, const float meta_cur[48], const float* meta_prev, const float* d_hist_prev,
+                       const float* d_mom_prev, const float* d_gbuf_prev, uint32_t w, uint32_t h, size_t row_pitch,
+                       const pt_temporal_params* p, float* d_hist, float* d_mom, float* d_gbuf, float* d_out, float* d_var,
+                       void* stream);
+/* The same on dense host buffers.  Blocking. */
+int pt_reproject(pt_scene* scene, const float* accum, const float* m2, uint32_t n, const float* geo, const float* alb,
+                 const float meta_cur[48], const float* meta_prev, const float* hist_prev, const float* mom_prev,
+                 const float* gbuf_prev, uint32_t w, uint32_t h, const pt_temporal_params* p, float* hist, float* mom,
+                 float* gbuf, float* out, float* var);
+
+/* The state on the device between calls: two sets of the three planes for a w x h image, the previous
+ * step's meta, and the step's working buffers, all counted in the scene's device_bytes while held.  One
+ * history per camera path; calls on one scene stay in stream order, as for pt_denoise.  A history whose scene
+ * was destroyed first has lost its buffers: every call on it but pt_history_destroy returns PT_ERR_INVALID. */
+typedef struct pt_history pt_history;
+int pt_history_create(pt_scene* scene, uint32_t w, uint32_t h, pt_history** hist_out);
+int pt_history_reset(pt_history* hist); /* the next step is a first step */
+void pt_history_destroy(pt_history* hist);
+/* One step, in order: a moments render of frames frame0 + i*stride (i < nframes, nframes >= 1) of the whole
+ * image of meta from zero; the guide buffers of frames frame0 .. frame0 + feature_frames - 1 (stride 1,
+ * feature_frames >= 1); pt_reproject_async against the stored meta and planes (tparams NULL = the
+ * defaults), after which the two sets swap; with dparams, pt_denoise_mean_async of the step's out and var on
+ * the step's guides (dparams NULL: unfiltered); the device tone map with sample_runs = 1 of the filtered
+ * (or accumulated) mean; the copies.  Outputs, all nullable, on the host: mean_out [h][w][3] and var_out
+ * [h][w] the filtered (or accumulated) mean and its variance, rgba_out [h][w][4], history_len_out [h][w]
+ * the new N.  counters: nullable, the render's plus the guide pass's.  meta's W, H must be the history's.
+ * Blocking.  The sets swap only when the whole step has succeeded: a step that fails leaves the history as the
+ * step before left it. */
+int pt_history_step(pt_history* hist, const float meta[48], uint32_t frame0, uint32_t nframes, uint32_t frame_stride,
+                    int max_depth, int mode, uint32_t feature_frames, const pt_temporal_params* tparams,
+                    const pt_denoise_params* dparams, float* mean_out, float* var_out, uint8_t* rgba_out,
+                    float* history_len_out, pt_counters* counters);
+
 /* Ray queries: the traversal itself, for rays the caller supplies — what does this ray hit, is this
  * segment blocked.  The answers are the reference's intersect() (src/wgsl-util/intersection-logic.wgsl),
  * bit for bit, whatever kernel, grid or option computes them.
