@@ -89,6 +89,8 @@ int fail(int code, const std::string& msg) {
     return code;
 }
 
+void mark_hip_touched() { g_hip_touched = true; }
+
 int opt_index(const char* name) {
     for (int i = 0; i < kNumOpts; ++i)
         if (!std::strcmp(name, kOptSpecs[i].name)) return i;

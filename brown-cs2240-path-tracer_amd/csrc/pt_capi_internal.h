@@ -16,6 +16,8 @@
 namespace pt {
 
 int fail(int code, const std::string& msg);  // sets the thread's pt_last_error (pt_capi.hip)
+// a call is about to start the HIP runtime: pt_set_hw_queues comes too late from now on (pt_capi.hip)
+void mark_hip_touched();
 
 #define HIP_TRY(expr)                                                                                      \
     do {                                                                                                  \
@@ -175,6 +177,9 @@ struct pt_scene {
     // frees their buffers and orphans them, so a later call on one is an error, not a fault
     pt::Scratch<float> d_temporal{&info.device_bytes};
     std::vector<pt_history*> histories;
+    // a scene made by pt_scene_create_mesh: its packed tree inside d_mem (bytes from the base, floats)
+    bool mesh_built = false;
+    size_t packed_off = 0, packed_len = 0;
 };
 
 namespace pt {

@@ -27,6 +27,9 @@ enum KernelId : int {
     KID_TONEMAP, KID_WF_STEP, KID_WF_LEAF, KID_NOISE_TILES, KID_TILE_MEAN, KID_FEATURES, KID_DENOISE_PREPARE, KID_ATROUS,
     KID_QUERY_HITS, KID_QUERY_OCCLUDED, KID_CAMERA_RAYS, KID_CAMERA_SEEDS, KID_GATHER_RAYS, KID_REPROJECT,
     KID_DENOISE_PREPARE_MEAN,
+    // the device scene builder's stages (pt_build.hip; a stage's launches share its id)
+    KID_BUILD_BOUNDS, KID_BUILD_KEYS, KID_BUILD_SORT, KID_BUILD_KARRAS, KID_BUILD_DEPTH, KID_BUILD_LEVEL, KID_BUILD_OFFSETS,
+    KID_BUILD_EMIT,
     KID_COUNT
 };
 inline const char* kernel_name(int k) {
@@ -35,7 +38,9 @@ inline const char* kernel_name(int k) {
                                              "k_wf_step",      "k_wf_leafpass",     "k_noise_tiles", "k_tile_mean",
                                              "k_features",     "k_denoise_prepare", "k_atrous",      "k_query_hits",
                                              "k_query_occluded", "k_camera_rays", "k_camera_seeds", "k_gather_rays",
-                                             "k_reproject",    "k_denoise_prepare_mean"};
+                                             "k_reproject",    "k_denoise_prepare_mean",
+                                             "k_build_bounds", "k_build_keys", "k_build_sort", "k_build_karras",
+                                             "k_build_depth",  "k_build_level", "k_build_offsets", "k_build_emit"};
     return (k >= 0 && k < KID_COUNT) ? n[k] : "?";
 }
 struct KernelProfiler {

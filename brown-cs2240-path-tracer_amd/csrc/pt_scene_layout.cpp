@@ -436,6 +436,19 @@ int build_layout(const float* tri, size_t tri_len, const float* bvh, size_t bvh_
     return build_lights(in, L, err);
 }
 
+int build_mesh_tables(const float* tri, size_t tri_len, HostLayout& L, std::string& err) {
+    if (tri_len < 16 || tri_len > (size_t)INT32_MAX) return fail(err, "triangle_data shorter than its 16-float header");
+    const float nverts_f = tri[0], nobj_f = tri[1];
+    if (!(nverts_f >= 0 && nverts_f == std::floor(nverts_f)) || !(nobj_f >= 1 && nobj_f == std::floor(nobj_f)))
+        return fail(err, "bad vertex/object counts in triangle_data header");
+    const Input in{tri, nullptr, tri_len, 0, (int64_t)nverts_f, (int64_t)nobj_f, wgsl_i32(tri[2]), wgsl_i32(tri[4])};
+    if (in.v_start < 0 || in.v_start + 3 * in.nverts > (int64_t)tri_len) return fail(err, "vertex section out of range");
+    if (in.m_start < 0 || in.m_start + 15 * in.nobj > (int64_t)tri_len) return fail(err, "material section out of range");
+    L.info.vertices = (uint32_t)in.nverts;
+    build_materials(in, L);
+    return build_lights(in, L, err);
+}
+
 ScenePlan plan_sections(const HostLayout& L, size_t counters_bytes) {
     ScenePlan p{};
     size_t end = 0;  // the end of the section before, with its minimum size

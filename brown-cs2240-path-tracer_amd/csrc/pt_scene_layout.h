@@ -56,6 +56,11 @@ struct HostLayout {
 int build_layout(const float* tri, size_t tri_len, const float* bvh, size_t bvh_len, const LayoutOptions& opt,
                  HostLayout& L, std::string& err);
 
+// build_layout's materials and light table alone (O(objects + emitters)), for a scene whose tree is
+// built elsewhere (pt_scene_create_mesh): the header checked as build_layout checks it, then L.mats,
+// L.lights, L.ntri and their pt_scene_info fields.  PT_OK, or PT_ERR_SCENE with the reason in err.
+int build_mesh_tables(const float* tri, size_t tri_len, HostLayout& L, std::string& err);
+
 // The scene's device allocation: its sections in upload order.  Those up to SEC_BFNARROW form the
 // span kernels stage into LDS ([0, span_end), 16-byte alignment inside it); the counters block
 // follows at off_counters; everything starts on 256 bytes otherwise.

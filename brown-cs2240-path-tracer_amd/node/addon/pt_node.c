@@ -156,22 +156,8 @@ static napi_value js_device_count(napi_env env, napi_callback_info info) {
     return r;
 }
 
-/* sceneCreate(triangle_data: Float32Array, bvh_data: Float32Array, device: number) -> external */
-static napi_value js_scene_create(napi_env env, napi_callback_info info) {
-    size_t argc = 3;
-    napi_value argv[3];
-    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-    float *tri, *bvh;
-    size_t tl, bl;
-    int32_t dev = 0;
-    if (argc < 2 || !get_f32(env, argv[0], &tri, &tl) || !get_f32(env, argv[1], &bvh, &bl) ||
-        (argc > 2 && !get_i32(env, argv[2], &dev))) {
-        napi_throw_type_error(env, NULL, "sceneCreate(Float32Array triangle_data, Float32Array bvh_data, device?)");
-        return NULL;
-    }
-    pt_scene* s = NULL;
-    int rc = pt_scene_create(tri, tl, bvh, bl, dev, &s);
-    if (rc) return throw_pt(env, rc);
+/* a new scene as the external the other calls take; the scene is destroyed if that fails */
+static napi_value wrap_scene(napi_env env, pt_scene* s) {
     scene_box* b = (scene_box*)calloc(1, sizeof(scene_box));
     if (!b) { pt_scene_destroy(s); napi_throw_error(env, NULL, "out of memory"); return NULL; }
     b->s = s;
@@ -189,6 +175,119 @@ static napi_value js_scene_create(napi_env env, napi_callback_info info) {
         napi_adjust_external_memory(env, (int64_t)si.device_bytes, &adj);
     }
     return ext;
+}
+
+/* sceneCreate(triangle_data: Float32Array, bvh_data: Float32Array, device: number) -> external */
+static napi_value js_scene_create(napi_env env, napi_callback_info info) {
+    size_t argc = 3;
+    napi_value argv[3];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    float *tri, *bvh;
+    size_t tl, bl;
+    int32_t dev = 0;
+    if (argc < 2 || !get_f32(env, argv[0], &tri, &tl) || !get_f32(env, argv[1], &bvh, &bl) ||
+        (argc > 2 && !get_i32(env, argv[2], &dev))) {
+        napi_throw_type_error(env, NULL, "sceneCreate(Float32Array triangle_data, Float32Array bvh_data, device?)");
+        return NULL;
+    }
+    pt_scene* s = NULL;
+    int rc = pt_scene_create(tri, tl, bvh, bl, dev, &s);
+    if (rc) return throw_pt(env, rc);
+    return wrap_scene(env, s);
+}
+
+/* the optional {maxLeaf, isolateEmitters} of the LBVH calls over pt_build_defaults; false: a type error is pending */
+static bool get_build_params(napi_env env, napi_value v, pt_build_params* prm) {
+    pt_build_defaults(prm);
+    napi_valuetype t = napi_undefined;
+    if (v && napi_typeof(env, v, &t) != napi_ok) return false;
+    if (t == napi_undefined || t == napi_null) return true;
+    bool has = false;
+    napi_value f;
+    if (t != napi_object) goto bad;
+    if (napi_has_named_property(env, v, "maxLeaf", &has) == napi_ok && has) {
+        int32_t m = 0;
+        if (napi_get_named_property(env, v, "maxLeaf", &f) != napi_ok || !get_i32(env, f, &m) || m < 0) goto bad;
+        prm->max_leaf = (uint32_t)m;
+    }
+    if (napi_has_named_property(env, v, "isolateEmitters", &has) == napi_ok && has) {
+        bool iso = true;
+        if (napi_get_named_property(env, v, "isolateEmitters", &f) != napi_ok || napi_get_value_bool(env, f, &iso) != napi_ok) goto bad;
+        prm->isolate_emitters = iso ? 1 : 0;
+    }
+    return true;
+bad:
+    napi_throw_type_error(env, NULL, "build options: { maxLeaf?: number, isolateEmitters?: boolean }");
+    return false;
+}
+
+/* sceneCreateMesh(triangle_data: Float32Array[, {maxLeaf, isolateEmitters}[, device]]) -> external: the
+ * scene's tree (the LBVH of pt_hip.h) and records built on the device, pt_scene_create_mesh */
+static napi_value js_scene_create_mesh(napi_env env, napi_callback_info info) {
+    size_t argc = 3;
+    napi_value argv[3];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    float* tri;
+    size_t tl;
+    int32_t dev = 0;
+    if (argc < 1 || !get_f32(env, argv[0], &tri, &tl) || (argc > 2 && !get_i32(env, argv[2], &dev))) {
+        napi_throw_type_error(env, NULL, "sceneCreateMesh(Float32Array triangle_data, options?, device?)");
+        return NULL;
+    }
+    pt_build_params prm;
+    if (!get_build_params(env, argc > 1 ? argv[1] : NULL, &prm)) return NULL;
+    pt_scene* s = NULL;
+    int rc = pt_scene_create_mesh(tri, tl, &prm, dev, &s);
+    if (rc) return throw_pt(env, rc);
+    return wrap_scene(env, s);
+}
+
+/* sceneExportBvh(scene) -> Float32Array: the packed tree of a scene made by sceneCreateMesh */
+static napi_value js_scene_export_bvh(napi_env env, napi_callback_info info) {
+    size_t argc = 1;
+    napi_value argv[1];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    pt_scene* s = argc ? get_scene(env, argv[0]) : NULL;
+    if (!s) {
+        if (!pending_exception(env)) napi_throw_type_error(env, NULL, "sceneExportBvh(scene)");
+        return NULL;
+    }
+    size_t len = 0;
+    int rc = pt_scene_export_bvh(s, NULL, 0, &len);
+    if (rc) return throw_pt(env, rc);
+    napi_value buf, arr;
+    void* data = NULL;
+    CHECK_NAPI(env, napi_create_arraybuffer(env, len * sizeof(float), &data, &buf));
+    rc = pt_scene_export_bvh(s, (float*)data, len, &len);
+    if (rc) return throw_pt(env, rc);
+    CHECK_NAPI(env, napi_create_typedarray(env, napi_float32_array, len, buf, 0, &arr));
+    return arr;
+}
+
+/* bvhBuildLbvh(triangle_data: Float32Array[, {maxLeaf, isolateEmitters}]) -> Float32Array bvh_data: the same
+ * tree built on the host, pt_bvh_build_lbvh */
+static napi_value js_bvh_build_lbvh(napi_env env, napi_callback_info info) {
+    size_t argc = 2;
+    napi_value argv[2];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    float* tri;
+    size_t tl;
+    if (argc < 1 || !get_f32(env, argv[0], &tri, &tl)) {
+        napi_throw_type_error(env, NULL, "bvhBuildLbvh(Float32Array triangle_data, options?)");
+        return NULL;
+    }
+    pt_build_params prm;
+    if (!get_build_params(env, argc > 1 ? argv[1] : NULL, &prm)) return NULL;
+    size_t len = 0;
+    int rc = pt_bvh_build_lbvh(tri, tl, &prm, NULL, 0, &len);
+    if (rc) return throw_pt(env, rc);
+    napi_value buf, arr;
+    void* data = NULL;
+    CHECK_NAPI(env, napi_create_arraybuffer(env, len * sizeof(float), &data, &buf));
+    rc = pt_bvh_build_lbvh(tri, tl, &prm, (float*)data, len, &len);
+    if (rc) return throw_pt(env, rc);
+    CHECK_NAPI(env, napi_create_typedarray(env, napi_float32_array, len, buf, 0, &arr));
+    return arr;
 }
 
 /* sceneDestroy(scene): free the scene's device memory now (the handle becomes unusable); throws
@@ -1472,6 +1571,9 @@ static napi_value init(napi_env env, napi_value exports) {
         {"profileEnable", NULL, js_profile_enable, NULL, NULL, NULL, napi_enumerable, NULL},
         {"profileRead", NULL, js_profile_read, NULL, NULL, NULL, napi_enumerable, NULL},
         {"bvhBuild", NULL, js_bvh_build, NULL, NULL, NULL, napi_enumerable, NULL},
+        {"bvhBuildLbvh", NULL, js_bvh_build_lbvh, NULL, NULL, NULL, napi_default, NULL},
+        {"sceneCreateMesh", NULL, js_scene_create_mesh, NULL, NULL, NULL, napi_default, NULL},
+        {"sceneExportBvh", NULL, js_scene_export_bvh, NULL, NULL, NULL, napi_default, NULL},
         {"sceneSetVertexNormals", NULL, js_scene_set_vertex_normals, NULL, NULL, NULL, napi_enumerable, NULL},
         {"sceneSetCamera", NULL, js_scene_set_camera, NULL, NULL, NULL, napi_default, NULL},
         {"reproject", NULL, js_reproject, NULL, NULL, NULL, napi_default, NULL},

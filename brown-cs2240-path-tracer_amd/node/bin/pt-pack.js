@@ -8,6 +8,8 @@
 // --native-bvh builds the BVH with the library's C++ builder (pt_bvh_build, byte-identical).
 // --all-meshes packs every primitive of the scene into one (the reference packs the first only).
 // --bvh sah builds the fast binned-SAH tree (same layout, not the reference's topology).
+// --bvh lbvh [--max-leaf N] builds the linear BVH of include/pt_hip.h (pt_bvh_build_lbvh): the tree a scene made
+// from the mesh alone builds on the device.
 const fs = require('fs');
 const path = require('path');
 const host = require('..');
@@ -26,7 +28,11 @@ function main(argv) {
     const [src, out] = args._;
     const opts = { web_root: args.web_root, quiet: true, native_bvh: !!args.native_bvh, all_meshes: !!args.all_meshes,
                    bvh: args.bvh || 'reference' };
-    if (opts.bvh !== 'reference' && opts.bvh !== 'sah') { console.error('--bvh reference|sah'); process.exit(2); }
+    if (!['reference', 'sah', 'lbvh'].includes(opts.bvh)) { console.error('--bvh reference|sah|lbvh'); process.exit(2); }
+    if (args.max_leaf !== undefined) {
+        if (opts.bvh !== 'lbvh' || !/^[1-8]$/.test(String(args.max_leaf))) { console.error('--bvh lbvh --max-leaf 1..8'); process.exit(2); }
+        opts.max_leaf = parseInt(args.max_leaf);
+    }
     let loaded;
     if (src.endsWith('.ini')) loaded = host.load_scene_from_ini(src, opts);
     else {

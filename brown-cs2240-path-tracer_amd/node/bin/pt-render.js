@@ -40,6 +40,8 @@
 //  reprojected into its camera; alpha in (0, 1] is the blend's floor, default the library's 0.2.  The sheet holds the
 //  accumulated tiles, with --denoise [iters] [--feature-frames N] filtered by the a-trous denoiser on each view's guides;
 //  not with --window, --counters 1, --camera, --projection or --dump-accum)
+// [--bvh device] (no tree is built or packed here: the scene builds the linear BVH of include/pt_hip.h on the GPU from
+//  the mesh alone, pt_scene_create_mesh; every other option as usual)
 // [--dump-rays FILE] (with equirect or ortho: the rays, 8 f32 each, then the seeds, one u32 each, as made)
 // [--dump-accum FILE] (with equirect or ortho: the accumulator, 3 f32 per pixel, before the tone map)
 const fs = require('fs');
@@ -54,6 +56,7 @@ async function main(argv) {
         else args._.push(argv[i]);
     }
     if (!args._.length) { console.error('usage: pt-render.js <scene.ini> [options]'); process.exit(2); }
+    if (args.bvh !== undefined && args.bvh !== 'device') { console.error('usage: pt-render.js <scene.ini> --bvh device'); process.exit(2); }
     let window = null, rects = null;
     if (args.window !== undefined) {
         try {
@@ -122,7 +125,7 @@ async function main(argv) {
         process.exit(2);
     }
     const t0 = Date.now();
-    const s = host.load_scene_from_ini(args._[0], { web_root: args.web_root, quiet: true });
+    const s = host.load_scene_from_ini(args._[0], { web_root: args.web_root, quiet: true, bvh: args.bvh === 'device' ? 'device' : undefined });
     if (args.spp) s.scene_description.Settings.samplesPerPixel = parseInt(args.spp);
     let camera = null;
     if (args.camera !== undefined) {
@@ -156,7 +159,7 @@ async function turn(args, s, turntable, camera, t0) {
     const views = cams.map((c, k) => ({ meta: host.make_meta(s.screenDimension, c, s.scene_description, 0), camera, dst: dsts[k], frame0: 0 }));
     const t1 = Date.now();
     const pt = host.native();
-    const scene = pt.sceneCreate(s.primitive_data[0].triangle_data, s.primitive_data[0].bvh_data, parseInt(args.device || '0'));
+    const scene = host.scene_of(pt, s.primitive_data[0], parseInt(args.device || '0'));
     let r;
     try {
         if (args.vertex_normals === '1') pt.sceneSetVertexNormals(scene, true);
@@ -183,7 +186,7 @@ async function turnTemporal(args, s, turntable, temporal, denoise, t0) {
     const { dsts, atlasW, atlasH } = host.view_atlas(cams.map(() => [W, H]), turntable.cols);
     const t1 = Date.now();
     const pt = host.native();
-    const scene = pt.sceneCreate(s.primitive_data[0].triangle_data, s.primitive_data[0].bvh_data, parseInt(args.device || '0'));
+    const scene = host.scene_of(pt, s.primitive_data[0], parseInt(args.device || '0'));
     const rgba = new Uint8ClampedArray(atlasW * atlasH * 4);
     let history = null;
     try {
@@ -216,7 +219,7 @@ function hash1u(n) {
 // --projection equirect|ortho: the rays and seeds the header documents, through queryRadiance
 function project(args, projection) {
     const t0 = Date.now();
-    const s = host.load_scene_from_ini(args._[0], { web_root: args.web_root, quiet: true });
+    const s = host.load_scene_from_ini(args._[0], { web_root: args.web_root, quiet: true, bvh: args.bvh === 'device' ? 'device' : undefined });
     if (args.spp) s.scene_description.Settings.samplesPerPixel = parseInt(args.spp);
     const [W, H] = s.screenDimension;
     const spp = s.scene_description.Settings.samplesPerPixel;
@@ -246,7 +249,7 @@ function project(args, projection) {
     const rays = host.unitRays(o, d);
     const t1 = Date.now();
     const pt = host.native();
-    const scene = pt.sceneCreate(s.primitive_data[0].triangle_data, s.primitive_data[0].bvh_data, parseInt(args.device || '0'));
+    const scene = host.scene_of(pt, s.primitive_data[0], parseInt(args.device || '0'));
     let accum;
     try {
         if (args.vertex_normals === '1') pt.sceneSetVertexNormals(scene, true);
@@ -275,12 +278,12 @@ function pick(args) {
         process.exit(2);
     }
     const [x, y] = parts.map(Number);
-    const s = host.load_scene_from_ini(args._[0], { web_root: args.web_root, quiet: true });
+    const s = host.load_scene_from_ini(args._[0], { web_root: args.web_root, quiet: true, bvh: args.bvh === 'device' ? 'device' : undefined });
     const [W, H] = s.screenDimension;
     if (x >= W || y >= H) { console.error(`--pick ${x},${y}: outside the ${W}x${H} image`); process.exit(2); }
     const pt = host.native();
     const meta = host.make_meta(s.screenDimension, s.camera_data, s.scene_description, 0);
-    const scene = pt.sceneCreate(s.primitive_data[0].triangle_data, s.primitive_data[0].bvh_data, parseInt(args.device || '0'));
+    const scene = host.scene_of(pt, s.primitive_data[0], parseInt(args.device || '0'));
     try {
         if (args.vertex_normals === '1') pt.sceneSetVertexNormals(scene, true);
         const ray = host.cameraRays(scene, meta, 0, [x, y, 1, 1]);
@@ -304,10 +307,10 @@ function gather(args) {
         console.error('usage: pt-render.js <scene.ini> --irradiance x,y,z,nx,ny,nz | --probe x,y,z [--samples N] [--seed S]: ' + text);
         process.exit(2);
     }
-    const s = host.load_scene_from_ini(args._[0], { web_root: args.web_root, quiet: true });
+    const s = host.load_scene_from_ini(args._[0], { web_root: args.web_root, quiet: true, bvh: args.bvh === 'device' ? 'device' : undefined });
     const meta = host.make_meta(s.screenDimension, s.camera_data, s.scene_description, 0);
     const pt = host.native();
-    const scene = pt.sceneCreate(s.primitive_data[0].triangle_data, s.primitive_data[0].bvh_data, parseInt(args.device || '0'));
+    const scene = host.scene_of(pt, s.primitive_data[0], parseInt(args.device || '0'));
     try {
         if (args.vertex_normals === '1') pt.sceneSetVertexNormals(scene, true);
         const points = host.gatherPoints(v.slice(0, 3), probe ? [0, 0, 0] : v.slice(3, 6), [seed]);

@@ -10,7 +10,7 @@ const { mat4_rot_axis, bounds_of_vec3, chunk_into_3, bounds_bounds_intersection_
 const geometry = require('./lib/geometry');
 const { xml2js } = require('./lib/xml');
 const scene = require('./lib/scene');
-const { programEntry, make_meta, check_window, check_rects, MODE, renderViews, view_atlas, turntable_cameras } = require('./lib/program-entry');
+const { programEntry, make_meta, check_window, check_rects, MODE, renderViews, view_atlas, turntable_cameras, scene_of } = require('./lib/program-entry');
 const { encode_png } = require('./lib/png');
 const addon = require('./lib/addon');
 
@@ -130,7 +130,7 @@ module.exports = {
     parse_scene_xml: scene.parse_scene_xml, pack_primitive: scene.pack_primitive,
     screen_dimension: scene.screen_dimension, load_scene_from_ini: scene.load_scene_from_ini,
     load_scene_xml_file: scene.load_scene_xml_file,
-    programEntry, make_meta, check_window, check_rects, MODE, encode_png, native: addon.load,
+    programEntry, make_meta, check_window, check_rects, MODE, encode_png, native: addon.load, scene_of,
     renderViews, view_atlas, turntable_cameras,
     queryHits, queryOccluded, cameraRays, queryRadiance, cameraSeeds, unitRays,
     gather, gatherRays, gatherPoints,

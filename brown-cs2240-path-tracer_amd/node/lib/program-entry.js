@@ -48,11 +48,20 @@ function check_rects(rects) {
     });
 }
 
+/** The native scene of one packed primitive: from its tree (sceneCreate), or — bvh_data null or absent, as
+ *  load_scene_* leaves it under bvh 'device' — built on the device from the mesh alone (sceneCreateMesh;
+ *  build = {maxLeaf, isolateEmitters} over the library's defaults). */
+function scene_of(pt, primitive, device, build) {
+    return primitive.bvh_data ? pt.sceneCreate(primitive.triangle_data, primitive.bvh_data, device)
+                              : pt.sceneCreateMesh(primitive.triangle_data, build || null, device);
+}
+
 /**
  * programEntry(screenDimension, primitive_data, camera_data, scene_description, options?)
  *   -> Promise<{accum: Float32Array(W*H*3), sample_runs, rgba: Uint8ClampedArray(W*H*4), counters, scene_info}>
  * options: {device=0, devices=[...] (several GPUs: pt_render_multi), maxDepth=16, mode='auto', frame0=0, chunk=spp,
  *           onFrames(done, total), imageOnly=false,
+ *           build={maxLeaf=4, isolateEmitters=true} (a primitive without bvh_data: its tree is built on the device),
  *           vertexNormals=false (the reference's commented-out smooth-normal branch; changes results),
  *           camera={model: 'thin_lens'|'ortho'|'equirect'|'pinhole', lensRadius=0, focusDistance=1} (a lens camera
  *           evaluated on the device, pt_scene_set_camera: combines with every other option),
@@ -85,8 +94,7 @@ async function programEntry(screenDimension, primitive_data, camera_data, scene_
     if (o.denoise && (win || rects || o.counters || o.imageOnly || o.chunk || o.onFrames || (o.devices && o.devices.length > 1)))
         throw Error('denoise: not with window, rects, counters, imageOnly, chunk, onFrames or several devices');
     if (o.devices && o.devices.length > 1) return programEntryMulti(pt, meta, W, H, primitive_data, scene_description, o, mode);
-    const scene = pt.sceneCreate(primitive_data[0].triangle_data, primitive_data[0].bvh_data,
-                                 o.devices && o.devices.length ? o.devices[0] : o.device);
+    const scene = scene_of(pt, primitive_data[0], o.devices && o.devices.length ? o.devices[0] : o.device, o.build);
     // the scene's device memory (scene + wavefront state) is released when the call ends, not
     // when V8 happens to collect the handle
     try {
@@ -131,7 +139,7 @@ async function programEntry(screenDimension, primitive_data, camera_data, scene_
 async function programEntryMulti(pt, meta, W, H, primitive_data, scene_description, o, mode) {
     const scenes = [];
     try {
-        for (const d of o.devices) scenes.push(pt.sceneCreate(primitive_data[0].triangle_data, primitive_data[0].bvh_data, d));
+        for (const d of o.devices) scenes.push(scene_of(pt, primitive_data[0], d, o.build));
         if (o.vertexNormals) for (const s of scenes) pt.sceneSetVertexNormals(s, true);
         if (o.camera) for (const s of scenes) pt.sceneSetCamera(s, o.camera);
         const spp = scene_description.Settings.samplesPerPixel;
@@ -216,4 +224,4 @@ function turntable_cameras(camera_data, n) {
     return out;
 }
 
-module.exports = { programEntry, make_meta, check_window, check_rects, MODE, renderViews, view_atlas, turntable_cameras };
+module.exports = { programEntry, make_meta, check_window, check_rects, MODE, renderViews, view_atlas, turntable_cameras, scene_of };

@@ -122,6 +122,16 @@ function pack_group(intermediate, opts) {
     // the fast binned-SAH tree (pt_bvh_build_sah2) in the same layout — not the reference's topology —
     // with the emitters (sum(Ke) > 0, program-raymarch.wgsl:136) in a leaf under the root, where the
     // exit-distance pruning of the unchanged traversal cannot hide them
+    // bvh 'lbvh': the linear BVH of include/pt_hip.h from the packed buffer alone (pt_bvh_build_lbvh; opts.max_leaf,
+    // opts.isolate_emitters over its defaults); bvh 'device': no tree here — the scene builds the same one on the
+    // GPU (sceneCreateMesh), bvh_data stays null
+    if (opts && opts.bvh === 'device') return { triangle_data: packed_array, bvh_data: null, bounds: bvh_bounds };
+    if (opts && opts.bvh === 'lbvh') {
+        const build = {};
+        if (opts.max_leaf !== undefined) build.maxLeaf = opts.max_leaf;
+        if (opts.isolate_emitters !== undefined) build.isolateEmitters = !!opts.isolate_emitters;
+        return { triangle_data: packed_array, bvh_data: require('./addon').load().bvhBuildLbvh(packed_array, build), bounds: bvh_bounds };
+    }
     if (opts && (opts.native_bvh || opts.bvh === 'sah')) {
         const tris = new Int32Array(bvh_objects.length * 4);
         bvh_objects.forEach((o, t) => tris.set(o.obj, 4 * t));
@@ -165,7 +175,8 @@ function load_scene_xml_file(scene_path, opts) {
     const web_root = opts.web_root || path.resolve(path.dirname(scene_path), '..');
     const load_file = opts.load_file || make_loader(web_root);
     const { camera_data, final_primitives } = parse_scene_xml(load_file(scene_path));
-    const popts = { quiet: opts.quiet !== false, native_bvh: !!opts.native_bvh, bvh: opts.bvh };
+    const popts = { quiet: opts.quiet !== false, native_bvh: !!opts.native_bvh, bvh: opts.bvh, max_leaf: opts.max_leaf,
+                    isolate_emitters: opts.isolate_emitters };
     const parse = (p) => {
         if (!p.data) throw Error('mesh primitive missing its data');
         const obj_data = load_file(p.data.path);

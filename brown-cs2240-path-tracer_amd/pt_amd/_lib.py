@@ -18,7 +18,8 @@ _BUILD_SRCS = ["pt_kernels.hip", "pt_wavefront.hip", "pt_wf_source.hip", "pt_wf_
                "pt_device.h", "pt_path.h", "pt_kernels.h", "../../include/pt_hip.h", "pt_bvh.cpp", "pt_leafbvh.h",
                "pt_leafbvh.cpp", "pt_leafskip.cpp", "pt_scene_layout.h", "pt_scene_layout.cpp", "pt_rect_plan.h",
                "pt_rect_plan.cpp", "pt_view_plan.h", "pt_view_plan.cpp", "pt_query_plan.h", "pt_step_addr.h", "pt_wf_plan.h",
-               "pt_wf_queue.h", "pt_wf_stage.h", "pt_occupancy.h", "Makefile"]
+               "pt_wf_queue.h", "pt_wf_stage.h", "pt_occupancy.h", "pt_build.hip", "pt_capi_build.hip", "pt_build.h",
+               "pt_lbvh_host.cpp", "Makefile"]
 MODE_AUTO, MODE_MEGAKERNEL, MODE_WAVEFRONT = 0, 1, 2
 MATH_FNS = ["sin", "cos", "tan", "acos", "log2", "exp2", "pow", "sqrt", "div", "hash1u", "hash1", "hash2x",
             "hash2y", "min", "max", "ray_inv"]
@@ -48,6 +49,16 @@ class SceneInfo(ctypes.Structure):
 
     def as_dict(self):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+class BuildParams(ctypes.Structure):
+    """pt_build_params (16 B): the LBVH's leaf size and whether the emitters go under the root."""
+    _fields_ = [("max_leaf", ctypes.c_uint32), ("isolate_emitters", ctypes.c_uint32), ("profile", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
+
+
+def _build_params(max_leaf, isolate_emitters, profile=False) -> BuildParams:
+    return BuildParams(_uint(max_leaf, "max_leaf"), 1 if isolate_emitters else 0, 1 if profile else 0, 0)
 
 
 class RadianceParams(ctypes.Structure):
@@ -615,6 +626,13 @@ def load_library():
     L.pt_bvh_build.argtypes = [p, sz, p, sz, p, sz, ctypes.POINTER(sz)]
     L.pt_bvh_build_sah.argtypes = [p, sz, p, sz, p, sz, ctypes.POINTER(sz)]
     L.pt_bvh_build_sah2.argtypes = [p, sz, p, sz, p, sz, p, sz, ctypes.POINTER(sz)]
+    bpp = ctypes.POINTER(BuildParams)
+    L.pt_build_defaults.argtypes = [bpp]
+    L.pt_bvh_build_lbvh.argtypes = [p, sz, bpp, p, sz, ctypes.POINTER(sz)]
+    L.pt_scene_create_mesh.argtypes = [p, sz, bpp, i, ctypes.POINTER(p)]
+    L.pt_scene_export_bvh.argtypes = [p, p, sz, ctypes.POINTER(sz)]
+    for fn in ("pt_build_defaults", "pt_bvh_build_lbvh", "pt_scene_create_mesh", "pt_scene_export_bvh"):
+        getattr(L, fn).restype = i
     L.pt_tonemap_async.argtypes = [p, p, sz, u32, p, p]
     L.pt_readback_async.argtypes = [p, p, sz, p, p]
     L.pt_render_image.argtypes = [p, p, u32, u32, u32, i, i, p, p]
@@ -755,6 +773,34 @@ class Scene:
         _check(self._lib.pt_scene_create(_ptr(self.triangle_data), self.triangle_data.size, _ptr(self.bvh_data),
                                          self.bvh_data.size, device, ctypes.byref(h)))
         self._h = h
+
+    @classmethod
+    def from_mesh(cls, triangle_data, max_leaf: int = 4, isolate_emitters: bool = True, device: int = 0,
+                  profile: bool = False) -> "Scene":
+        """pt_scene_create_mesh: the scene from triangle_data alone — its tree (the LBVH of include/pt_hip.h)
+        and device records are built on the GPU.  A traversal scene (no mailbox, leaf chunks, leaf pass or
+        remainders); export_bvh() returns its tree in the reference's packed layout.  profile: the build's kernels are
+        timed (profile_read() gives the time per stage, "k_build_sort", ...) and the timing stays enabled."""
+        self = cls.__new__(cls)
+        self._lib = load_library()
+        self.triangle_data = _f32(triangle_data)
+        self.bvh_data = None
+        self.device = device
+        prm = _build_params(max_leaf, isolate_emitters, profile)
+        h = ctypes.c_void_p()
+        _check(self._lib.pt_scene_create_mesh(_ptr(self.triangle_data), self.triangle_data.size, ctypes.byref(prm), device,
+                                              ctypes.byref(h)))
+        self._h = h
+        return self
+
+    def export_bvh(self) -> np.ndarray:
+        """pt_scene_export_bvh: the packed bvh_data of a scene made by from_mesh — what bvh_build_lbvh returns
+        for the same triangle_data and parameters."""
+        n = ctypes.c_size_t(0)
+        _check(self._lib.pt_scene_export_bvh(self._h, None, 0, ctypes.byref(n)))
+        out = np.empty(n.value, np.float32)
+        _check(self._lib.pt_scene_export_bvh(self._h, _ptr(out), out.size, ctypes.byref(n)))
+        return out
 
     def close(self):
         if getattr(self, "_h", None):
@@ -1632,6 +1678,19 @@ def selftest_valu(iters: int = 20000, reps: int = 5, packed: int = 0, device: in
     n = ctypes.c_uint64(0)
     _check(load_library().pt_selftest_valu(device, iters, reps, int(packed), ctypes.byref(ms), ctypes.byref(n)))
     return float(ms.value), int(n.value)
+
+
+def bvh_build_lbvh(triangle_data, max_leaf: int = 4, isolate_emitters: bool = True) -> np.ndarray:
+    """pt_bvh_build_lbvh: the LBVH of include/pt_hip.h over the records of a packed triangle_data, built on
+    the host (no GPU) -> packed bvh_data (f32).  Scene.from_mesh builds the same tree on the device."""
+    L = load_library()
+    t = _f32(triangle_data)
+    prm = _build_params(max_leaf, isolate_emitters)
+    n = ctypes.c_size_t(0)
+    _check(L.pt_bvh_build_lbvh(_ptr(t), t.size, ctypes.byref(prm), None, 0, ctypes.byref(n)))
+    out = np.empty(n.value, np.float32)
+    _check(L.pt_bvh_build_lbvh(_ptr(t), t.size, ctypes.byref(prm), _ptr(out), out.size, ctypes.byref(n)))
+    return out
 
 
 def bvh_build(vertices, tris, sah: bool = False, isolate=None) -> np.ndarray:

@@ -836,6 +836,83 @@ int pt_bvh_build_sah2(const double* vertices, size_t vertex_count, const int32_t
                       const uint8_t* isolate_material, size_t material_count, float* bvh_out, size_t bvh_cap,
                       size_t* bvh_len);
 
+/* ---------------------------------------------------------------------------------------------
+ * The LBVH (SURVEY.md §8(f)'s fast mode beside SAH): a linear BVH over Morton keys, built from the
+ * packed triangle_data alone — on the host by pt_bvh_build_lbvh, on the device by pt_scene_create_mesh.
+ * Both write the SAME tree, byte for byte; the rules below define it without reference to how either
+ * computes it.  f32 arithmetic throughout, every operation rounded once (no contraction), IEEE division.
+ *
+ * Input.  triangle_data as src/packer.ts:4-81 packs it: the 16-float header, nverts = tri[0] f32
+ *   vertices from tri[2], the index records (i0, i1, i2, material) of all objects contiguous from tri[3]
+ *   to tri[4], nobj = tri[1] materials of 15 floats from tri[4], vertex normals from tri[5].  Record r is
+ *   the r-th group of four floats of the index section and T = (tri[4] - tri[3]) / 4 their count.  The
+ *   header is checked as pt_scene_create checks it, and: tri[3] >= 16, tri[3] <= tri[4], the section a
+ *   whole number of records, T >= 1.  A vertex index (1-based, read as WGSL i32(f32)) outside [1, nverts],
+ *   a material outside [0, nobj), or a non-finite coordinate of a referenced vertex: PT_ERR_INVALID.
+ * Order of floats.  Every min and max below is taken in the total order of the finite floats in which
+ *   -0 < +0 (so neither depends on the order of evaluation); NaN coordinates of vertices no record
+ *   references are skipped.
+ * Flagged materials.  Material m is an emitter when Ke.x + Ke.y + Ke.z > 0, summed in f32 from left to
+ *   right (the Node host's rule, program-raymarch.wgsl:136).  With isolate_emitters set and both flagged
+ *   and unflagged records present, the root's left child is ONE leaf of all flagged records in record
+ *   order and its right child the tree over the rest (pt_bvh_build_sah2's convention and reason).
+ *   Otherwise the tree is over all records.
+ * Keys.  lo, hi: min and max over all vertices of the vertex section; they are also the outer bounds
+ *   bvh[0..5], unpadded.  Per record and axis: c = (mn + mx) * 0.5f of its three vertices' box;
+ *   ext = hi - lo; inv = ext > 0 ? 1024.0f / ext : 0.0f; x = (c - lo) * inv;
+ *   q = x >= 0 ? (uint32_t)fminf(x, 1023.0f) : 0   (a NaN x, from inf * 0, gives 0);
+ *   morton = spread(qx) << 2 | spread(qy) << 1 | spread(qz), spread moving bit k to bit 3k;
+ *   key = (uint64_t)morton << 32 | r.  Keys are unique, so their sorted order is unique.
+ * Topology.  The binary radix tree of the sorted keys of the records the tree is over: for sorted
+ *   positions [a, b], a < b, let p = clz64(key[a] ^ key[b]); the split is after the largest s in [a, b)
+ *   with clz64(key[a] ^ key[s]) > p (clz64(0) = 64); the left child is [a, s], the right [s + 1, b].
+ * Leaves.  The tree's top node has depth 1; under an emitter root the radix root has depth 2.  A radix
+ *   node of at most max_leaf records (1..8) whose parent holds more than max_leaf is a leaf of its records
+ *   in sorted order (an emitter root always counts as such a parent).  A radix node at depth PT_LBVH_MAX_DEPTH is
+ *   a leaf whatever it holds, so max_stack <= PT_LBVH_MAX_DEPTH - 1 stays below the device stack.  If the
+ *   whole tree would be one leaf of n records, the root gets two leaves instead, the first n / 2 records
+ *   and the rest, each with the box of all n (pt_bvh_build_sah's rule; n = 1: an empty left leaf, zero box).
+ * Boxes.  A child's box is the min and max of the f32 vertices of the records below it, then moved one
+ *   f32 ulp outward on every axis (nextafterf towards -inf / +inf).  An empty child keeps zeros.
+ * Packed form.  src/packer.ts:83-137 as pt_bvh_build_sah writes it: bounds, then pre-order nodes of 17
+ *   floats, the left child at o + 17: (0, 0, o + 17, right offset, -2, left box, right box); a leaf is
+ *   (1, 0, -1, -1, 4n), twelve zeros, then its records' four floats as triangle_data holds them.
+ * --------------------------------------------------------------------------------------------- */
+#define PT_LBVH_MAX_DEPTH 28
+typedef struct {
+    uint32_t max_leaf;          /* 1..8 */
+    uint32_t isolate_emitters;  /* 0 | 1 */
+    uint32_t profile;           /* 0 | 1: pt_scene_create_mesh times its kernels as if pt_profile_enable(scene, 1) had
+                                   been called before the build — pt_profile_read then gives the time per stage
+                                   ("k_build_bounds", "_keys", "_sort", "_karras", "_depth", "_level", "_offsets",
+                                   "_emit"; a stage's launches share its name) — and leaves the timing enabled */
+    uint32_t reserved;          /* 0 */
+} pt_build_params;              /* 16 B */
+/* max_leaf 4, isolate_emitters 1, profile 0. */
+int pt_build_defaults(pt_build_params* params);
+
+/* The LBVH above, built on the host (no GPU) top-down from its definition.  params NULL = the defaults;
+ * max_leaf outside 1..8, isolate_emitters or profile > 1 (profile is ignored here) or the reserved word set:
+ * PT_ERR_INVALID.  Size query and
+ * 2^24-float limit as pt_bvh_build_sah. */
+int pt_bvh_build_lbvh(const float* triangle_data, size_t triangle_len, const pt_build_params* params, float* bvh_out,
+                      size_t bvh_cap, size_t* bvh_len);
+
+/* A scene from the mesh alone: triangle_data is uploaded once and the LBVH above, its device records
+ * (nodes, triangle records, vertex normals) and its packed form are built ON THE DEVICE; materials and the
+ * light table, O(objects + emitters), on the host as pt_scene_create makes them (a mesh without emissive
+ * triangles is PT_ERR_INVALID here).  No 2^24-float limit.  The scene is a traversal scene: no mailbox,
+ * replay tree, leaf chunks, leaf pass or leaf remainders — the configuration options leaf_skip=0 and
+ * leaf_bvh=0 run on a packed scene — so even a Cornell box made this way runs k_wf_trace, not the fused
+ * step kernel; small scenes build on the host in microseconds and pt_scene_create remains their route.
+ * Every render, query and gather call takes the scene as any other.  params as pt_bvh_build_lbvh. */
+int pt_scene_create_mesh(const float* triangle_data, size_t triangle_len, const pt_build_params* params, int device,
+                         pt_scene** scene_out);
+/* The packed tree of a scene made by pt_scene_create_mesh (size query as pt_bvh_build): what
+ * pt_bvh_build_lbvh returns for the same input.  PT_ERR_INVALID for a scene made by pt_scene_create, and
+ * at or above 2^24 floats, where the format's f32 offsets stop being exact. */
+int pt_scene_export_bvh(pt_scene* scene, float* bvh_out, size_t bvh_cap, size_t* bvh_len);
+
 /* Kernel timing (no counterpart in the reference, which has no GPU timing): while enabled,
  * every kernel the scene launches is bracketed by two HIP events on the launch stream (no
  * synchronisation, a few microseconds per launch).  enable != 0 also discards earlier
